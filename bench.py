@@ -1,19 +1,27 @@
 """bench.py -- train samples/s of ViDAR's hot path (6-cam images -> ResNet101-DCNv2 + FPN -> BEV encode ->
 latent render -> occupancy head -> ray-march / chamfer losses -> backward -> AdamW) on N MI355X.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 One process per GPU, DDP gradient all-reduce over RCCL.  Prints ONE JSON line on rank 0 (the last line of
-its stdout) with the driver contract fields plus
+its stdout) with the driver contract fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`
+= milliseconds of one timed step) plus
   `roofline`         the dominant HIP kernel of the SURVEY 8(a) path, timed live with HIP events on the launch stream
                      inside the timed region; `traffic` = calibrated PMC bytes (profiles/pmc_traffic.json);
-  `configs`          short records of BASELINE.json's other named configs, timed in the same process (every N);
-  `ddp`              DDP's bucket accounting incl. the buckets it rebuilds after the first step (N > 1);
+  `ddp`              the gradient exchange's bucket accounting (N > 1; with --full also `allreduce_alone_ms`).
+A plain run does nothing else: set up, warm up, time --steps steps, write --dump-outputs, print the line.
+With --full it also measures, after the timed region and in the same process:
+  `configs`          short records of BASELINE.json's other named configs (every N);
+  `ddp_ab`           the other gradient-exchange modes on the headline config (N > 1);
   `roofline_kernels` per-kernel rooflines at the BASELINE shapes (dvr family up to the c4 stress shape, MSDA, KNN; N = 1);
+  `roofline_gemm`    the MFMA GEMM against the library kernel at two shapes (N = 1);
   `cpu_baseline`     op-level, full-size CPU rows of the oracle port next to the GPU's own times (rank 0, N = 1, a
                      child process outside the timed region).
+--dump-outputs DIR writes what the LAST timed step returned on rank 0 -- the total loss and every loss term
+(float64) -- as DIR/<name>.npy, so that two builds can be compared output for output: the inputs are seeded (the
+same arguments give the same inputs), and those losses depend on every earlier step's backward and AdamW update.
 A "sample" = one 5-frame x 6-camera sequence (global batch = number of GPUs x --samples-per-gpu; the reference asserts
 1 sample per GPU: detectors/vidar.py:306)."""
 from __future__ import annotations
@@ -52,7 +60,7 @@ def pmc_traffic(name):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=8, help="number of timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="vidar_1_8_nusc_1future")
     ap.add_argument("--rays-per-frame", type=int, default=30000)
@@ -77,8 +85,8 @@ def parse():
                             "mem_efficient_vidar_1_8_nusc_3future,vidar_OpenScene_mini_full_3future,"
                             "vidar_1_8_nusc_3future@1:bf16x3,"
                             "vidar_full_nusc_1future@2,vidar_full_nusc_1future@4,vidar_full_nusc_1future@8",
-                    help="comma-separated `config[@samples_per_gpu][:gemm][+weights][!]` entries timed after the main one in the same "
-                         "run (short records under `configs`, each with its peak device memory): BASELINE.json's other "
+                    help="with --full: comma-separated `config[@samples_per_gpu][:gemm][+weights][!]` entries timed after the main "
+                         "one in the same run (short records under `configs`, each with its peak device memory): BASELINE.json's other "
                          "named configs -- the north star's target sentence names vidar_1_8_nusc_3future (and the "
                          "reference's memory-efficient variant of it, README.md:143-148); OpenScene = 8 cameras; "
                          ":bf16x3 = the split-bf16 MFMA GEMM path (a labelled second record, the headline stays fp32); "
@@ -105,7 +113,16 @@ def parse():
     ap.add_argument("--no-gemm-tuning", action="store_true",
                     help="leave the library GEMMs on their default heuristics (A/B of vidar_amd/gemm_tuning.py)")
     ap.add_argument("--tunableop-file", help="where TunableOp writes the solutions it found (default /tmp/...)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the auxiliary measurements after the timed region: the extra configs, the other "
+                         "gradient-exchange modes, the per-kernel and GEMM rooflines and the CPU baseline (off by "
+                         "default: a plain run times the headline config only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the losses the last timed step returned as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def relaunch_command(args, argv, port=None):
@@ -535,6 +552,15 @@ def gemm_rooflines(dev):
     return rows
 
 
+def timed_steps_keep_last(step, steps, warmup, grouped, cuda, **kw):
+    """timed_steps -> (seconds, what the LAST call of `step` returned); only a reference is kept, no synchronisation"""
+    last = [None]
+
+    def call():
+        last[0] = step()
+    return timed_steps(call, steps, warmup, grouped, cuda, **kw), last[0]
+
+
 def timed_steps(step, steps, warmup, grouped, cuda, after_warmup=None, markers=None):
     """the contract's timing: `warmup` untimed steps, then EXACTLY `steps` steps bracketed by a barrier +
     synchronize on both sides; -> seconds, MAX over ranks (device-agnostic: the gloo test drives it on CPU)"""
@@ -621,16 +647,32 @@ def make_batch(cfg, args, rank, dev, spg=None):
     return batch
 
 
+def dump_outputs(out_dir, result):
+    """--dump-outputs: what the last timed step returned, as <out_dir>/loss_total.npy and <out_dir>/loss_<term>.npy
+    (float64 [1] each: the summed loss and every loss term).  They depend on every earlier step's backward and update.
+    Two runs agree to a tolerance, not bit for bit: the backward kernels accumulate with fp32 atomics, and AdamW carries
+    that rounding into the weights (losses ~1e-4 apart after a dozen steps).  Gradients and updated parameters are not
+    written: near-zero gradients change sign under that rounding, so single elements of either differ by 100 %."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    total, parts = result
+    arrays = {"loss_total": total}
+    arrays.update({f"loss_{k}": v for k, v in sorted(parts.items())})
+    for name, t in arrays.items():
+        np.save(out / f"{name}.npy", t.detach().double().reshape(1).cpu().numpy())
+
+
 def run_config(name, args, rank, local, world, dev, steps, warmup, with_markers, spg=None, gemm_mode=None, tune=True,
-               weights=None, ddp_mode=None):
-    """build the model of one named config, time `steps` training steps -> dict(elapsed, ops, ddp, cfg, peak_mem_gb)"""
+               weights=None, ddp_mode=None, dump_dir=None):
+    """build the model of one named config, time `steps` training steps -> dict(elapsed, ops, ddp, cfg, peak_mem_gb);
+    dump_dir: write the step's outputs there (rank 0; dump_outputs)"""
     from vidar_amd import gemm as G
     prev = G.set_mode(gemm_mode or G.mode())
     try:
         torch.cuda.reset_peak_memory_stats(dev)
         t0 = time.perf_counter()
         r = _run_config(name, args, rank, local, world, dev, steps, warmup, with_markers, spg, tune, weights or args.weights,
-                        ddp_mode)
+                        ddp_mode, dump_dir)
         if rank == 0:
             print(f"[bench] {name} spg={spg or args.samples_per_gpu} gemm={G.mode()} weights={r['weights']['mode']}: "
                   f"{r['elapsed'] / steps * 1e3:.1f} ms/step "
@@ -650,7 +692,7 @@ GEMM_DTYPE = {"lib": "f32", "auto": "f32", "f32": "f32",
 
 
 def _run_config(name, args, rank, local, world, dev, steps, warmup, with_markers, spg=None, tune=True, weights="init",
-                ddp_mode=None):
+                ddp_mode=None, dump_dir=None):
     from vidar_amd import gemm_tuning
     from vidar_amd import train as T
     from vidar_amd import weights as W
@@ -682,15 +724,18 @@ def _run_config(name, args, rank, local, world, dev, steps, warmup, with_markers
         gemm_tuning.thaw()
     else:
         gemm_tuning.freeze()
-    elapsed = timed_steps(lambda: T.train_step(ddp, opt, batch, cfg["grad_clip"]), steps, warmup, grouped, True,
-                          after_warmup=after_warmup,
-                          markers=(lambda k: _hip().vidar_marker(k, None)) if with_markers else None)
+    elapsed, last = timed_steps_keep_last(lambda: T.train_step(ddp, opt, batch, cfg["grad_clip"]), steps, warmup, grouped,
+                                          True, after_warmup=after_warmup,
+                                          markers=(lambda k: _hip().vidar_marker(k, None)) if with_markers else None)
     TIMER.enabled = False
     ops = TIMER.summary() if rank == 0 else {}
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, last)
+    del last
     info = ddp_info(ddp, world) if grouped else None
     del batch, ddp, opt, model
     torch.cuda.empty_cache()
-    if info and "allreduce_bytes_per_step" in info:
+    if args.full and info and "allreduce_bytes_per_step" in info:
         info["allreduce_alone_ms"] = allreduce_alone_ms(info["allreduce_bytes_per_step"], dev)
     return dict(elapsed=elapsed, ops=ops, ddp=info, cfg=cfg, weights=wrep)
 
@@ -698,10 +743,12 @@ def _run_config(name, args, rank, local, world, dev, steps, warmup, with_markers
 def main():
     args = parse()
     cmd = relaunch_command(args, sys.argv[1:])
-    if cmd is not None:                  # `python bench.py --gpus N` called plainly: become N RCCL ranks
+    if cmd is not None:                  # `python bench.py --gpus N` called plainly: run N RCCL ranks as a child
         print(f"[bench] --gpus {args.gpus} without a launcher: re-running as {' '.join(cmd[1:8])} ...", file=sys.stderr,
               flush=True)
-        os.execv(cmd[0], cmd)
+        import subprocess
+        rc = subprocess.run(cmd).returncode
+        sys.exit(128 - rc if rc < 0 else rc)             # killed by signal n: the shell's 128 + n
     if args.cpu_baseline_only:
         # never drive the host out of memory: cap this child's address space (a full-size CPU step took a box down)
         try:
@@ -730,12 +777,12 @@ def main():
     spg = args.samples_per_gpu
 
     main_run = run_config(args.config, args, rank, local, world, dev, args.steps, args.warmup, with_markers=True,
-                          gemm_mode=args.gemm)
+                          gemm_mode=args.gemm, dump_dir=args.dump_outputs)
     elapsed, ops, cfg = main_run["elapsed"], main_run["ops"], main_run["cfg"]
-    # the gradient-exchange modes side by side on the headline config, whenever a process group exists: which of them is
-    # fastest at N ranks is decided by THIS measurement (on one rank they only differ by host overhead)
+    # --full: the gradient-exchange modes side by side on the headline config, whenever a process group exists: which of
+    # them is fastest at N ranks is decided by THIS measurement (on one rank they only differ by host overhead)
     ddp_ab = []
-    if grouped and not args.no_ddp_ab:
+    if args.full and grouped and not args.no_ddp_ab:
         main_mode = os.environ.get("VIDAR_DDP", "flat")
         ddp_ab.append({"mode": main_mode, "ms_per_step": elapsed / args.steps * 1e3, "steps": args.steps, "headline": True})
         for mode in T.DDP_MODES:
@@ -751,7 +798,7 @@ def main():
                 torch.cuda.empty_cache()
     extras = []
     t_extras = time.perf_counter()
-    for entry in [c for c in args.extra_configs.split(",") if c]:
+    for entry in [c for c in args.extra_configs.split(",") if c] if args.full else []:
         rigor = entry.endswith("!")
         entry = entry.rstrip("!")
         xsteps, xwarm = (args.steps, args.warmup) if rigor else (args.extra_steps, args.extra_warmup)
@@ -858,9 +905,9 @@ def main():
             out["ddp"] = main_run["ddp"]
         if ddp_ab:
             out["ddp_ab"] = ddp_ab
-        # the two auxiliary legs run after the timed region; a failure in one of them is reported in the line
+        # --full: the two auxiliary legs run after the timed region; a failure in one of them is reported in the line
         # (and on stderr) instead of costing the measured throughput its record
-        if world == 1 and not args.no_kernel_rooflines and not grouped:
+        if args.full and world == 1 and not args.no_kernel_rooflines and not grouped:
             print("[bench] kernel rooflines ...", file=sys.stderr, flush=True)
             try:
                 out["roofline_kernels"] = kernel_rooflines(dev)
@@ -874,7 +921,7 @@ def main():
                 import traceback
                 traceback.print_exc()
                 out["roofline_gemm_error"] = f"{type(e).__name__}: {e}"
-        if world == 1 and not args.no_cpu_baseline and not grouped:
+        if args.full and world == 1 and not args.no_cpu_baseline and not grouped:
             print("[bench] cpu baseline (child process) ...", file=sys.stderr, flush=True)
             try:
                 out["cpu_baseline"] = cpu_baseline_record(args, ops, args.steps, out.get("roofline_kernels"))

@@ -30,11 +30,48 @@ def test_driver_flags_parse_and_defaults_are_single_gpu():
         a = bench.parse()
         assert a.gpus == 1 and a.steps > 0 and a.warmup >= 0 and a.config == "vidar_1_8_nusc_1future"
         assert not a.cpu_baseline_full                      # the full-size CPU step is opt-in
+        assert not a.full and a.dump_outputs is None        # a plain run times the headline only and writes nothing
         sys.argv = ["bench.py", "--gpus", "8", "--steps", "20", "--warmup", "5"]
         a = bench.parse()
         assert (a.gpus, a.steps, a.warmup) == (8, 20, 5)
+        sys.argv = ["bench.py", "--steps", "0"]
+        with pytest.raises(SystemExit):
+            bench.parse()
     finally:
         sys.argv = old
+
+
+def test_dump_outputs_writes_what_the_last_timed_step_returned(tmp_path, monkeypatch):
+    """--dump-outputs through _run_config: the files hold the return value of the LAST timed call of train_step (not
+    a warm-up step, not an extra step), losses as float64 [1] files, and the step runs exactly warmup + steps times"""
+    sys.path.insert(0, str(ROOT))
+    import numpy as np
+    import bench
+    from vidar_amd import train as T
+    from vidar_amd import weights as W
+    calls = []
+
+    def fake_step(model, opt, batch, max_norm=35.0):
+        calls.append(1)
+        n = float(len(calls))
+        return torch.tensor(n), {"frame.0.loss": torch.tensor(n / 4), "frame.1.loss": torch.tensor(3 * n / 4)}
+
+    monkeypatch.setattr(T, "build_model", lambda cfg: torch.nn.Linear(4, 2))
+    monkeypatch.setattr(T, "train_step", fake_step)
+    monkeypatch.setattr(W, "prepare", lambda model, batch, mode="init", checkpoint=None: {"mode": mode})
+    monkeypatch.setattr(bench, "make_batch", lambda cfg, args, rank, dev, spg=None: {})
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    args = type("A", (), dict(no_backbone=True, full=False, samples_per_gpu=1))()
+    out = tmp_path / "out"
+    r = bench._run_config("vidar_1_8_nusc_1future", args, 0, 0, 1, torch.device("cpu"), steps=3, warmup=2,
+                          with_markers=False, weights="init", dump_dir=str(out))
+    assert len(calls) == 5 and r["elapsed"] >= 0
+    names = sorted(f.name for f in out.glob("*.npy"))
+    assert names == ["loss_frame.0.loss.npy", "loss_frame.1.loss.npy", "loss_total.npy"]
+    got = {n: np.load(out / n) for n in names}
+    assert all(a.dtype == np.float64 and a.shape == (1,) for a in got.values())
+    assert got["loss_total.npy"][0] == 5.0 and got["loss_frame.0.loss.npy"][0] == 1.25
+    assert got["loss_frame.1.loss.npy"][0] == 3.75
 
 
 def test_pmc_traffic_is_backed_by_committed_profiles():
@@ -46,8 +83,9 @@ def test_pmc_traffic_is_backed_by_committed_profiles():
     nbytes, src = bench.pmc_traffic("msda_bwd[L=4,P=8]")
     assert nbytes and nbytes > 7.5e8                        # at least the algorithmic bytes (756 MB at 7 680 queries / camera)
     # counted on the access pattern AND at the size the in-model kernel time belongs to: spatially coherent queries
-    # (round 4), 7 680 padded visible queries per camera (round 5; the SURVEY shape has 10^4)
-    pmc_dir = "r05_pmc_msda_sca_coherent_nq7680"
+    # (round 4), 7 680 padded visible queries per camera (round 5; the SURVEY shape has 10^4), recounted at the
+    # binned backward (round 6)
+    pmc_dir = "r06_pmc_msda_sca_coherent_nq7680"
     assert pmc_dir in src and "coherent" in src and "calibration" in src and "Nq=7680" in src
     for f in ("pmc_FETCH_SIZE.csv", "pmc_WRITE_SIZE.csv"):
         assert (ROOT / "profiles" / pmc_dir / f).exists()
@@ -171,7 +209,7 @@ def test_grouped_timing_and_ddp_block_two_ranks_gloo():
 
 
 def test_plain_gpus_n_relaunches_as_n_ranks(monkeypatch):
-    """`python bench.py --gpus N` without a launcher must not silently measure ONE rank: it re-executes itself under
+    """`python bench.py --gpus N` without a launcher must not silently measure ONE rank: it runs itself, as a child, under
     torch.distributed.run with N ranks on 127.0.0.1 (the driver's own multi-GPU command line); inside a launcher
     (WORLD_SIZE set) nothing is re-launched, and a --gpus that disagrees with the launcher fails loudly."""
     sys.path.insert(0, str(ROOT))

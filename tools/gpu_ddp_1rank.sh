@@ -5,7 +5,7 @@ set -u
 cd "$(dirname "$0")/.."
 tag=${1:-ddp_1rank}; out=gpurun_out/$tag; mkdir -p $out
 VIDAR_FORCE_DDP=1 timeout 800 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 \
-  bench.py --gpus 1 --steps 10 --warmup 3 --extra-configs "" --no-cpu-baseline --no-kernel-rooflines > $out/bench_ddp_1rank.json 2> $out/bench_ddp_1rank.err
+  bench.py --gpus 1 --steps 10 --warmup 3 --full --extra-configs "" --no-cpu-baseline --no-kernel-rooflines > $out/bench_ddp_1rank.json 2> $out/bench_ddp_1rank.err
 echo "rc $?"; grep "^\[bench\]" $out/bench_ddp_1rank.err
 python - $out/bench_ddp_1rank.json <<'PY'
 import sys, json

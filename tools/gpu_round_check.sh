@@ -13,8 +13,8 @@ stamp "full GPU suite"
 timeout 900 python -m pytest tests -q -m gpu 2>&1 | tail -12 | tee $out/gpu_suite.log
 stamp "smoke"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $out/smoke.log
-stamp "bench (driver command), hard limit 480 s"
-timeout 480 python bench.py --gpus 1 --steps 20 --warmup 5 --op-table > $out/bench.json 2> $out/optable.txt
+stamp "bench --full (driver command + extra configs), hard limit 600 s"
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full --op-table > $out/bench.json 2> $out/optable.txt
 echo "rc $?"
 grep "^\[bench\]" $out/optable.txt
 python - $out/bench.json <<'PY'

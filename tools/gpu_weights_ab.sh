@@ -9,7 +9,7 @@ mkdir -p $out
 t0=$(date +%s)
 stamp() { echo "[$(( $(date +%s) - t0 )) s] $*"; }
 stamp "bench (driver command), hard limit 600 s"
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --op-table > $out/bench.json 2> $out/optable.txt
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full --op-table > $out/bench.json 2> $out/optable.txt
 echo "rc $?"
 grep "^\[bench\]" $out/optable.txt
 for w in trained_like init; do

@@ -97,8 +97,8 @@ class FlatAllReduce(torch.nn.Module):
     counts the gradients in; when the last one has arrived their flat buffer is all-reduced ASYNCHRONOUSLY (RCCL runs the
     collective on its own stream) under the history encoder's backward, and only the remaining third is exchanged after
     backward.  Same sums in the same rank order -> the same update as "flat" (tests/test_ddp_cpu.py).  Which of flat /
-    flat2 / torch is fastest at 8 ranks is a measurement bench.py makes itself whenever it runs on more than one rank
-    (`ddp_ab` in its line); on one rank the three differ only by their host overhead."""
+    flat2 / torch is fastest at 8 ranks is a measurement `bench.py --full` makes itself whenever it runs on more than one
+    rank (`ddp_ab` in its line); on one rank the three differ only by their host overhead."""
 
     def __init__(self, module, mode="flat"):
         super().__init__()
