@@ -302,13 +302,20 @@ int vidar_latent_render_gather_bwd_f32(const float* path_prob, const float* lora
  *   ray_ce     _get_grid_features :420-509 + cross_entropy(label 0) :586-592
  *   ray_gumbel dense rays :594-630 + _custom_gumbel_softmax_distance :754-773
  *   ray_argmax get_point_cloud_prediction :697-731 (test-time decode)
+ *   ray_dist   the use_dist_loss branch :575-585 (_custom_gumbel_softmax_distance on the GT rays)
  * sigma [F,Z,Y,X] f32 logits; origin [F,3]; pts [R,3] ray end points; tindex [R] f32 frame slot
- * (<0 / NaN / >=F: ray skipped); all in voxel units.  K must be 512 (ray_grid_num of the released
- * configs); step = ray_grid_step.  Outputs are per ray; reductions stay in the host framework.
+ * (<0 / NaN / >=F: ray skipped); all in voxel units.  K = ray_grid_num, 1 <= K <= vidar_ray_max_k()
+ * (65536; anything else is VIDAR_ERR_BAD_ARG): K == 512 (the released configs) runs the register-resident kernels,
+ * every other K the streamed ones, which never touch waypoints k >= K.  step = ray_grid_step.  Outputs are per ray;
+ * reductions stay in the host framework.
  *   ce[r]   = logsumexp_k(logit_k) - logit_0 over {end point, K waypoints}; valid[r] = 1 iff the
  *             end point lies strictly inside the volume (others are dropped, :464-467); lse saved.
  *   dist[r] = ((1-pn)+pn) * pd, pd = length of argmax_k(logit_k + noise[r,k]),
  *             pn = softmax mass of waypoints farther than pd;  aux[r] = {pd, pn, lse}.
+ *   ray_dist: the same rendered distance over the K + 1 logits of a GT ray -- entry 0 the sample AT the end point
+ *             with length |p - o|, entries 1..K the waypoints; noise [R, K+1] in that order, row r for ray r.  Rays are
+ *             dropped as in ray_ce (dist = gt_len = 0, valid = 0).  gt_len[r] = |p - o|, the L1 target.  aux [R,3] as
+ *             above is what the backward needs; it scatters onto the end point's corners too.
  * Backward entry points zero grad_sigma and accumulate with fp32 atomics.  All rays of a frame start at the sensor
  * origin, so the first waypoints' atomics serialise on a few hundred addresses: given a `workspace` of
  * vidar_ray_bwd_workspace_bytes(F,Z,Y,X) bytes (caller-owned device scratch on the call's device / stream, nothing
@@ -334,6 +341,21 @@ int vidar_ray_gumbel_bwd_f32(const float* sigma, const float* origin, const floa
 int vidar_ray_argmax_f32(const float* sigma, const float* origin, const float* pts,
                          const float* tindex, float* pred_dist, float* gt_dist, int F, int R, int Z,
                          int Y, int X, int K, float step, void* stream);
+int vidar_ray_dist_fwd_f32(const float* sigma, const float* origin, const float* gt_pts,
+                           const float* tindex, const float* noise /*[R,K+1]*/, float* dist,
+                           float* gt_len, float* aux /*[R,3]*/, float* valid, int F, int R, int Z,
+                           int Y, int X, int K, float step, void* stream);
+int vidar_ray_dist_bwd_f32(const float* sigma, const float* origin, const float* gt_pts,
+                           const float* tindex, const float* aux, const float* grad_dist,
+                           float* grad_sigma, int F, int R, int Z, int Y, int X, int K, float step,
+                           void* workspace, size_t workspace_bytes, void* stream);
+/* largest accepted K */
+int vidar_ray_max_k(void);
+/* Test / benchmark hook, process-wide: nonzero sends K == 512 through the streamed kernels as well (same bits: every
+ * lane adds its waypoints in the register form's order).  Returns the previous setting.  One atomic flag for the whole
+ * process, not a per-call or per-thread option: a thread that flips it changes which kernel the K == 512 calls of every
+ * other thread launch from then on (same results, different time), so production code leaves it alone. */
+int vidar_ray_force_streamed(int on);
 
 /* ---------------------------------------------------------------------------
  * Modulated deformable convolution v2 (backbone, "next" row SURVEY 8f-1).  Replaces the sampling

@@ -316,6 +316,37 @@ def bench_ray(which):
     d = ray_gumbel(sigma, o, pts, tix, noise)
     ms = timeit(lambda: torch.autograd.grad(d, sigma, torch.ones_like(d), retain_graph=True))
     report(f"ray_gumbel_bwd R={pts.shape[0]}", ms, 4 * (2 * 16 * 200 * 200 + pts.shape[0] * 4))
+    # any ray_grid_num (the streamed kernels) next to the register-resident K = 512 rows above; "512 streamed" is the
+    # same K through the streamed form.  `spread` = (max - min) / median of 5 repeats of the timed window.
+    from vidar_amd.plugin.dense_heads.ray_ops import ray_dist, force_streamed
+    import contextlib
+
+    def rep(fn, n=5):
+        ms = sorted(timeit(fn) for _ in range(n))
+        return ms[n // 2], round((ms[-1] - ms[0]) / ms[n // 2], 3)
+    R = pts.shape[0]
+    for K, step, streamed in ((512, 1.0, False), (512, 1.0, True), (1026, 1.0, False), (1024, 0.5, False)):
+        tag = f"K={K} step={step}" + (" streamed" if streamed else "")
+        with (force_streamed() if streamed else contextlib.nullcontext()):
+            ms, sp = rep(lambda: ray_ce(sigma, o, p, ti, step, K))
+            report(f"ray_ce_fwd {tag}", ms, 4 * (16 * 200 * 200 + 30000 * 5), spread=sp)
+            ce, valid = ray_ce(sigma, o, p, ti, step, K)
+            ms, sp = rep(lambda: torch.autograd.grad(ce, sigma, g, retain_graph=True))
+            report(f"ray_ce_bwd {tag}", ms, 4 * (2 * 16 * 200 * 200 + 30000 * 5), spread=sp)
+            noise = gumbel_noise(R, K)
+            ms, sp = rep(lambda: ray_gumbel(sigma, o, pts, tix, noise, step, K))
+            report(f"ray_gumbel_fwd {tag}", ms, 4 * (16 * 200 * 200 + R * (K + 4)), spread=sp)
+            d = ray_gumbel(sigma, o, pts, tix, noise, step, K)
+            ms, sp = rep(lambda: torch.autograd.grad(d, sigma, torch.ones_like(d), retain_graph=True))
+            report(f"ray_gumbel_bwd {tag}", ms, 4 * (2 * 16 * 200 * 200 + R * 4), spread=sp)
+    # the distance loss on the GT rays of ray_ce (use_dist_loss), noise [30000, K + 1]
+    for K, step in ((512, 1.0), (1024, 0.5)):
+        noise = gumbel_noise(p.shape[0], K + 1)
+        ms, sp = rep(lambda: ray_dist(sigma, o, p, ti, noise, step, K))
+        report(f"ray_dist_fwd P=30000 K={K} step={step}", ms, 4 * (16 * 200 * 200 + 30000 * (K + 11)), spread=sp)
+        dd, _, _ = ray_dist(sigma, o, p, ti, noise, step, K)
+        ms, sp = rep(lambda: torch.autograd.grad(dd, sigma, g, retain_graph=True))
+        report(f"ray_dist_bwd P=30000 K={K} step={step}", ms, 4 * (2 * 16 * 200 * 200 + 30000 * 8), spread=sp)
 
 
 def bench_gemm(which):

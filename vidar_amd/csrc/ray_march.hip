@@ -5,18 +5,33 @@
 //   ray_gumbel  : _get_grid_features on the dense voxel rays (:594-630) +
 //                 _custom_gumbel_softmax_distance (:754-773)
 //   ray_argmax  : test-time decode in get_point_cloud_prediction (:697-731)
+//   ray_dist    : the use_dist_loss branch (:575-585): _custom_gumbel_softmax_distance over the K + 1 logits
+//                 {end point, K waypoints} of the GT rays
 // The reference materialises ~8 arrays of [rays, 513] floats per call (waypoints, lengths, masks,
 // sampled logits, -inf masks, softmax); here one wave owns one ray, its 512 waypoints live in
 // registers (8 per lane) and only O(1) values per ray ever reach HBM.
 //
+// Waypoint count K = ray_grid_num, two forms:
+//   K == 512        register-resident (the released configs): the kernels without a suffix.
+//   1 <= K <= kKMax streamed (`*_any_kernel`): the wave walks the ray in passes of 64 waypoints (32 in the backward) and
+//                   keeps O(1) state per lane -- pass 1 finds the max logit (and the best perturbed logit, its index and
+//                   length), pass 2 samples the logits AGAIN for the exp sums (the "mass beyond the sample" needs
+//                   pred_dist, known only after pass 1).  Waypoints k >= K are never sampled and never read noise.
+//                   Every lane adds its waypoints in the same order as the register form, so K = 512 through the
+//                   streamed form gives the same bits (tests/test_ray_options_gpu.py; vidar_ray_force_streamed).
+//   kKMax = 65536: nothing in the streamed kernels depends on K but the trip count ((k + 0.5f) is exact in fp32 far past
+//   it, noise offsets are size_t); the bound only keeps a corrupt argument from becoming a minutes-long launch.  The
+//   longest ray of the 200 x 200 x 16 volume is its 283-voxel diagonal = 2264 waypoints at step 0.125.
+//
 // Geometry (voxel units, fp32, same operation order as the reference):
-//   rhat = (p - o)/|p - o| ;  s_k = o + rhat * (k + 0.5) * step, k = 0..K-1 (K = ray_grid_num = 512)
+//   rhat = (p - o)/|p - o| ;  s_k = o + rhat * (k + 0.5) * step, k = 0..K-1 (K = ray_grid_num)
 //   normalised g = s / (X,Y,Z) * 2 - 1 ; a waypoint is masked (-inf) iff any g <= -1 or g >= 1
 //   trilinear sample of sigma[Z,Y,X] at pixel ((g+1)*size-1)/2, zero padding, align_corners=False.
 // sigma layout: [F, Z, Y, X] f32 (x fastest) -- the head's own [bs,F,16,200,200] view.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include <atomic>
 
 #include "vidar_hip.h"
 #include "vidar_common.h"
@@ -26,6 +41,7 @@ namespace {
 constexpr int kWave = 64;
 constexpr int kPerLane = 8;           // K = 512 waypoints
 constexpr int kK = kWave * kPerLane;
+constexpr int kKMax = 65536;
 constexpr int kThreads = 256;
 constexpr int kRaysPerBlock = kThreads / kWave;
 
@@ -156,6 +172,27 @@ __device__ __forceinline__ void lane_logits(const float* __restrict__ vol, const
   }
 }
 
+// logit (and length) of waypoint k, for the streamed kernels
+__device__ __forceinline__ float logit_at(const float* __restrict__ vol, const Ray& r, const VolDims& v,
+                                          float step, int k, float& len) {
+  float sx, sy, sz;
+  waypoint(r, k, step, sx, sy, sz);
+  const Tri t = make_tri(sx, sy, sz, v);
+  len = dist_to(r, sx, sy, sz);
+  return t.masked ? kNegInf : tri_load(vol, t);
+}
+
+// (value, index, length) arg-max across the wave, first index wins ties
+__device__ __forceinline__ void wave_argmax(float& best, int& bi, float& blen) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) {
+    const float ob = __shfl_xor(best, s, kWave);
+    const int oi = __shfl_xor(bi, s, kWave);
+    const float ol = __shfl_xor(blen, s, kWave);
+    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; blen = ol; }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // GT-ray march + cross entropy on the end-point sample
 // ---------------------------------------------------------------------------------------------
@@ -191,11 +228,42 @@ __global__ __launch_bounds__(kThreads) void ray_ce_fwd_kernel(
   }
 }
 
-__global__ __launch_bounds__(kThreads) void ray_ce_bwd_kernel(
+// streamed form, any K
+__global__ __launch_bounds__(kThreads) void ray_ce_fwd_any_kernel(
+    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ gt,
+    const float* __restrict__ tindex, float* __restrict__ ce, float* __restrict__ lse_out,
+    float* __restrict__ valid, int R, VolDims v, float step, int K) {
+  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
+  if (r >= R) return;
+  const int lane = threadIdx.x % kWave;
+  const Ray ray = load_ray(origin, gt, tindex, r, v);
+  const Tri t0 = make_tri(ray.px, ray.py, ray.pz, v);
+  const bool ok = ray.f >= 0 && !t0.masked;
+  float out_ce = 0.f, out_lse = 0.f;
+  if (ok) {
+    const float* vol = sigma + (size_t)ray.f * v.Z * v.Y * v.X;
+    const float f0 = tri_load(vol, t0);
+    float m = f0, len;
+    for (int k = lane; k < K; k += kWave) m = fmaxf(m, logit_at(vol, ray, v, step, k, len));
+    m = wave_max(m);
+    float s = (lane == 0) ? expf(f0 - m) : 0.f;
+    for (int k = lane; k < K; k += kWave) s += expf(logit_at(vol, ray, v, step, k, len) - m);
+    s = wave_sum(s);
+    out_lse = m + logf(s);
+    out_ce = out_lse - f0;
+  }
+  if (lane == 0) {
+    ce[r] = out_ce; lse_out[r] = out_lse; valid[r] = ok ? 1.f : 0.f;
+  }
+}
+
+// K512: the fixed 16 passes of the register form's K; otherwise ceil(K / 32) passes with a tail predicate
+template <bool K512>
+__device__ __forceinline__ void ray_ce_bwd_body(
     const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ gt,
     const float* __restrict__ tindex, const float* __restrict__ lse_in,
     const float* __restrict__ grad_ce, float* __restrict__ grad_sigma, int R, VolDims v,
-    float step, int ncopies) {
+    float step, int ncopies, int K) {
   const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
   if (r >= R) return;
   const int lane = threadIdx.x % kWave;
@@ -210,12 +278,29 @@ __global__ __launch_bounds__(kThreads) void ray_ce_bwd_kernel(
   const float lse = lse_in[r];
   if (lane == 0) tri_scatter(gvol, t0, g * (expf(tri_load(vol, t0) - lse) - 1.f));
   const int cx = lane & 1;
-  for (int j = 0; j < 2 * kPerLane; ++j) {             // 32 waypoints per pass, a lane pair per waypoint
+  const int passes = K512 ? 2 * kPerLane : (K + kWave / 2 - 1) / (kWave / 2);
+  for (int j = 0; j < passes; ++j) {                   // 32 waypoints per pass, a lane pair per waypoint
+    const int k = (lane >> 1) + j * (kWave / 2);
+    if (!K512 && k >= K) break;                        // only in the last pass
     float sx, sy, sz;
-    waypoint(ray, (lane >> 1) + j * (kWave / 2), step, sx, sy, sz);
+    waypoint(ray, k, step, sx, sy, sz);
     const Tri t = make_tri(sx, sy, sz, v);
     if (!t.masked) tri_scatter_x(gvol, t, g * expf(tri_load(vol, t) - lse), cx);
   }
+}
+__global__ __launch_bounds__(kThreads) void ray_ce_bwd_kernel(
+    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ gt,
+    const float* __restrict__ tindex, const float* __restrict__ lse_in,
+    const float* __restrict__ grad_ce, float* __restrict__ grad_sigma, int R, VolDims v,
+    float step, int ncopies) {
+  ray_ce_bwd_body<true>(sigma, origin, gt, tindex, lse_in, grad_ce, grad_sigma, R, v, step, ncopies, kK);
+}
+__global__ __launch_bounds__(kThreads) void ray_ce_bwd_any_kernel(
+    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ gt,
+    const float* __restrict__ tindex, const float* __restrict__ lse_in,
+    const float* __restrict__ grad_ce, float* __restrict__ grad_sigma, int R, VolDims v,
+    float step, int ncopies, int K) {
+  ray_ce_bwd_body<false>(sigma, origin, gt, tindex, lse_in, grad_ce, grad_sigma, R, v, step, ncopies, K);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -275,11 +360,144 @@ __global__ __launch_bounds__(kThreads) void ray_gumbel_fwd_kernel(
   }
 }
 
-__global__ __launch_bounds__(kThreads) void ray_gumbel_bwd_kernel(
+// streamed form, any K
+__global__ __launch_bounds__(kThreads) void ray_gumbel_fwd_any_kernel(
+    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
+    const float* __restrict__ tindex, const float* __restrict__ noise, float* __restrict__ dist,
+    float* __restrict__ aux, int R, VolDims v, float step, int K) {
+  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
+  if (r >= R) return;
+  const int lane = threadIdx.x % kWave;
+  const Ray ray = load_ray(origin, pts, tindex, r, v);
+  float o_dist = 0.f, o_pd = 0.f, o_pn = 0.f, o_lse = 0.f;
+  if (ray.f >= 0) {
+    const float* vol = sigma + (size_t)ray.f * v.Z * v.Y * v.X;
+    float best = kNegInf; int bi = kKMax; float blen = 0.f;
+    float m = kNegInf;
+    for (int k = lane; k < K; k += kWave) {
+      float len;
+      const float f = logit_at(vol, ray, v, step, k, len);
+      const float z = f + noise[(size_t)r * K + k];
+      if (z > best || (z == best && k < bi)) { best = z; bi = k; blen = len; }
+      m = fmaxf(m, f);
+    }
+    wave_argmax(best, bi, blen);
+    m = wave_max(m);
+    const float pd = blen;
+    float se = 0.f, sn = 0.f;
+    for (int k = lane; k < K; k += kWave) {
+      float len;
+      const float e = expf(logit_at(vol, ray, v, step, k, len) - m);
+      se += e;
+      sn += (len > pd) ? e : 0.f;
+    }
+    se = wave_sum(se); sn = wave_sum(sn);
+    const float pn = sn / se;
+    o_pd = pd; o_pn = pn; o_lse = m + logf(se);
+    o_dist = ((1.f - pn) + pn) * pd;
+  }
+  if (lane == 0) {
+    dist[r] = o_dist;
+    aux[(size_t)r * 3 + 0] = o_pd; aux[(size_t)r * 3 + 1] = o_pn; aux[(size_t)r * 3 + 2] = o_lse;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// GT rays: the same hard gumbel sample over the K + 1 logits {end point, K waypoints} (use_dist_loss, :575-585).
+// Entry 0 is the sample AT the end point with length |p - o| (lane 0 carries it), entries 1..K the waypoints;
+// noise [R, K + 1] in that order.  Rays are dropped as in ray_ce.  Streamed, any K.  aux[r] = {pred_dist, prob_next, lse}
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void ray_dist_fwd_kernel(
+    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ gt,
+    const float* __restrict__ tindex, const float* __restrict__ noise, float* __restrict__ dist,
+    float* __restrict__ gt_len, float* __restrict__ aux, float* __restrict__ valid, int R, VolDims v, float step,
+    int K) {
+  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
+  if (r >= R) return;
+  const int lane = threadIdx.x % kWave;
+  const Ray ray = load_ray(origin, gt, tindex, r, v);
+  const Tri t0 = make_tri(ray.px, ray.py, ray.pz, v);
+  const bool ok = ray.f >= 0 && !t0.masked;
+  float o_dist = 0.f, o_len = 0.f, o_pd = 0.f, o_pn = 0.f, o_lse = 0.f;
+  if (ok) {
+    const float* vol = sigma + (size_t)ray.f * v.Z * v.Y * v.X;
+    const float* nz = noise + (size_t)r * ((size_t)K + 1);
+    const float f0 = tri_load(vol, t0);
+    const float len0 = dist_to(ray, ray.px, ray.py, ray.pz);
+    float best = kNegInf; int bi = kKMax + 1; float blen = 0.f;
+    if (lane == 0) { best = f0 + nz[0]; bi = 0; blen = len0; }
+    float m = f0;
+    for (int k = lane; k < K; k += kWave) {
+      float len;
+      const float f = logit_at(vol, ray, v, step, k, len);
+      const float z = f + nz[k + 1];
+      if (z > best || (z == best && k + 1 < bi)) { best = z; bi = k + 1; blen = len; }
+      m = fmaxf(m, f);
+    }
+    wave_argmax(best, bi, blen);
+    m = wave_max(m);
+    const float pd = blen;
+    const float e0 = (lane == 0) ? expf(f0 - m) : 0.f;
+    float se = e0, sn = (len0 > pd) ? e0 : 0.f;
+    for (int k = lane; k < K; k += kWave) {
+      float len;
+      const float e = expf(logit_at(vol, ray, v, step, k, len) - m);
+      se += e;
+      sn += (len > pd) ? e : 0.f;
+    }
+    se = wave_sum(se); sn = wave_sum(sn);
+    const float pn = sn / se;
+    o_pd = pd; o_pn = pn; o_lse = m + logf(se); o_len = len0;
+    o_dist = ((1.f - pn) + pn) * pd;
+  }
+  if (lane == 0) {
+    dist[r] = o_dist; gt_len[r] = o_len; valid[r] = ok ? 1.f : 0.f;
+    aux[(size_t)r * 3 + 0] = o_pd; aux[(size_t)r * 3 + 1] = o_pn; aux[(size_t)r * 3 + 2] = o_lse;
+  }
+}
+
+// d dist / d logit_k = pd * p_k * (ind_k - pn) on every live entry, the end point included
+__global__ __launch_bounds__(kThreads) void ray_dist_bwd_kernel(
+    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ gt,
+    const float* __restrict__ tindex, const float* __restrict__ aux, const float* __restrict__ grad_dist,
+    float* __restrict__ grad_sigma, int R, VolDims v, float step, int ncopies, int K) {
+  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
+  if (r >= R) return;
+  const int lane = threadIdx.x % kWave;
+  const float g = grad_dist[r];
+  if (g == 0.f) return;
+  const Ray ray = load_ray(origin, gt, tindex, r, v);
+  const Tri t0 = make_tri(ray.px, ray.py, ray.pz, v);
+  if (ray.f < 0 || t0.masked) return;
+  const size_t slice = (size_t)ray.f * v.Z * v.Y * v.X;
+  const float* vol = sigma + slice;
+  float* gvol = grad_sigma + (size_t)(blockIdx.x % ncopies) * v.F * v.Z * v.Y * v.X + slice;
+  const float pd = aux[(size_t)r * 3 + 0], pn = aux[(size_t)r * 3 + 1], lse = aux[(size_t)r * 3 + 2];
+  if (lane == 0) {
+    const float ind0 = dist_to(ray, ray.px, ray.py, ray.pz) > pd ? 1.f : 0.f;
+    tri_scatter(gvol, t0, g * pd * expf(tri_load(vol, t0) - lse) * (ind0 - pn));
+  }
+  const int cx = lane & 1;
+  const int passes = (K + kWave / 2 - 1) / (kWave / 2);
+  for (int j = 0; j < passes; ++j) {                   // 32 waypoints per pass, a lane pair per waypoint
+    const int k = (lane >> 1) + j * (kWave / 2);
+    if (k >= K) break;
+    float sx, sy, sz;
+    waypoint(ray, k, step, sx, sy, sz);
+    const Tri t = make_tri(sx, sy, sz, v);
+    if (t.masked) continue;
+    const float p = expf(tri_load(vol, t) - lse);
+    const float ind = dist_to(ray, sx, sy, sz) > pd ? 1.f : 0.f;
+    tri_scatter_x(gvol, t, g * pd * p * (ind - pn), cx);
+  }
+}
+
+template <bool K512>
+__device__ __forceinline__ void ray_gumbel_bwd_body(
     const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
     const float* __restrict__ tindex, const float* __restrict__ aux,
     const float* __restrict__ grad_dist, float* __restrict__ grad_sigma, int R, VolDims v,
-    float step, int ncopies) {
+    float step, int ncopies, int K) {
   const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
   if (r >= R) return;
   const int lane = threadIdx.x % kWave;
@@ -292,15 +510,32 @@ __global__ __launch_bounds__(kThreads) void ray_gumbel_bwd_kernel(
   float* gvol = grad_sigma + (size_t)(blockIdx.x % ncopies) * v.F * v.Z * v.Y * v.X + slice;
   const float pd = aux[(size_t)r * 3 + 0], pn = aux[(size_t)r * 3 + 1], lse = aux[(size_t)r * 3 + 2];
   const int cx = lane & 1;
-  for (int j = 0; j < 2 * kPerLane; ++j) {             // 32 waypoints per pass, a lane pair per waypoint
+  const int passes = K512 ? 2 * kPerLane : (K + kWave / 2 - 1) / (kWave / 2);
+  for (int j = 0; j < passes; ++j) {                   // 32 waypoints per pass, a lane pair per waypoint
+    const int k = (lane >> 1) + j * (kWave / 2);
+    if (!K512 && k >= K) break;                        // only in the last pass
     float sx, sy, sz;
-    waypoint(ray, (lane >> 1) + j * (kWave / 2), step, sx, sy, sz);
+    waypoint(ray, k, step, sx, sy, sz);
     const Tri t = make_tri(sx, sy, sz, v);
     if (t.masked) continue;
     const float p = expf(tri_load(vol, t) - lse);
     const float ind = dist_to(ray, sx, sy, sz) > pd ? 1.f : 0.f;
     tri_scatter_x(gvol, t, g * pd * p * (ind - pn), cx);
   }
+}
+__global__ __launch_bounds__(kThreads) void ray_gumbel_bwd_kernel(
+    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
+    const float* __restrict__ tindex, const float* __restrict__ aux,
+    const float* __restrict__ grad_dist, float* __restrict__ grad_sigma, int R, VolDims v,
+    float step, int ncopies) {
+  ray_gumbel_bwd_body<true>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, v, step, ncopies, kK);
+}
+__global__ __launch_bounds__(kThreads) void ray_gumbel_bwd_any_kernel(
+    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
+    const float* __restrict__ tindex, const float* __restrict__ aux,
+    const float* __restrict__ grad_dist, float* __restrict__ grad_sigma, int R, VolDims v,
+    float step, int ncopies, int K) {
+  ray_gumbel_bwd_body<false>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, v, step, ncopies, K);
 }
 
 // test-time decode: exact zeros are masked to -inf (:728), arg-max waypoint -> distance
@@ -341,9 +576,40 @@ __global__ __launch_bounds__(kThreads) void ray_argmax_kernel(
   if (lane == 0) { pred_dist[r] = o_pred; gt_dist[r] = o_gt; }
 }
 
-inline bool rm_bad(int F, int R, int Z, int Y, int X, int K) {
-  return F <= 0 || R < 0 || Z <= 0 || Y <= 0 || X <= 0 || K != kK;
+// streamed form, any K
+__global__ __launch_bounds__(kThreads) void ray_argmax_any_kernel(
+    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
+    const float* __restrict__ tindex, float* __restrict__ pred_dist, float* __restrict__ gt_dist,
+    int R, VolDims v, float step, int K) {
+  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
+  if (r >= R) return;
+  const int lane = threadIdx.x % kWave;
+  const Ray ray = load_ray(origin, pts, tindex, r, v);
+  float o_pred = 0.f, o_gt = 0.f;
+  if (ray.f >= 0) {
+    const float* vol = sigma + (size_t)ray.f * v.Z * v.Y * v.X;
+    float best = kNegInf; int bi = kKMax; float blen = 0.f;
+    for (int k = lane; k < K; k += kWave) {
+      float sx, sy, sz;
+      waypoint(ray, k, step, sx, sy, sz);
+      const Tri t = make_tri<false>(sx, sy, sz, v);
+      const float val = (sx == sx) ? tri_load(vol, t) : 0.f;
+      const float z = (val == 0.f) ? kNegInf : val;
+      const float l = dist_to(ray, sx, sy, sz);
+      if (z > best || (z == best && k < bi)) { best = z; bi = k; blen = l; }
+    }
+    wave_argmax(best, bi, blen);
+    o_pred = blen;
+    o_gt = dist_to(ray, ray.px, ray.py, ray.pz);
+  }
+  if (lane == 0) { pred_dist[r] = o_pred; gt_dist[r] = o_gt; }
 }
+
+inline bool rm_bad(int F, int R, int Z, int Y, int X, int K) {
+  return F <= 0 || R < 0 || Z <= 0 || Y <= 0 || X <= 0 || K < 1 || K > kKMax;
+}
+std::atomic<int> g_force_streamed{0};   // vidar_ray_force_streamed
+inline bool rm_k512(int K) { return K == kK && !g_force_streamed.load(std::memory_order_relaxed); }
 inline dim3 rm_grid(int R) { return dim3((R + kRaysPerBlock - 1) / kRaysPerBlock); }
 
 }  // namespace
@@ -366,6 +632,12 @@ size_t vidar_ray_bwd_workspace_bytes(int F, int Z, int Y, int X) {
   return sizeof(float) * (size_t)F * Z * Y * X * kRayCopies;
 }
 
+int vidar_ray_max_k(void) { return kKMax; }
+
+int vidar_ray_force_streamed(int on) {
+  return g_force_streamed.exchange(on != 0, std::memory_order_relaxed);
+}
+
 int vidar_ray_ce_fwd_f32(const float* sigma, const float* origin, const float* gt_pts,
                          const float* tindex, float* ce, float* lse, float* valid, int F, int R,
                          int Z, int Y, int X, int K, float step, void* stream) {
@@ -373,10 +645,37 @@ int vidar_ray_ce_fwd_f32(const float* sigma, const float* origin, const float* g
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   if (R == 0) return 0;
   VolDims v{F, Z, Y, X};
-  hipLaunchKernelGGL(ray_ce_fwd_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream, sigma,
-                     origin, gt_pts, tindex, ce, lse, valid, R, v, step);
+  if (rm_k512(K))
+    hipLaunchKernelGGL(ray_ce_fwd_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream, sigma,
+                       origin, gt_pts, tindex, ce, lse, valid, R, v, step);
+  else
+    hipLaunchKernelGGL(ray_ce_fwd_any_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream, sigma,
+                       origin, gt_pts, tindex, ce, lse, valid, R, v, step, K);
   return vidar_last_error();
 }
+
+}  // extern "C"
+
+namespace {
+// the shared shell of the three backward entries: zero the accumulator (private copies if the workspace is big enough),
+// launch, sum the copies
+template <class Launch>
+int rm_backward(float* grad_sigma, int F, int R, int Z, int Y, int X, void* workspace, size_t workspace_bytes,
+                hipStream_t s, Launch launch) {
+  const size_t n = (size_t)F * Z * Y * X;
+  const bool copies = workspace != nullptr && workspace_bytes >= vidar_ray_bwd_workspace_bytes(F, Z, Y, X);
+  float* acc = copies ? (float*)workspace : grad_sigma;
+  hipError_t e = hipMemsetAsync(acc, 0, sizeof(float) * n * (copies ? kRayCopies : 1), s);
+  if (e != hipSuccess) return (int)e;
+  if (R == 0) return copies ? (int)hipMemsetAsync(grad_sigma, 0, sizeof(float) * n, s) : 0;
+  launch(acc, copies ? kRayCopies : 1);
+  if (copies)
+    hipLaunchKernelGGL(ray_sum_copies_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, acc, grad_sigma, n);
+  return vidar_last_error();
+}
+}  // namespace
+
+extern "C" {
 
 int vidar_ray_ce_bwd_f32(const float* sigma, const float* origin, const float* gt_pts,
                          const float* tindex, const float* lse, const float* grad_ce,
@@ -385,18 +684,15 @@ int vidar_ray_ce_bwd_f32(const float* sigma, const float* origin, const float* g
   VIDAR_ENTER();
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const size_t n = (size_t)F * Z * Y * X;
-  const bool copies = workspace != nullptr && workspace_bytes >= vidar_ray_bwd_workspace_bytes(F, Z, Y, X);
-  float* acc = copies ? (float*)workspace : grad_sigma;
-  hipError_t e = hipMemsetAsync(acc, 0, sizeof(float) * n * (copies ? kRayCopies : 1), s);
-  if (e != hipSuccess) return (int)e;
-  if (R == 0) return copies ? (int)hipMemsetAsync(grad_sigma, 0, sizeof(float) * n, s) : 0;
   VolDims v{F, Z, Y, X};
-  hipLaunchKernelGGL(ray_ce_bwd_kernel, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, gt_pts, tindex, lse, grad_ce,
-                     acc, R, v, step, copies ? kRayCopies : 1);
-  if (copies)
-    hipLaunchKernelGGL(ray_sum_copies_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, acc, grad_sigma, n);
-  return vidar_last_error();
+  return rm_backward(grad_sigma, F, R, Z, Y, X, workspace, workspace_bytes, s, [&](float* acc, int ncopies) {
+    if (rm_k512(K))
+      hipLaunchKernelGGL(ray_ce_bwd_kernel, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, gt_pts, tindex, lse,
+                         grad_ce, acc, R, v, step, ncopies);
+    else
+      hipLaunchKernelGGL(ray_ce_bwd_any_kernel, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, gt_pts, tindex, lse,
+                         grad_ce, acc, R, v, step, ncopies, K);
+  });
 }
 
 int vidar_ray_gumbel_fwd_f32(const float* sigma, const float* origin, const float* pts,
@@ -406,8 +702,12 @@ int vidar_ray_gumbel_fwd_f32(const float* sigma, const float* origin, const floa
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   if (R == 0) return 0;
   VolDims v{F, Z, Y, X};
-  hipLaunchKernelGGL(ray_gumbel_fwd_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream,
-                     sigma, origin, pts, tindex, noise, dist, aux, R, v, step);
+  if (rm_k512(K))
+    hipLaunchKernelGGL(ray_gumbel_fwd_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream,
+                       sigma, origin, pts, tindex, noise, dist, aux, R, v, step);
+  else
+    hipLaunchKernelGGL(ray_gumbel_fwd_any_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream,
+                       sigma, origin, pts, tindex, noise, dist, aux, R, v, step, K);
   return vidar_last_error();
 }
 
@@ -418,18 +718,41 @@ int vidar_ray_gumbel_bwd_f32(const float* sigma, const float* origin, const floa
   VIDAR_ENTER();
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const size_t n = (size_t)F * Z * Y * X;
-  const bool copies = workspace != nullptr && workspace_bytes >= vidar_ray_bwd_workspace_bytes(F, Z, Y, X);
-  float* acc = copies ? (float*)workspace : grad_sigma;
-  hipError_t e = hipMemsetAsync(acc, 0, sizeof(float) * n * (copies ? kRayCopies : 1), s);
-  if (e != hipSuccess) return (int)e;
-  if (R == 0) return copies ? (int)hipMemsetAsync(grad_sigma, 0, sizeof(float) * n, s) : 0;
   VolDims v{F, Z, Y, X};
-  hipLaunchKernelGGL(ray_gumbel_bwd_kernel, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, pts, tindex, aux,
-                     grad_dist, acc, R, v, step, copies ? kRayCopies : 1);
-  if (copies)
-    hipLaunchKernelGGL(ray_sum_copies_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, acc, grad_sigma, n);
+  return rm_backward(grad_sigma, F, R, Z, Y, X, workspace, workspace_bytes, s, [&](float* acc, int ncopies) {
+    if (rm_k512(K))
+      hipLaunchKernelGGL(ray_gumbel_bwd_kernel, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, pts, tindex, aux,
+                         grad_dist, acc, R, v, step, ncopies);
+    else
+      hipLaunchKernelGGL(ray_gumbel_bwd_any_kernel, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, pts, tindex, aux,
+                         grad_dist, acc, R, v, step, ncopies, K);
+  });
+}
+
+int vidar_ray_dist_fwd_f32(const float* sigma, const float* origin, const float* gt_pts,
+                           const float* tindex, const float* noise, float* dist, float* gt_len, float* aux,
+                           float* valid, int F, int R, int Z, int Y, int X, int K, float step, void* stream) {
+  VIDAR_ENTER();
+  if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
+  if (R == 0) return 0;
+  VolDims v{F, Z, Y, X};
+  hipLaunchKernelGGL(ray_dist_fwd_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream, sigma, origin,
+                     gt_pts, tindex, noise, dist, gt_len, aux, valid, R, v, step, K);
   return vidar_last_error();
+}
+
+int vidar_ray_dist_bwd_f32(const float* sigma, const float* origin, const float* gt_pts,
+                           const float* tindex, const float* aux, const float* grad_dist,
+                           float* grad_sigma, int F, int R, int Z, int Y, int X, int K, float step,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  VIDAR_ENTER();
+  if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  VolDims v{F, Z, Y, X};
+  return rm_backward(grad_sigma, F, R, Z, Y, X, workspace, workspace_bytes, s, [&](float* acc, int ncopies) {
+    hipLaunchKernelGGL(ray_dist_bwd_kernel, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, gt_pts, tindex, aux,
+                       grad_dist, acc, R, v, step, ncopies, K);
+  });
 }
 
 int vidar_ray_argmax_f32(const float* sigma, const float* origin, const float* pts,
@@ -439,8 +762,12 @@ int vidar_ray_argmax_f32(const float* sigma, const float* origin, const float* p
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   if (R == 0) return 0;
   VolDims v{F, Z, Y, X};
-  hipLaunchKernelGGL(ray_argmax_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream, sigma,
-                     origin, pts, tindex, pred_dist, gt_dist, R, v, step);
+  if (rm_k512(K))
+    hipLaunchKernelGGL(ray_argmax_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream, sigma,
+                       origin, pts, tindex, pred_dist, gt_dist, R, v, step);
+  else
+    hipLaunchKernelGGL(ray_argmax_any_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream, sigma,
+                       origin, pts, tindex, pred_dist, gt_dist, R, v, step, K);
   return vidar_last_error();
 }
 

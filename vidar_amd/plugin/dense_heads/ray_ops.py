@@ -1,8 +1,11 @@
 """Autograd wrappers of the fused head ray-march kernels (csrc/ray_march.hip).  They replace the
-tensor programs inside ViDARHeadBase (dense_heads/vidar_head_base.py:420-509, :586-592, :697-731,
-:754-773); per-ray results come back and the (cheap) weighting / reductions stay in torch."""
+tensor programs inside ViDARHeadBase (dense_heads/vidar_head_base.py:420-509, :575-592, :697-731,
+:754-773); per-ray results come back and the (cheap) weighting / reductions stay in torch.
+K = ray_grid_num is any value in 1..max_k(); 512 (K_SAMPLES, the released configs) runs the register-resident
+kernels, every other value the streamed ones."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import torch
@@ -12,6 +15,20 @@ from torch.autograd.function import once_differentiable
 from ..._lib import lib, check, ptr, stream_of, workspace, TIMER
 
 K_SAMPLES = 512
+
+
+def max_k():
+    return int(lib().vidar_ray_max_k())
+
+
+@contextlib.contextmanager
+def force_streamed(on=True):
+    """Test / benchmark hook: K == 512 runs the streamed kernels too inside the block (same bits)."""
+    was = lib().vidar_ray_force_streamed(int(bool(on)))
+    try:
+        yield
+    finally:
+        lib().vidar_ray_force_streamed(was)
 
 
 def _f(t):
@@ -84,6 +101,39 @@ class _RayGumbel(Function):
         return g, None, None, None, None, None, None
 
 
+class _RayDist(Function):
+    @staticmethod
+    def forward(ctx, sigma, origin, gt, tindex, noise, step, K):
+        sigma, origin, gt, tindex, noise = _f(sigma), _f(origin), _f(gt), _f(tindex), _f(noise)
+        F_, R, Z, Y, X = _dims(sigma, gt)
+        if noise.shape != (R, K + 1):
+            raise RuntimeError(f"noise must be [{R},{K + 1}]")
+        dist = torch.empty(R, device=sigma.device); gt_len = torch.empty_like(dist); valid = torch.empty_like(dist)
+        aux = torch.empty((R, 3), device=sigma.device)
+        with TIMER.span("ray_dist_fwd", 4 * (sigma.numel() + R * (K + 11))):
+          check(lib().vidar_ray_dist_fwd_f32(ptr(sigma), ptr(origin), ptr(gt), ptr(tindex), ptr(noise),
+                                           ptr(dist), ptr(gt_len), ptr(aux), ptr(valid), F_, R, Z, Y, X, K,
+                                           ctypes.c_float(step), stream_of(sigma)), "ray_dist_fwd")
+        ctx.save_for_backward(sigma, origin, gt, tindex, aux)
+        ctx.cfg = (step, K)
+        ctx.mark_non_differentiable(gt_len, valid)
+        return dist, gt_len, valid
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_dist, _grad_len, _grad_valid):
+        sigma, origin, gt, tindex, aux = ctx.saved_tensors
+        step, K = ctx.cfg
+        F_, R, Z, Y, X = _dims(sigma, gt)
+        g = torch.empty_like(sigma)
+        ws, wsp, wsn = workspace(lib().vidar_ray_bwd_workspace_bytes, F_, Z, Y, X, like=sigma)
+        with TIMER.span("ray_dist_bwd", 4 * (2 * sigma.numel() + R * 8)):
+          check(lib().vidar_ray_dist_bwd_f32(ptr(sigma), ptr(origin), ptr(gt), ptr(tindex), ptr(aux),
+                                           ptr(_f(grad_dist)), ptr(g), F_, R, Z, Y, X, K,
+                                           ctypes.c_float(step), wsp, wsn, stream_of(sigma)), "ray_dist_bwd")
+        return g, None, None, None, None, None, None
+
+
 def ray_ce(sigma, origin, gt, tindex, step=1.0, K=K_SAMPLES):
     """sigma [F,Z,Y,X], origin [F,3], gt [R,3], tindex [R] -> (ce [R], valid [R])"""
     return _RayCE.apply(sigma, origin, gt, tindex, float(step), int(K))
@@ -100,6 +150,14 @@ def ray_gumbel(sigma, origin, pts, tindex, noise=None, step=1.0, K=K_SAMPLES):
     if noise is None:
         noise = gumbel_noise(pts.shape[0], K, sigma.device)
     return _RayGumbel.apply(sigma, origin, pts, tindex, noise, float(step), int(K))
+
+
+def ray_dist(sigma, origin, gt, tindex, noise=None, step=1.0, K=K_SAMPLES):
+    """_custom_gumbel_softmax_distance on the GT rays (use_dist_loss): noise [R, K+1], entry 0 the end point.
+    -> (dist [R] differentiable, gt_len [R] = |gt - origin|, valid [R]); dropped rays give 0, 0, 0."""
+    if noise is None:
+        noise = gumbel_noise(gt.shape[0], int(K) + 1, sigma.device)
+    return _RayDist.apply(sigma, origin, gt, tindex, noise, float(step), int(K))
 
 
 def ray_argmax(sigma, origin, pts, tindex, step=1.0, K=K_SAMPLES):

@@ -3,8 +3,9 @@ semantics of projects/mmdet3d_plugin/bevformer/dense_heads/vidar_head_base.py:31
 
 What changed is the execution plan, not the math:
   * the waypoint / grid_sample / -inf mask / cross-entropy chain (:420-509, :586-592) is one fused
-    kernel per (batch item) call (ray_ops.ray_ce), likewise the dense gumbel render (:594-630,
-    :754-773) and the test-time arg-max decode (:697-731);
+    kernel per (batch item) call (ray_ops.ray_ce), likewise the distance loss on the GT rays
+    (:575-585, ray_ops.ray_dist), the dense gumbel render (:594-630, :754-773) and the test-time
+    arg-max decode (:697-731); any ray_grid_num up to ray_ops.max_k();
   * GT clouds are never compacted with boolean indexing (host syncs at :441, :464-467, :636-644):
     rays carry a frame slot (-1 = ignore) and validity is decided on device;
   * the training chamfer (:654) runs on the nearest-neighbour kernel with a validity mask instead
@@ -142,10 +143,6 @@ class ViDARHeadBase(ViDARHeadTemplate):
         self.use_dist_loss = use_dist_loss
         self.use_dense_loss = use_dense_loss
         assert self.use_ce_loss or self.use_dist_loss or self.use_dense_loss
-        if use_dist_loss:
-            raise NotImplementedError("use_dist_loss is off in every released config (:567-578)")
-        if ray_grid_num != ray_ops.K_SAMPLES:
-            raise NotImplementedError(f"ray kernels are specialised for ray_grid_num == {ray_ops.K_SAMPLES}")
         self.dense_loss_weight = dense_loss_weight
         self.gumbel_noise_fn = None      # tests inject the reference's noise here
 
@@ -177,6 +174,23 @@ class ViDARHeadBase(ViDARHeadTemplate):
         step = self.ray_grid_step
         loss_dict = dict()
         sigmas = [self._volumes(bev_preds, b, Z, H, W) for b in range(bs)]
+
+        if self.use_dist_loss:
+            # (:575-585) hard gumbel sample over {end point, waypoints} of the GT rays, L1 against the ray length.
+            # Its noise is drawn before the dense loss's, as in the reference.
+            num = bev_preds.new_zeros(())
+            den = bev_preds.new_zeros(())
+            scale = (tgt_pc_range[3] - tgt_pc_range[0]) / W
+            for b in range(bs):
+                R = gt_grids[b].shape[0]
+                noise = (self.gumbel_noise_fn(R, self.ray_grid_num + 1) if self.gumbel_noise_fn
+                         else ray_ops.gumbel_noise(R, self.ray_grid_num + 1, gt_grids.device))
+                dist, gt_len, valid = ray_ops.ray_dist(sigmas[b], origin_grids[b], gt_grids[b], tindex[b], noise,
+                                                       step, self.ray_grid_num)
+                w = lw[tindex[b].clamp(min=0).long()] * valid
+                num = num + (torch.abs(dist - gt_len) * scale * w).sum()
+                den = den + w.sum()
+            loss_dict["dist.loss"] = num / torch.clamp(den, min=1)
 
         if self.use_ce_loss:
             num = bev_preds.new_zeros(())
