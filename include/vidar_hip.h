@@ -463,6 +463,44 @@ int vidar_stem_bn_relu_pool_f32(const float* x, const float* scale, const float*
 int vidar_affine_act_bwd_f32(const float* grad_y, const float* y, const float* scale, float* grad_x,
                              float* grad_residual, int N, int C, int HW, int relu, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Deformable convolution v3, the core op of the InternImage backbone (csrc/dcnv3.hip).  Replaces the reference's
+ * `DCNv3` extension (projects/mmdet3d_plugin/bevformer/backbones/ops_dcnv3: dcnv3_forward / dcnv3_backward,
+ * src/cuda/dcnv3_im2col_cuda.cuh:217-276, :149-213, :776-839).  Channel-last:
+ *   input [N,H,W,G*gc], offset [N,Ho,Wo,G*P*2] as (w, h) pairs, mask [N,Ho,Wo,G*P], out / grad_out [N,Ho,Wo,G*gc],
+ *   P = kh*kw with point p = i_w*kh + j_h, Ho = (H + 2*pad_h - (dil_h*(kh-1)+1)) / stride_h + 1 (same for Wo),
+ *   out = sum_p mask_p * bilinear(input[:, g, :], loc_p), loc as in :249-260; a point counts iff
+ *   loc_h > -1 && loc_w > -1 && loc_h < H && loc_w < W (zero outside, NaN locations contribute nothing).
+ * group_channels: any positive value (16-byte loads when it is a multiple of 4 and the buffers are 16-byte aligned).
+ * VIDAR_ERR_BAD_ARG: non-positive sizes, kh*kw > 1024, a kernel extent larger than the padded input, or any of the
+ * tensors holding 2^31 - 512 elements or more.  The reference's im2col_step only batches its launches and has no
+ * counterpart here.
+ * backward: grad_offset (already multiplied by offset_scale, :212-213) and grad_mask are fully written with plain stores
+ * in a fixed summation order (bit-reproducible); grad_input is zeroed by the call, then accumulated with fp32 atomics.
+ * `workspace` / vidar_dcnv3_backward_workspace_bytes are RESERVED: every form of the backward accumulates on chip or
+ * straight into grad_input, the function returns 0 and the call ignores both arguments (NULL / 0 is what callers pass).
+ * ------------------------------------------------------------------------- */
+/* A/B switch of the grad_input accumulation of vidar_dcnv3_backward_f32 (bit 0: lane layout, bit 1: LDS window).
+ *   0: one fp32 atomic per (channel, point, corner), an item's lanes owning 4 channels each (16-byte loads);
+ *   1 (default, measured fastest: profiles/kbench_dcnv3.md): the same with ONE channel per lane, so that an atomic
+ *      instruction of an item covers one contiguous gc*4-byte segment;
+ *   2 / 3: a workgroup owns a tile of output pixels of one (image, group), sums the tile's contributions in an LDS window
+ *      of the input (tile + kernel extent + 3 pixels of learned offset on every side) and flushes the window once,
+ *      channel-contiguous; samples beyond the window add straight to memory; lanes as in 0 / 1.  Shapes whose window
+ *      exceeds 64 KiB of LDS take form 0 / 1.
+ * Same sums up to fp32 order; grad_offset / grad_mask are plain stores in every form.  Values outside 0..3 are ignored.
+ * Returns the previous value. */
+int vidar_dcnv3_set_variant(int variant);
+int vidar_dcnv3_forward_f32(const float* input, const float* offset, const float* mask, float* out, int N, int H, int W,
+                            int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                            int group, int group_channels, float offset_scale, void* stream);
+size_t vidar_dcnv3_backward_workspace_bytes(int N, int H, int W, int kh, int kw, int stride_h, int stride_w, int pad_h,
+                                            int pad_w, int dil_h, int dil_w, int group, int group_channels);
+int vidar_dcnv3_backward_f32(const float* input, const float* offset, const float* mask, const float* grad_out,
+                             float* grad_input, float* grad_offset, float* grad_mask, int N, int H, int W, int kh, int kw,
+                             int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int group,
+                             int group_channels, float offset_scale, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

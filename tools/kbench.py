@@ -225,6 +225,63 @@ def bench_dcn(which):
                        4 * (3 * x.numel() + gcols.numel() + 2 * off.numel() + 2 * mask.numel()))
 
 
+def bench_dcnv3(which):
+    """DCNv3 forward / backward (csrc/dcnv3.hip) at the four stage shapes of InternImage-T and -B for 6 cameras at
+    928 x 1600 (3x3, stride 1, pad 1; gc = 16), trained-like offsets N(0, (1.5 px)^2) and softmax masks, next to the same
+    call through `dcnv3_core_pytorch` (torch's grid_sample, what `DCNv3_pytorch` runs) as the comparison line.  The two are
+    ALTERNATED in the same process: 5 rounds of (HIP x n, torch x m) after a warm-up of both, n / m sized so that a group spans >= 5 ms; the line reports the
+    median round and the spread (min .. max) of the rounds.  The torch backward is autograd's backward alone (the graph is
+    built outside the timed region)."""
+    from vidar_amd.plugin.ops_dcnv3 import dcnv3_core_pytorch
+    from vidar_amd.third_lib import dcnv3
+    from vidar_amd._lib import lib
+    g = torch.Generator().manual_seed(0)
+    prev = lib().vidar_dcnv3_set_variant(-1)
+    print(json.dumps({"dcnv3_backward_variant": prev}), flush=True)
+    rounds = 5
+    N, P = 6, 9
+
+    def alternate(fa, fb):
+        # every timed group spans at least ~5 ms of device time (5 .. 100 launches, from the warm-up's own timing)
+        reps = lambda ms: int(min(100, max(5, 5.0 / max(ms, 1e-3))))
+        ia, ib = reps(timeit(fa, warm=2, it=3)), reps(timeit(fb, warm=2, it=3))
+        ta, tb = [], []
+        for _ in range(rounds):
+            ta.append(timeit(fa, warm=0, it=ia)); tb.append(timeit(fb, warm=0, it=ib))
+        return sorted(ta), sorted(tb)
+
+    for model, c0, g0 in (("T", 64, 4), ("B", 112, 7)):
+        for i, (H, W) in enumerate(((232, 400), (116, 200), (58, 100), (29, 50))):
+            C, G = c0 << i, g0 << i
+            gc = C // G
+            geo = (3, 3, 1, 1, 1, 1, 1, 1, G, gc, 1.0)
+            x = torch.randn(N, H, W, C, generator=g).cuda()
+            off = (torch.randn(N, H, W, G * P * 2, generator=g) * 1.5).cuda()
+            mask = torch.softmax(torch.randn(N, H, W, G, P, generator=g), -1).reshape(N, H, W, G * P).cuda()
+            gout = torch.randn(N, H, W, C, generator=g).cuda()
+            tag = f"InternImage-{model} stage {i} N={N} {H}x{W} C={C} G={G}"
+            fwd_bytes = 4 * (2 * x.numel() + off.numel() + mask.numel())
+            bwd_bytes = 4 * (4 * x.numel() + 2 * off.numel() + 2 * mask.numel())    # reads x, grad_out; zeroes + writes grad_input
+
+            def torch_fwd():
+                with torch.no_grad():
+                    return dcnv3_core_pytorch(x, off, mask, *geo)
+            th, tt = alternate(lambda: dcnv3.dcnv3_forward(x, off, mask, *geo, 256), torch_fwd)
+            mid = rounds // 2
+            report(f"dcnv3_fwd {tag}", th[mid], fwd_bytes, min_ms=round(th[0], 4), max_ms=round(th[-1], 4))
+            report(f"dcnv3_fwd grid_sample {tag}", tt[mid], fwd_bytes, min_ms=round(tt[0], 4), max_ms=round(tt[-1], 4),
+                   ratio_vs_hip=round(tt[mid] / th[mid], 2), faster_beyond_spread=bool(th[-1] < tt[0]))
+            ops = [t.clone().requires_grad_(True) for t in (x, off, mask)]
+            y = dcnv3_core_pytorch(*ops, *geo)
+            th, tt = alternate(lambda: dcnv3.dcnv3_backward(x, off, mask, *geo, gout, 256),
+                               lambda: torch.autograd.grad(y, ops, gout, retain_graph=True))
+            report(f"dcnv3_bwd {tag}", th[mid], bwd_bytes, min_ms=round(th[0], 4), max_ms=round(th[-1], 4))
+            report(f"dcnv3_bwd grid_sample {tag}", tt[mid], bwd_bytes, min_ms=round(tt[0], 4), max_ms=round(tt[-1], 4),
+                   ratio_vs_hip=round(tt[mid] / th[mid], 2), faster_beyond_spread=bool(th[-1] < tt[0]))
+            del y, ops
+            torch.cuda.empty_cache()
+
+
 def bench_affine(which):
     """Frozen BN + (residual) + ReLU of the backbone (csrc/affine_act.hip) at the stage-3 shapes of the 24 history images."""
     from vidar_amd.plugin.backbones import FrozenBN

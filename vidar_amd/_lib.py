@@ -30,6 +30,9 @@ def lib() -> ctypes.CDLL:
         dcn = os.environ.get("VIDAR_DCN_VARIANT")                # A/B of the DCNv2 col2im gather (LDS window / global loads)
         if dcn is not None:
             _lib.vidar_dcn_set_variant(int(dcn))
+        v3 = os.environ.get("VIDAR_DCNV3_VARIANT")              # A/B of the DCNv3 backward's grad_input accumulation (tools)
+        if v3 is not None:
+            _lib.vidar_dcnv3_set_variant(int(v3))
         order = os.environ.get("VIDAR_MSDA_ITEM_ORDER")          # A/B of the MSDA gather kernels' item order (tools, bench)
         if order is not None:
             _lib.vidar_msda_set_item_order(int(order))

@@ -38,6 +38,18 @@ def load_checkpoint(model, path, map_location="cpu", strict=False, revise_keys=(
     return ckpt, list(res.missing_keys), list(res.unexpected_keys)
 
 
+def backbone_state_dict(path, map_location="cpu"):
+    """Weights of an image backbone out of a released checkpoint: the `state_dict` / `model` entry (or the file itself),
+    `backbone.` stripped from every key that has it, then `module.` from all keys when the first one carries it
+    (bevformer/backbones/internimage.py:655-674)."""
+    ckpt = torch.load(path, map_location=map_location, weights_only=False)
+    sd = ckpt.get("state_dict", ckpt.get("model", ckpt))
+    out = OrderedDict((k[len("backbone."):] if k.startswith("backbone.") else k, v) for k, v in sd.items())
+    if out and next(iter(out)).startswith("module."):
+        out = OrderedDict((k[len("module."):], v) for k, v in out.items())
+    return out
+
+
 def resume(model, optimizer, path, map_location="cpu"):
     """restore weights + optimizer + (epoch, iter) like `runner.resume`."""
     ckpt, missing, unexpected = load_checkpoint(model, path, map_location, strict=True)

@@ -49,6 +49,15 @@ def _latent_render(step):
                 reduction=16, act="sigmoid")
 
 
+# InternImage-T / -S / -B as the image backbone (`with_backbone="internimage_t"` ...): the released model sizes, the three
+# 1/8 .. 1/32 maps into the same FPN as the ResNet101 path
+INTERNIMAGE = {
+    "internimage_t": dict(channels=64, depths=(4, 4, 18, 4), groups=(4, 8, 16, 32), post_norm=False, drop_path_rate=0.2),
+    "internimage_s": dict(channels=80, depths=(4, 4, 21, 4), groups=(5, 10, 20, 40), post_norm=True, drop_path_rate=0.3),
+    "internimage_b": dict(channels=112, depths=(4, 4, 21, 4), groups=(7, 14, 28, 56), post_norm=True, drop_path_rate=0.4),
+}
+
+
 def model_config(name, bev_h=200, bev_w=200, with_backbone=False):
     v = VARIANTS[name]
     lr = _latent_render(v["lr_step"])
@@ -101,7 +110,18 @@ def model_config(name, bev_h=200, bev_w=200, with_backbone=False):
                  random_drop_prev_end_idx=v["drop_prev"][1],
                  backwarded_prev_frame_num=v["backward_prev"], future_pred_head=head,
                  pts_bbox_head=bev_head)
-    if with_backbone:
+    if isinstance(with_backbone, str):
+        if with_backbone not in INTERNIMAGE:
+            raise KeyError(f"with_backbone={with_backbone!r}: expected True / False or one of {sorted(INTERNIMAGE)}")
+        ii = INTERNIMAGE[with_backbone]
+        model["img_backbone"] = dict(type="InternImage", core_op="DCNv3", channels=ii["channels"],
+                                     depths=list(ii["depths"]), groups=list(ii["groups"]), mlp_ratio=4.0,
+                                     drop_path_rate=ii["drop_path_rate"], norm_layer="LN", layer_scale=1.0,
+                                     offset_scale=1.0, post_norm=ii["post_norm"], with_cp=False, out_indices=(1, 2, 3))
+        model["img_neck"] = dict(type="FPN", in_channels=[ii["channels"] * m for m in (2, 4, 8)], out_channels=DIM,
+                                 start_level=0, add_extra_convs="on_output", num_outs=4,
+                                 relu_before_extra_convs=True)
+    elif with_backbone:
         model["img_backbone"] = dict(type="ResNet", depth=101, num_stages=4, out_indices=(1, 2, 3),
                                      frozen_stages=1, norm_cfg=dict(type="BN2d", requires_grad=False),
                                      norm_eval=True, style="caffe",

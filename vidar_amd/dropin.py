@@ -5,8 +5,8 @@ The reference reaches its native code in three ways:
     (bevformer/utils/e2e_predictor_utils.py:86-90, :118-121; third_lib/dvr is built the same way),
   * `import chamferdist` (utils/e2e_predictor_utils.py:163-183, detectors/vidar.py eval path),
   * `mmcv.utils.ext_loader.load_ext('_ext', ['ms_deform_attn_backward', 'ms_deform_attn_forward'])`.
-`install()` registers `dvr`, `dvxlr`, `dvxlr_v2`, `chamferdist` (and `chamferdist._C`) as top-level modules
-and, with `patch_loaders=True`, answers the two loader calls with the shims, so the reference's wrapper
+`install()` registers `dvr`, `dvxlr`, `dvxlr_v2`, `chamferdist` (and `chamferdist._C`) and `DCNv3` (the compiled
+module `import DCNv3` of backbones/ops_dcnv3/functions/dcnv3_func.py:15 expects) as top-level modules and, with `patch_loaders=True`, answers the two loader calls with the shims, so the reference's wrapper
 files run unchanged on top of libvidar_hip.so.  `uninstall()` undoes it."""
 from __future__ import annotations
 
@@ -22,6 +22,8 @@ def shim(name):
         return importlib.import_module(f"vidar_amd.third_lib.{name}")
     if name in ("chamferdist", "chamferdist._C", "chamferdist.chamfer"):
         return importlib.import_module("vidar_amd.third_lib." + name)
+    if name == "DCNv3":
+        return importlib.import_module("vidar_amd.third_lib.dcnv3")
     if name == "_ext":
         return importlib.import_module("vidar_amd.third_lib.mmcv_ext")
     raise KeyError(name)
@@ -44,7 +46,7 @@ def load_ext(name, funcs):
 
 
 def install(patch_loaders=True):
-    for n in NAMES + ("chamferdist", "chamferdist._C", "chamferdist.chamfer"):
+    for n in NAMES + ("chamferdist", "chamferdist._C", "chamferdist.chamfer", "DCNv3"):
         _saved.setdefault(("mod", n), sys.modules.get(n))
         sys.modules[n] = shim(n)
     if patch_loaders:
