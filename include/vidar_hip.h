@@ -501,6 +501,43 @@ int vidar_dcnv3_backward_f32(const float* input, const float* offset, const floa
                              int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int group,
                              int group_channels, float offset_scale, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Detection loss tail of the BEVFormer fine-tune step (csrc/det_loss.hip): Hungarian cost matrices and the focal / L1
+ * losses of ALL decoder layers and samples in one launch each (bevformer/dense_heads/bevformer_head.py:215-393,
+ * core/bbox/assigners/hungarian_assigner_3d.py:106-123).  fp32, latency-bound; its point is one host read per step.
+ *   cls [NL,B,Q,C] logits (C <= 64), box [NL,B,Q,10] predictions in normalised code (cx, cy, log w, log l, cz, log h,
+ *   sin, cos, vx, vy); ground truth packed over the batch: gt_box_norm [total_g,10] (normalize_bbox applied),
+ *   gt_label [total_g] i32 in [0, C), gt_start [B+1] i32 (device; sample b owns rows gt_start[b] .. gt_start[b+1]).
+ * match_cost: cost [NL, Q*total_g]; sample b's block of a layer's row starts at Q*gt_start[b] and is [Q, G_b] row-major:
+ *   p = sigmoid(cls[l,b,q,gt_label[g]])
+ *   cost = cls_weight * (-alpha (1-p)^gamma log(p + 1e-12) + (1-alpha) p^gamma log(1 - p + 1e-12))
+ *        + reg_weight * sum_{k<8} |box[l,b,q,k] - gt_box_norm[g,k]|
+ *   total_g == 0 (or any empty extent) returns 0 without a launch; samples with G_b == 0 write nothing.
+ * loss_fwd: labels [NL,B,Q] i32 (C = background), matched_gt [NL,B,Q] i32 (index inside the sample's rows, -1 = none)
+ *   sums[l,0] = sum over (b,q,c) of the sigmoid focal loss, mmcv semantics: target class
+ *               -alpha (1-p)^gamma log(max(p, FLT_MIN)), other classes -(1-alpha) p^gamma log(max(1-p, FLT_MIN))
+ *   sums[l,1] = sum over matched (b,q) whose target row is finite in all 10 entries of
+ *               sum_k code_weights[k] |box[l,b,q,k] - gt_box_norm[matched,k]|
+ *   Deterministic: per-workgroup partials (fp64 sums of the fp32 terms) in `workspace`
+ *   (vidar_det_loss_workspace_bytes, caller-owned scratch, 8-byte aligned), then a fixed-order pass per layer; no
+ *   floating-point atomics.
+ * loss_bwd: grad_sums [NL,2] -> grad_cls, grad_box written in full (zeros where nothing flows); sign(0) = 0.
+ * VIDAR_ERR_BAD_ARG: negative sizes, C outside 1..64, NL > 65535, B*Q or total_g*10 beyond the 32-bit index range used,
+ * a missing pointer, a workspace that is too small.
+ * ------------------------------------------------------------------------- */
+int vidar_det_match_cost_f32(const float* cls, const float* box, const float* gt_box_norm, const int32_t* gt_label,
+                             const int32_t* gt_start, float* cost, float alpha, float gamma, float cls_weight,
+                             float reg_weight, int NL, int B, int Q, int C, int total_g, void* stream);
+size_t vidar_det_loss_workspace_bytes(int NL, int B, int Q);
+int vidar_det_loss_fwd_f32(const float* cls, const float* box, const int32_t* labels, const int32_t* matched_gt,
+                           const float* gt_box_norm, const int32_t* gt_start, const float* code_weights, float* sums,
+                           float alpha, float gamma, int NL, int B, int Q, int C, int total_g, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int vidar_det_loss_bwd_f32(const float* cls, const float* box, const int32_t* labels, const int32_t* matched_gt,
+                           const float* gt_box_norm, const int32_t* gt_start, const float* code_weights,
+                           const float* grad_sums, float* grad_cls, float* grad_box, float alpha, float gamma, int NL,
+                           int B, int Q, int C, int total_g, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

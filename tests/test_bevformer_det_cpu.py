@@ -1,0 +1,439 @@
+"""CPU: the BEVFormer detection fine-tune path -- registry surface and state-dict layout of the released fine-tune configs,
+the loss tail (PyTorch composition of the fused kernels' arithmetic against an fp64 restatement and against the
+reference-structured loss_single path, assignments included), box coder and video-mode inference, the ViDAR -> BEVFormer
+checkpoint hand-over, the untouched ViDAR initialisation, the C ABI and the word list the GPU pool refuses."""
+import copy
+import ctypes
+import re
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+import vidar_amd.plugin as P
+from vidar_amd.configs import FINETUNE, get_config
+from vidar_amd.plugin.config import Config
+
+ROOT = Path(__file__).resolve().parents[1]
+REF_CFG = Path("/root/reference/projects/configs/vidar_finetune")
+REF_PATHS = {"finetune/vidar_1_8_nusc_1future": "nusc_1_4_subset/vidar_1_8_nusc_1future.py",
+             "finetune/vidar_1_8_nusc_3future": "nusc_1_4_subset/vidar_1_8_nusc_3future.py",
+             "finetune/vidar_full_nusc_1future": "nusc_fullset/vidar_full_nusc_1future.py",
+             "baseline": "nusc_1_4_subset/bevformer_1_4_baseline.py"}
+FPN_SMALL = [(15, 25), (8, 13), (4, 7), (2, 4)]
+DET_KEYS = ("pts_bbox_head.transformer.decoder.", "pts_bbox_head.cls_branches.", "pts_bbox_head.reg_branches.",
+            "pts_bbox_head.query_embedding.", "pts_bbox_head.transformer.reference_points.", "pts_bbox_head.code_weights")
+
+
+def shapes(model):
+    return {k: tuple(v.shape) for k, v in model.state_dict().items()}
+
+
+def test_registry_names_of_the_detection_branch():
+    assert "BEVFormer" in P.DETECTORS and "BEVFormerHead" in P.HEADS
+    assert "DetectionTransformerDecoder" in P.TRANSFORMER_LAYER_SEQUENCE and "BEVFormerEncoder" in P.TRANSFORMER_LAYER_SEQUENCE
+    assert "DetrTransformerDecoderLayer" in P.TRANSFORMER_LAYER and "BEVFormerLayer" in P.TRANSFORMER_LAYER
+    assert "MultiheadAttention" in P.ATTENTION and "CustomMSDeformableAttention" in P.ATTENTION
+    from vidar_amd.plugin import core_bbox as B
+    assert "NMSFreeCoder" in B.BBOX_CODERS and "HungarianAssigner3D" in B.BBOX_ASSIGNERS
+    assert all(k in B.MATCH_COST for k in ("FocalLossCost", "BBox3DL1Cost", "IoUCost"))
+    assert all(k in P.LOSSES for k in ("FocalLoss", "L1Loss", "GIoULoss"))
+
+
+@pytest.mark.parametrize("name", list(FINETUNE))
+def test_finetune_recipe_builds_a_detector_with_the_reference_head_layout(name):
+    cfg = get_config(name)
+    assert cfg["load_from"] == f"work_dirs/{FINETUNE[name]['pretrain']}/latest.pth" and cfg["task"] == "detection"
+    sd = shapes(P.build_detector(cfg["model"]))
+    h = "pts_bbox_head."
+    d = h + "transformer.decoder.layers."
+    for l in range(6):
+        assert sd[d + f"{l}.attentions.0.attn.in_proj_weight"] == (768, 256)
+        assert sd[d + f"{l}.attentions.0.attn.in_proj_bias"] == (768,)
+        assert sd[d + f"{l}.attentions.0.attn.out_proj.weight"] == (256, 256)
+        assert sd[d + f"{l}.attentions.1.sampling_offsets.weight"] == (64, 256)       # 8 heads x 1 level x 4 points x 2
+        assert sd[d + f"{l}.attentions.1.attention_weights.weight"] == (32, 256)
+        assert sd[d + f"{l}.attentions.1.value_proj.weight"] == (256, 256)
+        assert sd[d + f"{l}.ffns.0.layers.0.0.weight"] == (512, 256) and sd[d + f"{l}.norms.2.weight"] == (256,)
+        assert sd[h + f"cls_branches.{l}.0.weight"] == (256, 256) and sd[h + f"cls_branches.{l}.1.weight"] == (256,)
+        assert sd[h + f"cls_branches.{l}.6.weight"] == (10, 256) and sd[h + f"reg_branches.{l}.4.weight"] == (10, 256)
+    assert sd[h + "query_embedding.weight"] == (900, 512) and sd[h + "bev_embedding.weight"] == (40000, 256)
+    assert sd[h + "transformer.reference_points.weight"] == (3, 256) and sd[h + "code_weights"] == (10,)
+    assert sd[h + "transformer.encoder.layers.2.latent_render.lora_b.weight"] == (256, 16)
+    assert not any(k.startswith("future_pred_head") for k in sd)
+
+
+@pytest.mark.skipif(not REF_CFG.exists(), reason="reference tree not mounted")
+@pytest.mark.parametrize("name", list(REF_PATHS))
+def test_released_finetune_config_loads_unchanged(name):
+    cfg = Config.fromfile(REF_CFG / REF_PATHS[name])
+    assert cfg.model.type == "BEVFormer" and cfg.model.pts_bbox_head.type == "BEVFormerHead"
+    a = P.build_detector(dict(cfg.model))                        # includes ResNet101-DCNv2 + FPN
+    sa = shapes(a)
+    assert "img_backbone.layer3.0.conv2.conv_offset.weight" in sa and a.pts_bbox_head.assigner is not None
+    if name == "baseline":
+        assert not any(".latent_render." in k for k in sa)
+        assert sa["pts_bbox_head.transformer.decoder.layers.5.attentions.0.attn.in_proj_weight"] == (768, 256)
+        return
+    assert cfg.load_from == get_config(name)["load_from"]
+    assert sa == shapes(P.build_detector(get_config(name, with_backbone=True)["model"]))
+    lr = a.pts_bbox_head.transformer.encoder.layers[2].latent_render
+    assert lr.grid_step == FINETUNE[name]["lr_step"]
+    assert a.pts_bbox_head.transformer.reference_points.weight.requires_grad
+
+
+def test_options_outside_the_scope_name_themselves():
+    cfg = get_config("finetune/vidar_1_8_nusc_1future", bev_h=8, bev_w=8)["model"]
+    bad = copy.deepcopy(cfg); bad["pts_bbox_head"]["as_two_stage"] = True
+    with pytest.raises(NotImplementedError, match="as_two_stage"):
+        P.build_detector(bad)
+    bad = copy.deepcopy(cfg); bad["pts_bbox_head"]["loss_iou"]["loss_weight"] = 1.0
+    with pytest.raises(NotImplementedError, match="GIoULoss"):
+        P.build_detector(bad)
+    bad = copy.deepcopy(cfg); bad["pts_backbone"] = dict(type="SECOND")
+    with pytest.raises(NotImplementedError, match="pts_backbone"):
+        P.build_detector(bad)
+
+
+# ---- the loss tail --------------------------------------------------------------------------------------------------
+def tail_case(seed, NL, B, Q, C, counts, nan_rows=True, dtype=torch.float32):
+    from vidar_amd.plugin.core_bbox import normalize_bbox
+    from vidar_amd.plugin.dense_heads import det_ops
+    from vidar_amd.synthetic import boxes_3d
+    g = torch.Generator().manual_seed(seed)
+    cls = torch.randn(NL, B, Q, C, generator=g) * 2 - 2
+    box = torch.randn(NL, B, Q, 10, generator=g)
+    bl = [boxes_3d(seed * 10 + b, num=n, nan_velocity_rate=0.2 if nan_rows else 0.0) for b, n in enumerate(counts)]
+    raw = [torch.from_numpy(b) for b, _ in bl]
+    labels = [torch.from_numpy(l) for _, l in bl]
+    centred = [torch.cat([r[:, :2], r[:, 2:3] + r[:, 5:6] * 0.5, r[:, 3:]], 1) for r in raw]
+    packed = torch.cat(centred)
+    gt_norm = normalize_bbox(packed) if packed.shape[0] else torch.zeros((0, 10))
+    gt_label = torch.cat(labels).to(torch.int32)
+    gt_start = torch.from_numpy(det_ops.gt_starts(counts))
+    return dict(cls=cls.to(dtype), box=box.to(dtype), gt_norm=gt_norm.to(dtype), gt_label=gt_label, gt_start=gt_start,
+                counts=counts, raw=raw, centred=centred, labels=labels)
+
+
+def cost_fp64(c, alpha=0.25, gamma=2.0, cls_w=2.0, reg_w=0.25):
+    """the issue's formula, element by element in fp64 -> list over layers of list over samples of [Q, G]"""
+    cls, box, gt, lab = c["cls"].double(), c["box"].double(), c["gt_norm"].double(), c["gt_label"].long()
+    out = []
+    for l in range(cls.shape[0]):
+        row = []
+        for b, G in enumerate(c["counts"]):
+            s = int(c["gt_start"][b])
+            p = torch.sigmoid(cls[l, b][:, lab[s:s + G]])
+            cc = cls_w * (-alpha * (1 - p) ** gamma * torch.log(p + 1e-12) + (1 - alpha) * p ** gamma * torch.log(1 - p + 1e-12))
+            rc = reg_w * (box[l, b][:, None, :8] - gt[None, s:s + G, :8]).abs().sum(-1)
+            row.append(cc + rc)
+        out.append(row)
+    return out
+
+
+def loss_fp64(c, labels, matched, cw, alpha=0.25, gamma=2.0):
+    cls, box, gt = c["cls"].double(), c["box"].double(), c["gt_norm"].double()
+    NL, B, Q, C = cls.shape
+    p = torch.sigmoid(cls)
+    tiny = float(np.finfo(np.float32).tiny)
+    onehot = labels.long().unsqueeze(-1) == torch.arange(C)
+    focal = torch.where(onehot, -alpha * (1 - p) ** gamma * torch.log(p.clamp(min=tiny)),
+                        -(1 - alpha) * p ** gamma * torch.log((1 - p).clamp(min=tiny)))
+    s_box = torch.zeros(NL, dtype=torch.float64)
+    for l in range(NL):
+        for b in range(B):
+            for q in range(Q):
+                m = int(matched[l, b, q])
+                if m >= 0:
+                    t = gt[int(c["gt_start"][b]) + m]
+                    if torch.isfinite(t).all():
+                        s_box[l] += ((box[l, b, q] - t).abs() * cw.double()).sum()
+    return torch.stack([focal.reshape(NL, -1).sum(1), s_box], 1)
+
+
+CASES = [(1, 3, 2, 30, 10, [7, 12]), (2, 2, 1, 9, 10, [0]), (3, 2, 2, 9, 10, [14, 0]), (4, 6, 1, 30, 10, [30]),
+         (5, 1, 2, 12, 4, [1, 5])]          # G = 0, G > Q, G = Q, a sample without boxes beside one with
+
+
+@pytest.mark.parametrize("case", CASES, ids=[f"case{c[0]}" for c in CASES])
+def test_torch_composition_of_the_cost_matches_fp64_and_the_assigner(case):
+    from scipy.optimize import linear_sum_assignment
+    from vidar_amd.plugin.core_bbox import build_assigner
+    from vidar_amd.plugin.dense_heads import det_ops as D
+    seed, NL, B, Q, C, counts = case
+    c = tail_case(seed, NL, B, Q, C, [min(n, 40) for n in counts])
+    if C != 10:
+        c["gt_label"] = c["gt_label"] % C
+        c["labels"] = [l % C for l in c["labels"]]
+    cost = D.match_cost_torch(c["cls"], c["box"], c["gt_norm"], c["gt_label"], c["counts"], 0.25, 2.0, 2.0, 0.25)
+    assert cost.shape == (NL, Q * sum(c["counts"]))
+    want = cost_fp64(c)
+    matched = D.solve(cost.numpy(), NL, Q, c["counts"])
+    assigner = build_assigner(dict(type="HungarianAssigner3D", cls_cost=dict(type="FocalLossCost", weight=2.0),
+                                   reg_cost=dict(type="BBox3DL1Cost", weight=0.25), iou_cost=dict(type="IoUCost", weight=0.0)))
+    for l in range(NL):
+        for b, G in enumerate(c["counts"]):
+            s = int(c["gt_start"][b])
+            blk = cost[l, Q * s:Q * (s + G)].reshape(Q, G)
+            torch.testing.assert_close(blk.double(), want[l][b], rtol=1e-5, atol=1e-5)
+            # the reference-structured assigner (one cost matrix per (layer, sample)) gives the same assignment
+            res = assigner.assign(c["box"][l, b], c["cls"][l, b], c["centred"][b], c["labels"][b].long())
+            assert torch.equal(res.gt_inds - 1, torch.from_numpy(matched[l, b]).long())
+            assert int((matched[l, b] >= 0).sum()) == min(Q, G)
+            if G:
+                rows, cols = linear_sum_assignment(want[l][b].numpy())
+                got = float(want[l][b][np.nonzero(matched[l, b] >= 0)[0], matched[l, b][matched[l, b] >= 0]].sum())
+                assert abs(got - float(want[l][b][rows, cols].sum())) <= 1e-6 * abs(got)
+
+
+@pytest.mark.parametrize("case", CASES, ids=[f"case{c[0]}" for c in CASES])
+def test_torch_composition_of_the_loss_matches_fp64_forward_and_backward(case):
+    from vidar_amd.plugin.dense_heads import det_ops as D
+    seed, NL, B, Q, C, counts = case
+    c = tail_case(seed, NL, B, Q, C, [min(n, 40) for n in counts])
+    c["gt_label"] = c["gt_label"] % C
+    cost = D.match_cost_torch(c["cls"], c["box"], c["gt_norm"], c["gt_label"], c["counts"], 0.25, 2.0, 2.0, 0.25)
+    matched = torch.from_numpy(D.solve(cost.numpy(), NL, Q, c["counts"]))
+    labels = D.labels_from_matched(matched, c["gt_label"], c["gt_start"], C)
+    assert int((labels < C).sum()) == int((matched >= 0).sum())
+    cw = torch.tensor([1.0] * 8 + [0.2] * 2)
+    cls, box = c["cls"].clone().requires_grad_(True), c["box"].clone().requires_grad_(True)
+    sums = D.det_loss_sums_torch(cls, box, labels, matched, c["gt_norm"], c["gt_start"], cw, 0.25, 2.0)
+    assert torch.isfinite(sums).all()
+    torch.testing.assert_close(sums.double(), loss_fp64(c, labels, matched, cw), rtol=2e-5, atol=1e-5)
+    w = torch.tensor([[1.0, 0.5]]).repeat(NL, 1)
+    g_cls, g_box = torch.autograd.grad((sums * w).sum(), [cls, box])
+    c64 = dict(c, cls=c["cls"].double().requires_grad_(True), box=c["box"].double().requires_grad_(True),
+               gt_norm=c["gt_norm"].double())
+    s64 = D.det_loss_sums_torch(c64["cls"], c64["box"], labels, matched, c64["gt_norm"], c["gt_start"], cw.double(), 0.25, 2.0)
+    r_cls, r_box = torch.autograd.grad((s64 * w.double()).sum(), [c64["cls"], c64["box"]])
+    torch.testing.assert_close(g_cls.double(), r_cls, rtol=1e-5, atol=1e-6)
+    torch.testing.assert_close(g_box.double(), r_box, rtol=1e-5, atol=1e-6)
+    assert torch.isfinite(g_cls).all() and torch.isfinite(g_box).all()
+    if sum(c["counts"]) == 0:
+        assert float(sums[:, 1].detach().abs().max()) == 0.0 and float(g_box.abs().max()) == 0.0
+
+
+def small_head(num_query=12, seed=0):
+    torch.manual_seed(seed)
+    cfg = get_config("finetune/vidar_1_8_nusc_1future", bev_h=8, bev_w=8)["model"]
+    cfg["pts_bbox_head"]["num_query"] = num_query
+    model = P.build_detector(cfg)
+    model.init_weights()
+    return model
+
+
+@pytest.mark.parametrize("counts", [[5, 20], [0, 3], [0, 0]])
+def test_head_loss_composition_equals_the_reference_structured_loss(counts):
+    """BEVFormerHead.loss on CPU tensors runs loss_single per decoder layer (assigner, FocalLoss, L1Loss as the reference);
+    the packed composition the fused kernels implement must give the same dictionary."""
+    from vidar_amd.plugin.core_bbox import LiDARInstance3DBoxes, normalize_bbox
+    from vidar_amd.plugin.dense_heads import det_ops as D
+    head = small_head().pts_bbox_head
+    NL, B, Q, C = 6, 2, 12, 10
+    c = tail_case(11, NL, B, Q, C, counts)
+    preds = dict(all_cls_scores=c["cls"], all_bbox_preds=c["box"], enc_cls_scores=None, enc_bbox_preds=None)
+    ref = head.loss([LiDARInstance3DBoxes(r) for r in c["raw"]], [l for l in c["labels"]], preds)
+    assert set(ref) == {"loss_cls", "loss_bbox"} | {f"d{i}.{k}" for i in range(5) for k in ("loss_cls", "loss_bbox")}
+    cost = D.match_cost_torch(c["cls"], c["box"], c["gt_norm"], c["gt_label"], counts, 0.25, 2.0, 2.0, 0.25)
+    matched = D.hungarian(cost, NL, Q, counts)
+    labels = D.labels_from_matched(matched, c["gt_label"], c["gt_start"], C)
+    sums = D.det_loss_sums_torch(c["cls"], c["box"], labels, matched, c["gt_norm"], c["gt_start"], head.code_weights, 0.25, 2.0)
+    pos = max(sum(min(Q, g) for g in counts), 1)
+    for l in range(NL):
+        key = "" if l == NL - 1 else f"d{l}."
+        torch.testing.assert_close(sums[l, 0] * 2.0 / pos, ref[key + "loss_cls"], rtol=1e-5, atol=1e-6)
+        torch.testing.assert_close(sums[l, 1] * 0.25 / pos, ref[key + "loss_bbox"], rtol=1e-5, atol=1e-6)
+
+
+def test_box_code_round_trip_and_coder():
+    from vidar_amd.plugin.core_bbox import NMSFreeCoder, denormalize_bbox, normalize_bbox
+    from vidar_amd.synthetic import boxes_3d
+    raw = torch.from_numpy(boxes_3d(5, num=20, nan_velocity_rate=0.0)[0])
+    code = normalize_bbox(raw)
+    assert code.shape == (20, 10)
+    torch.testing.assert_close(code[:, 2], raw[:, 3].log())
+    torch.testing.assert_close(code[:, 4], raw[:, 2])
+    torch.testing.assert_close(denormalize_bbox(code), raw, rtol=1e-5, atol=1e-5)
+    coder = NMSFreeCoder(pc_range=[-51.2, -51.2, -5.0, 51.2, 51.2, 3.0], post_center_range=[-61.2, -61.2, -10.0, 61.2, 61.2, 10.0],
+                         max_num=7, num_classes=10)
+    scores = torch.full((1, 1, 20, 10), -5.0)
+    scores[0, 0, 3, 4], scores[0, 0, 9, 1], scores[0, 0, 9, 2] = 3.0, 2.0, 1.0
+    far = code.clone(); far[3, 0] = 100.0                              # the best query lies outside the post-centre range
+    out = coder.decode(dict(all_cls_scores=scores, all_bbox_preds=far[None, None]))[0]
+    assert out["labels"][:2].tolist() == [1, 2] and len(out["scores"]) == 6
+    torch.testing.assert_close(out["bboxes"][0], raw[9], rtol=1e-5, atol=1e-5)
+    torch.testing.assert_close(out["scores"][:2], torch.sigmoid(torch.tensor([2.0, 1.0])))
+
+
+def test_training_step_and_video_inference_on_cpu_oracle():
+    """forward_train end to end on the oracle-routed ops (every trainable parameter gets a gradient), then forward_test
+    over a 3-frame, 2-scene sequence: scene-change reset, can_bus delta rewriting, prev_bev carry."""
+    from oracle import cpu_ops
+    from vidar_amd import train as T
+    from vidar_amd.plugin.core_bbox import LiDARInstance3DBoxes
+    from vidar_amd.synthetic import fpn_features, make_sample
+    torch.manual_seed(0); np.random.seed(0)
+    cfg = get_config("finetune/vidar_1_8_nusc_1future", bev_h=24, bev_w=24)
+    cfg["model"]["pts_bbox_head"]["num_query"] = 30
+    model = T.build_model(cfg).train()
+    opt = T.build_optimizer(model)
+    metas, _, boxes, labels = make_sample(0, queue_length=cfg["queue_length"], rays_per_frame=10, with_boxes=True)
+    feats = fpn_features(0, 4, shapes=FPN_SMALL)
+    batch = dict(img_metas=[metas], img_feats=feats, gt_bboxes_3d=[LiDARInstance3DBoxes(boxes)],
+                 gt_labels_3d=[torch.from_numpy(labels)])
+    with cpu_ops.patched():
+        total, parts = T.train_step(model, opt, batch)
+    assert torch.isfinite(total)
+    assert set(parts) == {"loss_cls", "loss_bbox"} | {f"d{i}.{k}" for i in range(5) for k in ("loss_cls", "loss_bbox")}
+    missing = [n for n, p in model.named_parameters() if p.requires_grad and p.grad is None]
+    assert not missing, missing
+
+    model.eval()
+    seq = [copy.deepcopy(metas[1]), copy.deepcopy(metas[2]), copy.deepcopy(metas[3])]
+    for m, pose in zip(seq, ([10.0, 5.0, 0.0, 30.0], [11.0, 5.5, 0.0, 33.0], [50.0, 9.0, 0.0, 90.0])):
+        m["can_bus"][:3], m["can_bus"][-1] = pose[:3], pose[3]
+    seq[2]["scene_token"] = "another scene"
+    seen, results = [], []
+    inner = model.pts_bbox_head.forward
+
+    def spy(mlvl_feats, img_metas, prev_bev=None, only_bev=False):
+        seen.append((None if prev_bev is None else prev_bev.clone(), img_metas[0]["can_bus"].copy()))
+        return inner(mlvl_feats, img_metas, prev_bev=prev_bev, only_bev=only_bev)
+    model.pts_bbox_head.forward = spy
+    with cpu_ops.patched():
+        for t, m in enumerate(seq):
+            results.append(model(return_loss=False, img_metas=[[m]], img_feats=[[f[:, t] for f in feats]]))
+            if t == 0:
+                bev0 = model.prev_frame_info["prev_bev"].clone()
+    # frame 0: first of its scene -> no history, zero ego motion
+    assert seen[0][0] is None and np.all(seen[0][1][:3] == 0) and seen[0][1][-1] == 0
+    # frame 1: same scene -> the BEV of frame 0 is carried, can_bus holds the deltas to frame 0
+    assert torch.equal(seen[1][0], bev0)
+    np.testing.assert_allclose(seen[1][1][:3], [1.0, 0.5, 0.0]); np.testing.assert_allclose(seen[1][1][-1], 3.0)
+    # frame 2: scene change -> reset
+    assert seen[2][0] is None and np.all(seen[2][1][:3] == 0) and seen[2][1][-1] == 0
+    np.testing.assert_allclose(model.prev_frame_info["prev_pos"], [50.0, 9.0, 0.0])
+    assert model.prev_frame_info["prev_angle"] == 90.0 and model.prev_frame_info["scene_token"] == "another scene"
+    for r in results:
+        box = r[0]["pts_bbox"]
+        n = len(box["boxes_3d"])
+        assert 0 < n <= 300 and box["boxes_3d"].tensor.shape == (n, 9) and box["scores_3d"].shape == (n,)
+        assert bool((box["scores_3d"][:-1] >= box["scores_3d"][1:]).all()) and int(box["labels_3d"].max()) < 10
+        assert bool((box["boxes_3d"].tensor[:, 3:6] > 0).all())
+
+
+def test_vidar_checkpoint_hands_over_to_bevformer_with_exactly_the_named_keys(tmp_path):
+    from vidar_amd import checkpoint as C
+    torch.manual_seed(1)
+    vidar = P.build_detector(get_config("vidar_1_8_nusc_1future", bev_h=8, bev_w=8)["model"])
+    vidar.init_weights()
+    path = C.save_checkpoint(vidar, tmp_path / "latest.pth")
+    det = small_head(seed=2)
+    before = {k: v.clone() for k, v in det.state_dict().items()}
+    _, missing, unexpected = C.load_checkpoint(det, path, strict=False)
+    # the detection-only tensors: decoder, cls_branches, reg_branches, query_embedding, transformer.reference_points.
+    # `code_weights` is NOT among them: the ViDAR head keeps that buffer-like parameter (tests/test_plugin_cpu.py requires
+    # "pts_bbox_head.code_weights" in ViDAR's state_dict, as the released checkpoints have it), so it is handed over.
+    want = sorted(k for k in before if k.startswith(DET_KEYS[:5]))
+    assert missing and sorted(missing) == want
+    assert "pts_bbox_head.code_weights" in vidar.state_dict() and "pts_bbox_head.code_weights" not in missing
+    assert unexpected and all(k.startswith("future_pred_head.") for k in unexpected)
+    assert sorted(unexpected) == sorted(k for k in vidar.state_dict() if k.startswith("future_pred_head."))
+    src = vidar.state_dict()
+    shared = [k for k in before if k in src]
+    assert len(shared) > 100 and "pts_bbox_head.transformer.encoder.layers.2.latent_render.lora_b.weight" in shared
+    for k, v in det.state_dict().items():
+        assert torch.equal(v, src[k] if k in src else before[k]), k
+
+
+def test_vidar_is_built_exactly_as_before():
+    """the detection decoder named in ViDAR's config is neither built nor does it draw random numbers: the same seed gives the
+    same tensors with and without a decoder entry in the config, and none of the detection keys exist.  (That ViDAR's own
+    initialisation stream and arithmetic are what they were before this branch existed is what the recorded goldens check:
+    tests/test_detector_golden_cpu.py, test_transformer_golden_cpu.py, test_reference_golden_gpu.py.)"""
+    def build(with_decoder):
+        cfg = get_config("vidar_1_8_nusc_1future", bev_h=8, bev_w=8)["model"]
+        if with_decoder:
+            cfg["pts_bbox_head"]["transformer"]["decoder"] = get_config("finetune/vidar_1_8_nusc_1future")["model"][
+                "pts_bbox_head"]["transformer"]["decoder"]
+        torch.manual_seed(3); np.random.seed(3)
+        m = P.build_detector(cfg)
+        m.init_weights()
+        return m
+    a, b = build(False).state_dict(), build(True).state_dict()
+    assert list(a) == list(b)
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
+    assert not any(k.startswith(DET_KEYS[:5]) for k in a)
+    m = build(True)
+    assert m.pts_bbox_head.transformer.decoder is None
+    assert not hasattr(m.pts_bbox_head.transformer, "reference_points")
+
+
+def test_synthetic_boxes_are_seeded_and_leave_the_sample_alone():
+    from vidar_amd.synthetic import PC_RANGE, boxes_3d, make_sample
+    plain = make_sample(4, rays_per_frame=20)
+    both = make_sample(4, rays_per_frame=20, with_boxes=True)
+    assert len(plain) == 2 and len(both) == 4 and np.array_equal(plain[1], both[1])
+    assert all(np.array_equal(a["can_bus"], b["can_bus"]) for a, b in zip(plain[0], both[0]))
+    sizes = set()
+    for seed in range(40):
+        box, lab = boxes_3d(seed)
+        again, _ = boxes_3d(seed)
+        assert np.array_equal(box, again, equal_nan=True)
+        assert box.shape == (len(lab), 9) and box.dtype == np.float32 and lab.dtype == np.int64 and 0 <= len(lab) <= 150
+        if len(lab):
+            assert (box[:, 3:6] > 0).all() and lab.min() >= 0 and lab.max() < 10
+            assert (box[:, :2] > PC_RANGE[0]).all() and (box[:, :2] < PC_RANGE[3]).all()
+        sizes.add(len(lab))
+    assert len(sizes) > 20 and boxes_3d(0, num=0)[0].shape == (0, 9)
+
+
+# ---- ABI ------------------------------------------------------------------------------------------------------------
+DET_ENTRY_POINTS = ("vidar_det_match_cost_f32", "vidar_det_loss_workspace_bytes", "vidar_det_loss_fwd_f32",
+                    "vidar_det_loss_bwd_f32")
+
+
+def test_abi_declares_and_exports_the_detection_loss_entry_points():
+    from vidar_amd import build
+    header = (ROOT / "include" / "vidar_hip.h").read_text()
+    lib = ctypes.CDLL(str(build.build(verbose=False)))
+    for name in DET_ENTRY_POINTS:
+        assert name + "(" in header and hasattr(lib, name), name
+    f = lib.vidar_det_loss_workspace_bytes
+    f.restype = ctypes.c_size_t
+    assert f(6, 1, 900) == 6 * 15 * 2 * 8 and f(6, 2, 900) == 6 * 29 * 2 * 8 and f(0, 1, 900) == 0    # fp64 partials
+
+
+def test_no_cpu_path_behind_the_detection_entry_points():
+    from vidar_amd.plugin.dense_heads import det_ops as D
+    c = tail_case(1, 2, 1, 6, 10, [3])
+    with pytest.raises(RuntimeError):
+        D.match_cost(c["cls"], c["box"], c["gt_norm"], c["gt_label"], c["gt_start"], 3, 0.25, 2.0, 2.0, 0.25)
+    m = torch.full((2, 1, 6), -1, dtype=torch.int32)
+    with pytest.raises(RuntimeError):
+        D.DetLossFunction.apply(c["cls"], c["box"], m + 11, m, c["gt_norm"], c["gt_start"], torch.ones(10), 0.25, 2.0)
+
+
+def test_source_tree_holds_none_of_the_refused_words():
+    """scalar stores / scalar atomics / scalar cache write-backs and the runtime switch named in the GPU pool's rules: not in
+    any source file, comments and strings included (documents may speak of them)"""
+    stems = ["s_" + "store_dword", "s_buffer_" + "store", "s_scratch_" + "store", "s_" + "atomic_", "s_buffer_" + "atomic",
+             "s_dcache_" + "wb", "s_dcache_" + "discard", "DEBUG_HIP_FORCE_" + "GRAPH_QUEUES", "HSA_" + "XNACK=1", "xnack" + "+"]
+    pat = re.compile("(?<![A-Za-z0-9])(?:" + "|".join(re.escape(s) for s in stems) + ")", re.I)    # whole mnemonics only
+    hits = []
+    roots = [ROOT / d for d in ("include", "vidar_amd", "tools", "tests", "oracle")]
+    files = [f for r in roots for f in r.rglob("*")] + list(ROOT.glob("*.py")) + list(ROOT.glob("*.sh"))
+    for f in files:
+        if not f.is_file() or f.suffix in (".md", ".rst", ".txt", ".so", ".o", ".npz", ".pyc", ".pth") \
+                or "_ref" in f.parts or "_obj" in f.parts or f.stat().st_size > (4 << 20):
+            continue
+        try:
+            text = f.read_text()
+        except (UnicodeDecodeError, OSError):
+            continue
+        if pat.search(text):
+            hits.append(str(f.relative_to(ROOT)))
+    assert not hits, hits

@@ -501,6 +501,69 @@ def bench_gemm_pmc(which):
     torch.cuda.synchronize()
 
 
+def det_operands(seed, NL, B, Q, C, counts, device):
+    """synthetic operands of the detection loss tail: logits, box codes, packed normalised ground truth"""
+    from vidar_amd.plugin.core_bbox import normalize_bbox
+    from vidar_amd.plugin.dense_heads import det_ops
+    from vidar_amd.synthetic import boxes_3d
+    g = torch.Generator().manual_seed(seed)
+    cls = (torch.randn(NL, B, Q, C, generator=g) * 2 - 3).to(device)
+    box = torch.randn(NL, B, Q, 10, generator=g).to(device)
+    bl = [boxes_3d(seed + b, num=n) for b, n in enumerate(counts)]
+    raw = torch.from_numpy(np.concatenate([b for b, _ in bl])).to(device)
+    raw = torch.cat([raw[:, :2], raw[:, 2:3] + raw[:, 5:6] * 0.5, raw[:, 3:]], 1)
+    gt_norm = normalize_bbox(raw) if raw.shape[0] else torch.zeros((0, 10), device=device)
+    gt_label = torch.from_numpy(np.concatenate([l for _, l in bl])).to(device=device, dtype=torch.int32)
+    gt_start = torch.from_numpy(det_ops.gt_starts(counts)).to(device)
+    cw = torch.tensor([1.0] * 8 + [0.2] * 2, device=device)
+    return cls, box, gt_norm.contiguous(), gt_label, gt_start, cw
+
+
+def bench_det(which):
+    """the detection loss tail of one fine-tune step (NL 6, B 1, Q 900, C 10): fused HIP kernels against the plain PyTorch
+    composition of the same arithmetic, same process.  Device time per piece by HIP events (median of 5 x 50), and the
+    whole tail -- cost, host assignment, losses forward + backward -- by wall clock with a device drain (median of 30)."""
+    import time
+    from vidar_amd.plugin.dense_heads import det_ops as D
+    dev = torch.device("cuda", 0)
+    NL, B, Q, C = 6, 1, 900, 10
+    for G in (37, 150):
+        counts = [G]
+        cls, box, gt_norm, gt_label, gt_start, cw = det_operands(G, NL, B, Q, C, counts, dev)
+        cls.requires_grad_(True); box.requires_grad_(True)
+        args = (0.25, 2.0, 2.0, 0.25)
+        matched = D.hungarian(D.match_cost(cls, box, gt_norm, gt_label, gt_start, G, *args), NL, Q, counts)
+        labels = D.labels_from_matched(matched, gt_label, gt_start, C)
+        gsum = torch.ones(NL, 2, device=dev)
+
+        def loss_pair(fn):
+            s = fn(cls, box, labels, matched, gt_norm, gt_start, cw, 0.25, 2.0)
+            torch.autograd.grad(s, [cls, box], gsum)
+
+        def tail(fused):
+            cost = (D.match_cost(cls, box, gt_norm, gt_label, gt_start, G, *args) if fused
+                    else D.match_cost_torch(cls.detach(), box.detach(), gt_norm, gt_label, counts, *args))
+            m = D.hungarian(cost, NL, Q, counts)
+            lab = D.labels_from_matched(m, gt_label, gt_start, C)
+            s = (D.DetLossFunction.apply if fused else D.det_loss_sums_torch)(cls, box, lab, m, gt_norm, gt_start, cw, 0.25, 2.0)
+            torch.autograd.grad(s, [cls, box], gsum)
+
+        med = lambda f: float(np.median([timeit(f, warm=5, it=50) for _ in range(5)]))
+        r = dict(G=G,
+                 cost_hip_ms=med(lambda: D.match_cost(cls, box, gt_norm, gt_label, gt_start, G, *args)),
+                 cost_torch_ms=med(lambda: D.match_cost_torch(cls.detach(), box.detach(), gt_norm, gt_label, counts, *args)),
+                 loss_fwd_bwd_hip_ms=med(lambda: loss_pair(D.DetLossFunction.apply)),
+                 loss_fwd_bwd_torch_ms=med(lambda: loss_pair(D.det_loss_sums_torch)))
+        for name, fused in (("tail_wall_hip_ms", True), ("tail_wall_torch_ms", False)):
+            ts = []
+            for i in range(35):
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                tail(fused)
+                torch.cuda.synchronize(); ts.append((time.perf_counter() - t0) * 1e3)
+            r[name] = float(np.median(ts[5:]))
+        report("det_loss_tail", r.pop("loss_fwd_bwd_hip_ms"), **{k: round(v, 4) if isinstance(v, float) else v for k, v in r.items()})
+
+
 if __name__ == "__main__":
     import os
     if os.environ.get("VIDAR_MSDA_ITEM_ORDER") is not None:          # A/B of the gather kernels' item order (0 banded, 1 head-major)

@@ -8,7 +8,11 @@
 Every rank evaluates samples rank, rank+W, ... (synthetic generator, or with --ann-file the validation info pkl
 read by vidar_amd.data in test mode: full history required, key-frame cloud only, no augmentation), the
 per-sample `frame.k` dicts are gathered over the process group (RCCL) and rank 0 prints the
-reference's summary (chamfer distance, L1 and AbsRel ray errors per future frame)."""
+reference's summary (chamfer distance, L1 and AbsRel ray errors per future frame).
+
+A detection recipe (finetune/...) runs the BEVFormer detector in video mode instead: the frames of each synthetic sequence go
+through forward_test one by one (the previous frame's BEV carried along, reset at a scene change) and the decoded boxes of
+every frame are printed -- count, best scores, labels.  NDS / mAP need the nuScenes devkit and are not computed."""
 import argparse
 import json
 import os
@@ -61,6 +65,8 @@ def main(argv=None):
     model = T.build_model(meta["model"]).to(dev)
     if args.checkpoint:
         C.load_checkpoint(model, args.checkpoint, map_location=dev)
+    if meta.get("task") == "detection":
+        return video_detection(model, meta, args, dev, rank, world)
     n_future = meta["model"]["test_future_frame_num"]
 
     def batch(i):
@@ -101,6 +107,40 @@ def main(argv=None):
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
+
+
+def video_detection(model, meta, args, dev, rank, world):
+    import copy
+    from vidar_amd.synthetic import fpn_features, make_sample
+    if args.ann_file or args.submission:
+        raise SystemExit("detection recipes evaluate synthetic sequences only (no box annotations in the data reader, no "
+                         "submission format); --ann-file / --submission do not apply")
+    model.eval()
+    T_img = meta["queue_length"] + 1
+    records = []
+    for i in range(rank, args.samples, world):
+        metas = make_sample(50000 + i, queue_length=meta["queue_length"], future_frames=0, rays_per_frame=1,
+                            num_cams=meta["num_cams"], img_hw=meta["img_hw"])[0]
+        if args.no_backbone:
+            feats = fpn_features(i, T_img, num_cams=meta["num_cams"], shapes=meta["fpn_shapes"], device=dev)
+        else:
+            g = torch.Generator().manual_seed(50000 + i)
+            img = torch.randn(1, T_img, meta["num_cams"], 3, *meta["img_hw"], generator=g).to(dev)
+        pose = np.zeros(4)
+        for t in range(T_img):
+            m = copy.deepcopy(metas[t])
+            pose += [*m["can_bus"][:3], m["can_bus"][-1]]               # forward_test expects absolute ego poses
+            m["can_bus"][:3], m["can_bus"][-1] = pose[:3], pose[3]
+            kw = dict(img_feats=[[f[:, t] for f in feats]]) if args.no_backbone else dict(img=[img[:, t]])
+            box = model(return_loss=False, img_metas=[[m]], **kw)[0]["pts_bbox"]
+            records.append(dict(sample=m["sample_idx"], frame=t, boxes=len(box["boxes_3d"]),
+                                top_scores=[round(float(v), 4) for v in box["scores_3d"][:3]],
+                                top_labels=[int(v) for v in box["labels_3d"][:3]],
+                                top_box=[round(float(v), 3) for v in box["boxes_3d"].tensor[0]] if len(box["boxes_3d"]) else None))
+            print(json.dumps(records[-1]), flush=True)
+    if args.out:                                     # this rank's frames
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(json.dumps(records, indent=1))
 
 
 if __name__ == "__main__":

@@ -1,6 +1,7 @@
 """Thin launcher (the reference: tools/train.py + tools/dist_train.sh around mmcv's runner):
 
     python tools/train.py vidar_1_8_nusc_1future --iters 100 --work-dir work_dirs/demo
+    python tools/train.py finetune/vidar_1_8_nusc_1future --load-from work_dirs/demo/latest.pth --iters 100
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/train.py \
         /path/to/released/config.py --iters 1000 --cfg-options model.supervise_all_future=False
 
@@ -28,6 +29,9 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--work-dir", default="work_dirs/run")
     ap.add_argument("--resume-from")
+    ap.add_argument("--load-from", help="checkpoint whose weights initialise the model (fine-tuning: a ViDAR pre-training "
+                                        "checkpoint handed over to the BEVFormer detector); default: the recipe's load_from "
+                                        "when that file exists")
     ap.add_argument("--no-backbone", action="store_true")
     ap.add_argument("--rays-per-frame", type=int, default=30000)
     ap.add_argument("--samples", type=int, default=4, help="distinct synthetic samples cycled per rank")
@@ -40,7 +44,7 @@ def main():
 
     from vidar_amd import checkpoint as C
     from vidar_amd import train as T
-    from vidar_amd.configs import VARIANTS, get_config
+    from vidar_amd.configs import FINETUNE, VARIANTS, get_config
     from vidar_amd.plugin.config import Config
     from vidar_amd.synthetic import fpn_features, make_sample
 
@@ -48,7 +52,7 @@ def main():
     dev = torch.device("cuda", local)
     torch.cuda.set_device(local)
     file_cfg = None
-    if args.config in VARIANTS:
+    if args.config in VARIANTS or args.config in FINETUNE:
         meta = get_config(args.config, with_backbone=not args.no_backbone)
         model_cfg, opt_cfg, clip = meta["model"], meta["optimizer"], meta["grad_clip"]
     else:
@@ -66,6 +70,15 @@ def main():
     gemm_tuning.enable(rank=rank)               # tuned library-GEMM solutions (vidar_amd/gemm_tuning.py)
     torch.manual_seed(args.seed); np.random.seed(args.seed + rank)
     model = T.build_model(model_cfg).to(dev).train()
+    detection = model_cfg["type"] == "BEVFormer"
+    load_from = args.load_from or (meta.get("load_from") if detection and os.path.exists(meta.get("load_from", "")) else None)
+    if load_from:
+        _, missing, unexpected = C.load_checkpoint(model, load_from, map_location=dev, strict=False)
+        if rank == 0:
+            print(f"loaded {load_from}: {len(missing)} tensors keep their initialisation "
+                  f"({sorted({k.split('.')[1] if k.startswith('pts_bbox_head.') else k.split('.')[0] for k in missing})}), "
+                  f"{len(unexpected)} tensors of the checkpoint are not used "
+                  f"({sorted({k.split('.')[0] for k in unexpected})})")
     ddp = T.wrap_ddp(model, local)
     opt = T.build_optimizer(model, **opt_cfg)
     sched = T.CosineWithWarmup(opt, args.iters)
@@ -76,7 +89,22 @@ def main():
         if it0 >= args.iters:
             raise SystemExit(f"checkpoint is at iteration {it0}, --iters {args.iters} leaves nothing to do")
 
+    def detection_sample(i):
+        from vidar_amd.plugin.core_bbox import LiDARInstance3DBoxes
+        T_ = meta["queue_length"] + 1
+        metas, _, boxes, labels = make_sample(1000 * rank + i, queue_length=meta["queue_length"], future_frames=0,
+                                              rays_per_frame=1, num_cams=meta["num_cams"], img_hw=meta["img_hw"], with_boxes=True)
+        b = dict(img_metas=[metas], gt_bboxes_3d=[LiDARInstance3DBoxes(boxes)], gt_labels_3d=[torch.from_numpy(labels)])
+        if args.no_backbone:
+            b["img_feats"] = fpn_features(i, T_, num_cams=meta["num_cams"], shapes=meta["fpn_shapes"], device=dev)
+        else:
+            g = torch.Generator().manual_seed(1000 * rank + i)
+            b["img"] = torch.randn(1, T_, meta["num_cams"], 3, *meta["img_hw"], generator=g).to(dev)
+        return b
+
     def sample(i):
+        if detection:
+            return detection_sample(i)
         metas, gt = make_sample(1000 * rank + i, queue_length=meta["queue_length"],
                                 future_frames=meta["future_frames"], rays_per_frame=args.rays_per_frame,
                                 num_cams=meta["num_cams"], img_hw=meta["img_hw"])
@@ -91,6 +119,8 @@ def main():
     work = Path(args.work_dir)
     if rank == 0:
         work.mkdir(parents=True, exist_ok=True)
+    if args.ann_file and detection:
+        raise SystemExit("detection fine-tuning reads synthetic samples only: the data reader has no box annotations yet")
     if args.ann_file:                      # real data: reader -> rank-sharded sampler -> collate -> device
         from vidar_amd.configs import dataset_kwargs
         from vidar_amd.data import ViDARSequenceDataset

@@ -133,7 +133,68 @@ def model_config(name, bev_h=200, bev_w=200, with_backbone=False):
     return model
 
 
+# Detection fine-tune recipes (projects/configs/vidar_finetune/**): the pre-trained BEV encoder of the ViDAR recipe of the
+# same name under a BEVFormer detection head; `load_from` names the pre-training run whose checkpoint is handed over.
+FINETUNE = {
+    "finetune/vidar_1_8_nusc_1future": dict(pretrain="vidar_1_8_nusc_1future", lr_step=1.0),
+    "finetune/vidar_1_8_nusc_3future": dict(pretrain="vidar_1_8_nusc_3future", lr_step=0.5),
+    "finetune/vidar_full_nusc_1future": dict(pretrain="vidar_full_nusc_1future", lr_step=0.5),
+}
+CLASS_NAMES = ("car", "truck", "construction_vehicle", "bus", "trailer", "barrier", "motorcycle", "bicycle", "pedestrian",
+               "traffic_cone")
+
+
+def finetune_model_config(name, bev_h=200, bev_w=200, with_backbone=False, num_query=900):
+    """model dict of a detection fine-tune recipe: the encoder half of `model_config(pretrain)` (LatentRendering step of
+    the fine-tune file), a 6-layer DetectionTransformerDecoder, focal / L1 losses and the Hungarian assigner."""
+    f = FINETUNE[name]
+    base = model_config(f["pretrain"], bev_h, bev_w, with_backbone)
+    src = base["pts_bbox_head"]
+    transformer = dict(src["transformer"])
+    transformer.pop("num_cams", None)                         # the fine-tune files leave the default (6)
+    enc = transformer["encoder"]
+    enc["transformerlayers"]["latent_render"] = _latent_render(f["lr_step"])
+    enc["transformerlayers"]["attn_cfgs"][1].pop("num_cams", None)
+    transformer.pop("rotate_center", None)
+    if (bev_h, bev_w) != (200, 200):
+        transformer["rotate_center"] = [bev_w // 2, bev_h // 2]
+    transformer["decoder"] = dict(
+        type="DetectionTransformerDecoder", num_layers=6, return_intermediate=True,
+        transformerlayers=dict(type="DetrTransformerDecoderLayer",
+                               attn_cfgs=[dict(type="MultiheadAttention", embed_dims=DIM, num_heads=8, dropout=0.1),
+                                          dict(type="CustomMSDeformableAttention", embed_dims=DIM, num_levels=1)],
+                               feedforward_channels=FFN_DIM, ffn_dropout=0.1,
+                               operation_order=("self_attn", "norm", "cross_attn", "norm", "ffn", "norm")))
+    voxel_size = [0.2, 0.2, 8]
+    head = dict(type="BEVFormerHead", bev_h=bev_h, bev_w=bev_w, num_query=num_query, num_classes=10, in_channels=DIM,
+                sync_cls_avg_factor=True, with_box_refine=True, as_two_stage=False, transformer=transformer,
+                bbox_coder=dict(type="NMSFreeCoder", post_center_range=[-61.2, -61.2, -10.0, 61.2, 61.2, 10.0],
+                                pc_range=PC_RANGE, max_num=300, voxel_size=voxel_size, num_classes=10),
+                positional_encoding=dict(src["positional_encoding"]),
+                loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=2.0),
+                loss_bbox=dict(type="L1Loss", loss_weight=0.25), loss_iou=dict(type="GIoULoss", loss_weight=0.0))
+    model = dict(type="BEVFormer", use_grid_mask=True, video_test_mode=True, backwarded_prev_frame_num=1,
+                 pts_bbox_head=head,
+                 train_cfg=dict(pts=dict(grid_size=[512, 512, 1], voxel_size=voxel_size, point_cloud_range=PC_RANGE,
+                                         out_size_factor=4,
+                                         assigner=dict(type="HungarianAssigner3D", cls_cost=dict(type="FocalLossCost", weight=2.0),
+                                                       reg_cost=dict(type="BBox3DL1Cost", weight=0.25),
+                                                       iou_cost=dict(type="IoUCost", weight=0.0), pc_range=PC_RANGE))))
+    for k in ("img_backbone", "img_neck"):
+        if k in base:
+            model[k] = base[k]
+    return model
+
+
 def get_config(name, bev_h=200, bev_w=200, with_backbone=False):
+    if name in FINETUNE:
+        f = FINETUNE[name]
+        out = get_config(f["pretrain"], bev_h, bev_w, with_backbone)
+        out.update(name=name, model=finetune_model_config(name, bev_h, bev_w, with_backbone), task="detection",
+                   class_names=CLASS_NAMES, load_from=f"work_dirs/{f['pretrain']}/latest.pth",
+                   work_dir=f"work_dirs/fine-tune/{f['pretrain']}")
+        out["queue_length"] = 3          # the detection dataset's queue_length 4 counts the current frame: 3 history frames
+        return out
     v = VARIANTS[name]
     h, w = v["img_hw"]
     shapes = [((h // s) + (1 if h % s else 0), (w // s) + (1 if w % s else 0)) for s in (8, 16, 32, 64)]

@@ -46,6 +46,7 @@ class TransformerLayerSequence(nn.Module):
         self.pre_norm = self.layers[0].pre_norm
 
 
+@TRANSFORMER_LAYER_SEQUENCE.register_module()
 class BEVFormerEncoder(TransformerLayerSequence):
     def __init__(self, *args, pc_range=None, num_points_in_pillar=4, return_intermediate=False,
                  dataset_type="nuscenes", latent_rendering_lid=None, **kwargs):
@@ -273,3 +274,19 @@ class BEVFormerLayerV2(MyCustomBaseTransformerLayer):
                 query = self.ffns[ffn_index](query, identity if self.pre_norm else None, fuse_norm=fuse)
                 ffn_index += 1
         return query
+
+
+@TRANSFORMER_LAYER.register_module()
+class BEVFormerLayer(BEVFormerLayerV2):
+    """encoder.py:256-425: the layer of the plain BEVFormer baseline -- BEVFormerLayerV2 without the latent_render step
+    (the same forward; six operations, no `latent_render` among them)."""
+
+    def __init__(self, attn_cfgs, feedforward_channels, ffn_dropout=0.0, operation_order=None,
+                 act_cfg=dict(type="ReLU", inplace=True), norm_cfg=dict(type="LN"), ffn_num_fcs=2, **kwargs):
+        if "latent_render" in kwargs:
+            raise NotImplementedError("BEVFormerLayer: latent_render (use BEVFormerLayerV2)")
+        super().__init__(attn_cfgs=attn_cfgs, feedforward_channels=feedforward_channels, ffn_dropout=ffn_dropout,
+                         operation_order=operation_order, act_cfg=act_cfg, norm_cfg=norm_cfg, ffn_num_fcs=ffn_num_fcs,
+                         **kwargs)
+        assert len(operation_order) == 6
+        assert set(operation_order) == {"self_attn", "norm", "cross_attn", "ffn"}

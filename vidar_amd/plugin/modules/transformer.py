@@ -1,7 +1,8 @@
 """PerceptionTransformer -- names / kwargs / parameter names / semantics of
-projects/mmdet3d_plugin/bevformer/modules/transformer.py:24-195 (get_bev_features path).  The
-detection decoder of the config is never built: ViDAR deletes it right after construction
-(detectors/vidar.py:105-107)."""
+projects/mmdet3d_plugin/bevformer/modules/transformer.py:24-195 (get_bev_features path) and :197-284
+(forward: BEV features -> object queries -> detection decoder).  The detection decoder of the config is built only on
+request (`build_decoder=True`, which BEVFormerHead sets): ViDAR deletes it right after construction
+(detectors/vidar.py:105-107), so the pre-training model never constructs it and draws no random numbers for it."""
 from __future__ import annotations
 
 import numpy as np
@@ -20,10 +21,14 @@ from .temporal_self_attention import TemporalSelfAttention
 class PerceptionTransformer(nn.Module):
     def __init__(self, num_feature_levels=4, num_cams=6, two_stage_num_proposals=300, encoder=None,
                  decoder=None, embed_dims=256, rotate_prev_bev=True, use_shift=True, use_can_bus=True,
-                 can_bus_norm=True, use_cams_embeds=True, rotate_center=[100, 100], **kwargs):
+                 can_bus_norm=True, use_cams_embeds=True, rotate_center=[100, 100], build_decoder=False,
+                 **kwargs):
         super().__init__()
+        if kwargs.get("as_two_stage"):
+            raise NotImplementedError("PerceptionTransformer: as_two_stage=True")
         self.encoder = build_transformer_layer_sequence(encoder)
-        self.decoder = None                 # config keeps a detection decoder ViDAR never uses
+        # config keeps a detection decoder ViDAR never uses; BEVFormerHead asks for it (build_decoder=True)
+        self.decoder = build_transformer_layer_sequence(decoder) if (build_decoder and decoder is not None) else None
         self.embed_dims = embed_dims
         self.num_feature_levels = num_feature_levels
         self.num_cams = num_cams
@@ -38,7 +43,7 @@ class PerceptionTransformer(nn.Module):
         self.cams_embeds = nn.Parameter(torch.Tensor(num_cams, embed_dims))
         # detection-branch leftover (transformer.py:73): unused on this path, kept so that released
         # checkpoints load with strict=True; frozen so that DDP never waits for its gradient
-        self.reference_points = nn.Linear(embed_dims, 3).requires_grad_(False)
+        self.reference_points = nn.Linear(embed_dims, 3).requires_grad_(self.decoder is not None)
         self.can_bus_mlp = nn.Sequential(nn.Linear(18, embed_dims // 2), nn.ReLU(inplace=True),
                                          nn.Linear(embed_dims // 2, embed_dims), nn.ReLU(inplace=True))
         if can_bus_norm:
@@ -50,8 +55,9 @@ class PerceptionTransformer(nn.Module):
         for p in self.parameters():
             if p.dim() > 1:
                 nn.init.xavier_uniform_(p)
+        from .vidar_decoder import CustomMSDeformableAttention
         for m in self.modules():
-            if isinstance(m, (MSDeformableAttention3D, TemporalSelfAttention)):
+            if isinstance(m, (MSDeformableAttention3D, TemporalSelfAttention, CustomMSDeformableAttention)):
                 m.init_weights()
         nn.init.normal_(self.level_embeds)
         nn.init.normal_(self.cams_embeds)
@@ -108,3 +114,30 @@ class PerceptionTransformer(nn.Module):
                             bev_pos=bev_pos, spatial_shapes=spatial_shapes,
                             level_start_index=level_start_index, prev_bev=prev_bev, shift=shift,
                             **kwargs)
+
+    def forward(self, mlvl_feats, bev_queries, object_query_embed, bev_h, bev_w, grid_length=[0.512, 0.512],
+                bev_pos=None, reg_branches=None, cls_branches=None, prev_bev=None, **kwargs):
+        """transformer.py:197-284 -> (bev_embed [H*W, bs, C], inter_states [layers, num_query, bs, C],
+        init_reference [bs, num_query, 3], inter_references [layers, bs, num_query, 3])"""
+        if self.decoder is None:
+            raise RuntimeError("PerceptionTransformer was built without its detection decoder (build_decoder=True)")
+        bev_embed = self.get_bev_features(mlvl_feats, bev_queries, bev_h, bev_w, grid_length=grid_length,
+                                          bev_pos=bev_pos, prev_bev=prev_bev, **kwargs)      # [bs, H*W, C]
+        # the decoder's deformable attention reads the BEV as ONE level of bev_h x bev_w (checked here from host integers;
+        # CustomMSDeformableAttention's own check would read a device tensor once per decoder layer)
+        assert bev_embed.shape[1] == bev_h * bev_w
+        bs = mlvl_feats[0].size(0)
+        query_pos, query = torch.split(object_query_embed, self.embed_dims, dim=1)
+        query_pos = query_pos.unsqueeze(0).expand(bs, -1, -1)
+        query = query.unsqueeze(0).expand(bs, -1, -1)
+        reference_points = self.reference_points(query_pos).sigmoid()
+        init_reference_out = reference_points
+        query = query.permute(1, 0, 2)
+        query_pos = query_pos.permute(1, 0, 2)
+        bev_embed = bev_embed.permute(1, 0, 2)
+        inter_states, inter_references = self.decoder(
+            query=query, key=None, value=bev_embed, query_pos=query_pos, reference_points=reference_points,
+            reg_branches=reg_branches, cls_branches=cls_branches,
+            spatial_shapes=const_tensor([[bev_h, bev_w]], query.device, torch.long),
+            level_start_index=const_tensor([0], query.device, torch.long), **kwargs)
+        return bev_embed, inter_states, init_reference_out, inter_references

@@ -202,7 +202,8 @@ class CustomMSDeformableAttention(PredictionMSDeformableAttention):
         if not self.batch_first:                     # (num_query, bs, C) -> (bs, num_query, C)
             query = query.permute(1, 0, 2)
             value = value.permute(1, 0, 2)
-        assert int((spatial_shapes[:, 0] * spatial_shapes[:, 1]).sum()) == value.shape[1]
+        if not spatial_shapes.is_cuda:               # on the device the read would be a host sync per decoder layer
+            assert int((spatial_shapes[:, 0] * spatial_shapes[:, 1]).sum()) == value.shape[1]
         batch_first, self.batch_first = self.batch_first, True
         try:
             out = super().forward(query, key, value, identity=torch.zeros_like(query), query_pos=None,

@@ -90,8 +90,10 @@ def camera_matrices(img_hw=(928, 1600), focal=1266.0, centre=(800.0, 450.0), yaw
 
 
 def make_sample(seed=0, queue_length=4, future_frames=2, rays_per_frame=30000, img_hw=(928, 1600),
-                num_cams=6, first_has_prev=False):
-    """-> (img_metas: list[T] of dict, gt_points [sum P, 5] float32).  T = queue_length + 1 image
+                num_cams=6, first_has_prev=False, with_boxes=False):
+    """-> (img_metas: list[T] of dict, gt_points [sum P, 5] float32); with_boxes=True appends the detection ground truth of
+    the current frame, (gt_bboxes_3d [G, 9] float32, gt_labels_3d [G] int64) of `boxes_3d`, drawn from a generator of their
+    own so that the first two results do not depend on the flag.  T = queue_length + 1 image
     frames; GT clouds exist for T + future_frames frames (dataset convention
     datasets/nuscenes_vidar_dataset_v1.py:57-70, :199-200)."""
     rng = np.random.default_rng(seed)
@@ -134,7 +136,33 @@ def make_sample(seed=0, queue_length=4, future_frames=2, rays_per_frame=30000, i
         p = lidar_points(rng, rays_per_frame)
         pts.append(np.concatenate([p, rng.uniform(0, 1, (rays_per_frame, 1)).astype(np.float32),
                                    np.full((rays_per_frame, 1), k, np.float32)], 1))
-    return metas, np.concatenate(pts).astype(np.float32)
+    gt_points = np.concatenate(pts).astype(np.float32)
+    if with_boxes:
+        return (metas, gt_points) + boxes_3d(seed)
+    return metas, gt_points
+
+
+# nuScenes-like (w, l, h) means of the 10 detection classes (car, truck, construction_vehicle, bus, trailer, barrier,
+# motorcycle, bicycle, pedestrian, traffic_cone)
+BOX_SIZES = ((1.95, 4.6, 1.7), (2.5, 6.9, 2.8), (2.8, 6.4, 3.2), (2.9, 11.0, 3.5), (2.9, 12.3, 3.9), (2.5, 0.5, 1.0),
+             (0.8, 2.1, 1.5), (0.6, 1.7, 1.3), (0.7, 0.7, 1.8), (0.4, 0.4, 1.1))
+
+
+def boxes_3d(seed, num=None, pc_range=PC_RANGE, nan_velocity_rate=0.05):
+    """Seeded 3D boxes in the LiDAR frame -> (boxes [G, 9] float32: x, y, z of the BOTTOM face centre, w, l, h, yaw, vx,
+    vy; labels [G] int64 in [0, 10)).  G = `num`, or 0 .. 150 drawn from the seed; centres inside `pc_range`, positive
+    sizes; a few boxes carry NaN velocities, as nuScenes annotations without a velocity estimate do."""
+    rng = np.random.default_rng([int(seed), 0xB0C5])
+    G = int(rng.integers(0, 151)) if num is None else int(num)
+    labels = rng.integers(0, len(BOX_SIZES), G).astype(np.int64)
+    size = np.asarray(BOX_SIZES, dtype=np.float64)[labels].reshape(G, 3) * rng.uniform(0.8, 1.25, (G, 3))
+    lo, hi = np.asarray(pc_range[:3]), np.asarray(pc_range[3:])
+    xy = rng.uniform(lo[:2] + 1.0, hi[:2] - 1.0, (G, 2))
+    z = rng.uniform(-2.5, -0.5, (G, 1))
+    yaw = rng.uniform(-np.pi, np.pi, (G, 1))
+    vel = rng.normal(0.0, 2.0, (G, 2))
+    vel[rng.uniform(0, 1, G) < nan_velocity_rate] = np.nan
+    return np.concatenate([xy, z, size, yaw, vel], 1).astype(np.float32), labels
 
 
 def fpn_features(seed, T, num_cams=6, channels=256, shapes=FPN_SHAPES_NUSC, device="cpu", bs=1):
