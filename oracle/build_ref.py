@@ -22,6 +22,22 @@ gpurun-ignored).  Reference sources are read where they lie and are never copied
 
 gcc on x86-64 without -mfma cannot fuse multiply-adds, so these builds evaluate the reference's
 expressions in strict IEEE order; -ffp-contract=off is passed anyway.
+
+Which pin is which, for the dvr family:
+
+  * HOST SHIM BUILD (above): ref_dvr.so, ref_dvxlr.so, ref_dvxlr_v2.so.  The kernel bodies as written, but the
+    headers, the launch, blockIdx/threadIdx and atomicAdd are stand-ins of ours.  It is what the CPU suite uses
+    (tests/test_oracle_dvr*.py) and what sees every ray set before a GPU does.
+  * DEVICE BUILD: ref_dvr_hip.so, ref_dvxlr_hip.so, ref_dvxlr_v2_hip.so.  The same three .cu files compiled by hipcc
+    for gfx950 as device code against the real torch-ROCm headers, with the reference's own .cpp pybind files
+    (init / render / render_forward, init / render / get_grad_sigma, render_v2 / get_grad_sigma_v2) compiled
+    unmodified beside them.  Nothing of oracle/ref_shim is used.  The text hipcc reads is the reference text under
+    HIP_TOKENS -- the two CUDA includes, `cuda*` runtime identifiers, `X.type()` in the dispatch macro -- and
+    nothing else; kernel bodies, `<<<>>>` launches and atomicAdd stay as written
+    (tests/test_ref_device_build_cpu.py).  -ffp-contract=off as in the host build and in the product, so the three
+    can be compared bit for bit.  It pins oracle/dvr_oracle.c and the product kernels on a GPU
+    (tests/test_reference_device_gpu.py).
+  * GOLDENS: tests/golden/dvr_family_*.npz and e2e_utils.npz are recordings of the host shim build.
 """
 from __future__ import annotations
 
@@ -42,6 +58,41 @@ CU_MODULES = {
     "ref_dvxlr": ("third_lib/dvxlr/dvxlr.cu", "REF_DVXLR"),
     "ref_dvxlr_v2": ("third_lib/dvxlr/dvxlr_v2.cu", "REF_DVXLR_V2"),
 }
+
+
+# The device build (`*_hip.so`): the same three .cu files compiled by hipcc for gfx950 as DEVICE code, next
+# to the reference's own .cpp pybind files (compiled unmodified).  HIP_TOKENS is the whole difference
+# between the reference text and what the compiler reads; tests/test_ref_device_build_cpu.py checks that.
+HIP_TOKENS = (
+    (re.compile(r"#include <cuda(?:_runtime)?\.h>"), "#include <hip/hip_runtime.h>"),
+    (re.compile(r"\bcuda([A-Z]\w*)"), r"hip\1"),
+    (re.compile(r"(\w+)\.type\(\)"), r"\1.scalar_type()"),
+)
+HIP_MODULES = {
+    "ref_dvr_hip": ("third_lib/dvr/dvr.cu", "third_lib/dvr/dvr.cpp"),
+    "ref_dvxlr_hip": ("third_lib/dvxlr/dvxlr.cu", "third_lib/dvxlr/dvxlr.cpp"),
+    "ref_dvxlr_v2_hip": ("third_lib/dvxlr/dvxlr_v2.cu", "third_lib/dvxlr/dvxlr_v2.cpp"),
+}
+HIP_ARCH = "gfx950"
+
+
+def hip_line(line: str) -> tuple[str, int]:
+    """One source line under the token table -> (line, number of table hits)."""
+    hits = 0
+    for pat, repl in HIP_TOKENS:
+        line, n = pat.subn(repl, line)
+        hits += n
+    return line, hits
+
+
+def hip_text(text: str) -> tuple[str, int]:
+    """A reference .cu under the token table, line by line -> (text for hipcc, number of table hits)."""
+    out, hits = [], 0
+    for line in text.split("\n"):
+        line, n = hip_line(line)
+        out.append(line)
+        hits += n
+    return "\n".join(out), hits
 
 
 DCNV3_CUH = "projects/mmdet3d_plugin/bevformer/backbones/ops_dcnv3/src/cuda/dcnv3_im2col_cuda.cuh"
@@ -68,6 +119,58 @@ def _torch_flags():
     cxx = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-w",
            f"-D_GLIBCXX_USE_CXX11_ABI={abi}"]
     return inc, ld, cxx
+
+
+def _torch_hip_flags():
+    import torch
+    from torch.utils.cpp_extension import include_paths, library_paths
+
+    inc = [f"-I{p}" for p in include_paths(device_type="cuda")] + [f"-I{sysconfig.get_paths()['include']}"]
+    libdirs = library_paths(device_type="cuda")
+    ld = [f"-L{p}" for p in libdirs] + [f"-Wl,-rpath,{p}" for p in libdirs]
+    ld += ["-lc10", "-lc10_hip", "-ltorch_cpu", "-ltorch_hip", "-ltorch", "-ltorch_python", "-lamdhip64"]
+    abi = int(torch._C._GLIBCXX_USE_CXX11_ABI)
+    cxx = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-w", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
+           f"-D_GLIBCXX_USE_CXX11_ABI={abi}"]
+    return inc, ld, cxx
+
+
+def _build_hip_module(name: str, verbose: bool) -> Path:
+    """hipcc: the token-table text of the .cu, the reference's .cpp as it lies, one shared library."""
+    cu, cpp = (REF / rel for rel in HIP_MODULES[name])
+    out = so_path(name)
+    if not _needs(out, [cu, cpp, Path(__file__)]):
+        return out
+    inc, ld, cxx = _torch_hip_flags()
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    obj_k = OUT / f"{name}_kernels.o"
+    obj_b = OUT / f"{name}_bind.o"
+    if verbose:
+        print(f"[build_ref] {HIP_MODULES[name][0]} -> {out.name} ({HIP_ARCH} device build)", flush=True)
+    # hipcc drops --offload-arch when the source comes from stdin (the result is a host-only object), so the text
+    # goes through a file in the git-ignored oracle/_ref, which is removed again with the objects
+    tmp = OUT / f"{name}_kernels.hip"
+    tmp.write_text(hip_text(cu.read_text())[0])
+    try:
+        subprocess.run([hipcc, f"--offload-arch={HIP_ARCH}", *cxx, *inc, f"-DTORCH_EXTENSION_NAME={name}",
+                        "-c", str(tmp), "-o", str(obj_k)], check=True)
+    finally:
+        tmp.unlink()
+    subprocess.run([hipcc, *cxx, *inc, f"-DTORCH_EXTENSION_NAME={name}", "-x", "c++", "-c", str(cpp),
+                    "-o", str(obj_b)], check=True)
+    subprocess.run([hipcc, f"--offload-arch={HIP_ARCH}", "-shared", str(obj_k), str(obj_b), *ld, "-o", str(out)],
+                   check=True)
+    obj_k.unlink()
+    obj_b.unlink()
+    return out
+
+
+def build_hip(verbose: bool = True) -> list[Path]:
+    """The three device builds, side by side (three compiler processes)."""
+    from concurrent.futures import ThreadPoolExecutor
+    OUT.mkdir(exist_ok=True)
+    with ThreadPoolExecutor(max_workers=len(HIP_MODULES)) as pool:
+        return list(pool.map(lambda n: _build_hip_module(n, verbose), HIP_MODULES))
 
 
 def available() -> bool:
@@ -133,6 +236,9 @@ def build(verbose: bool = True) -> list[Path]:
         subprocess.run(["g++", *cxx, *inc, f"-I{cd}", "-DTORCH_EXTENSION_NAME=ref_chamferdist_C",
                         "-shared", *map(str, srcs), *ld, "-o", str(out)], check=True)
     built.append(out)
+
+    # --- the same three .cu files as device code for gfx950 ---------------------------------------
+    built += build_hip(verbose)
     return built
 
 

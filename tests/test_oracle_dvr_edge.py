@@ -44,14 +44,20 @@ def test_edge_rays_match_reference_build(ref_modules):
     assert same(rr[0].numpy(), orr[0]) and same(rr[1].numpy(), orr[1])
 
 
-@settings(max_examples=25, deadline=None)
-@given(seed=st.integers(0, 10_000), Z=st.integers(1, 6), Y=st.integers(1, 12), X=st.integers(1, 12),
-       snap=st.booleans())
-def test_random_volumes_match_reference_build(seed, Z, Y, X, snap):
-    from oracle import build_ref
-    if not build_ref.so_path("ref_dvxlr_v2").exists():
-        pytest.skip("oracle/_ref not built")
-    ref = build_ref.load("ref_dvxlr_v2")
+# (seed, Z, Y, X, snap): a fixed sample of what test_random_volumes_match_reference_build draws -- both extremes of
+# every axis, flat / column / single-voxel volumes, snapped and free coordinates.  The GPU suite sends exactly these
+# to the reference's device kernels (tests/test_reference_device_gpu.py); the host build sees them here first.
+FIXED_VOLUMES = [
+    (0, 1, 1, 1, False), (1, 1, 1, 1, True), (2, 6, 12, 12, False), (3, 6, 12, 12, True), (4, 1, 12, 12, True),
+    (5, 6, 1, 1, False), (6, 1, 1, 12, True), (7, 1, 12, 1, False), (8, 6, 1, 12, True), (9, 3, 7, 5, False),
+    (10, 2, 9, 11, True), (11, 4, 4, 4, True), (12, 5, 10, 3, False), (13, 2, 2, 2, True), (14, 6, 11, 7, False),
+    (101, 3, 3, 9, True), (257, 4, 8, 8, False), (999, 5, 5, 12, True), (1234, 1, 6, 6, False), (2048, 2, 12, 2, True),
+    (4097, 6, 6, 1, False), (5000, 3, 12, 4, True), (7777, 4, 2, 10, False), (9999, 5, 9, 9, True), (10000, 6, 3, 6, False),
+]
+
+
+def random_volume(seed, Z, Y, X, snap):
+    """sigma, origin, points, tindex, sigma_regul of one drawn volume (24 rays, ~10 % padded)."""
     rng = np.random.default_rng(seed)
     sigma = rng.uniform(0, 2, (1, 1, Z, Y, X)).astype(np.float32)
     regul = rng.standard_normal(sigma.shape).astype(np.float32)
@@ -62,7 +68,28 @@ def test_random_volumes_match_reference_build(seed, Z, Y, X, snap):
         pts = np.round(pts * 2) / 2
         pts[0][(pts[0] == origin[0, 0]).all(1)] += 1.0
     tindex = np.where(rng.uniform(size=(1, 24)) < 0.1, -1.0, 0.0).astype(np.float32)
+    return sigma, origin, pts, tindex, regul
+
+
+def _random_volume_matches(ref, seed, Z, Y, X, snap):
+    sigma, origin, pts, tindex, regul = random_volume(seed, Z, Y, X, snap)
     r = [x.numpy() for x in ref.render_v2(ts(sigma), ts(origin), ts(pts), ts(tindex), ts(regul))]
     o = O.dvxlr_render(sigma, origin, pts, tindex, regul)
     for a, b, nm in zip(r, o, ["pred", "gt", "dd", "idx", "ray_pred", "indicator"]):
         assert same(a, b), (nm, seed, Z, Y, X, snap)
+
+
+@pytest.mark.parametrize("seed,Z,Y,X,snap", FIXED_VOLUMES)
+def test_fixed_volumes_match_reference_build(seed, Z, Y, X, snap, ref_modules):
+    _random_volume_matches(ref_modules("ref_dvxlr_v2"), seed, Z, Y, X, snap)
+
+
+@settings(max_examples=25, deadline=None)
+@given(seed=st.integers(0, 10_000), Z=st.integers(1, 6), Y=st.integers(1, 12), X=st.integers(1, 12),
+       snap=st.booleans())
+def test_random_volumes_match_reference_build(seed, Z, Y, X, snap):
+    from oracle import build_ref
+    if not build_ref.so_path("ref_dvxlr_v2").exists():
+        pytest.skip("oracle/_ref not built")
+    ref = build_ref.load("ref_dvxlr_v2")
+    _random_volume_matches(ref, seed, Z, Y, X, snap)
