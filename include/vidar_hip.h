@@ -538,6 +538,46 @@ int vidar_det_loss_bwd_f32(const float* cls, const float* box, const int32_t* la
                            const float* grad_sums, float* grad_cls, float* grad_box, float alpha, float gamma, int NL,
                            int B, int Q, int C, int total_g, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Device-side image pipeline (csrc/img_prep.hip, math in csrc/img_prep_math.h): raw uint8 HWC BGR frames -> the fp32
+ * [n, 3, Hp, Wp] network input, with the bits of the host pipeline (PhotoMetricDistortionMultiViewImage, CropResizeFlipImage
+ * = PIL crop / bicubic resize / flip, NormalizeMultiviewImage, RandomScaleImageMultiViewImage, PadMultiViewImage:
+ * projects/mmdet3d_plugin/datasets/pipelines/transform_3d.py:8-190,:295-327, augmentation.py:10-203).  n = all images of a
+ * sample (T * cams); every call is one launch, vidar_img_resample_u8 one per pass (at most two).
+ *
+ * photo [n, 12] f32 (device), per image: [0] shift, [1] gain before the HSV stage, [2] saturation factor, [3] hue turn in
+ *   degrees, [4] gain after the HSV stage, [5] flags (1 shift, 2 gain-before, 4 saturation, 8 turn, 16 gain-after; a step
+ *   whose bit is clear is not evaluated), [6..8] channel permutation, out[c] = in[perm[c]] (0 1 2 = none), [9..11] reserved.
+ *   Every step is one correctly rounded fp32 operation in numpy's order; bit-identical to the host path.
+ * photometric_u8: src [n,H,W,3] u8 -> dst [n,H,W,3] u8, the float -> uint8 rule being: truncate toward zero to int32, keep
+ *   the low 8 bits.  photometric_f32: the same values before the cast, dst [n,H,W,3] f32.
+ * resample_u8: PIL's two-pass 8-bit bicubic resampler of the window (crop_x, crop_y, crop_w, crop_h) of every image
+ *   -> dst [n,out_h,out_w,3] u8, mirrored left-right when `flip`.  tab_x / tab_y (device, int32): [out, 2] pairs (first
+ *   source index inside the window, tap count) followed by [out, ksize] fixed-point coefficients (22 fractional bits),
+ *   ksize = 2 * ceil(2 * max(in / out, 1)) + 1; an output value is clip((sum pixel * k + 2^21) >> 22, 0, 255), horizontal
+ *   pass first, uint8 in between.  A NULL table (with ksize 0) skips that pass and needs in == out; `flip` needs the
+ *   horizontal pass (the in == out table is the identity).  With both passes the intermediate [n,crop_h,out_w,3] plane lives
+ *   in `workspace` (vidar_img_resample_workspace_bytes, caller-owned).  Table CONTENTS cannot send an access outside the
+ *   window (bounds are clamped on the device); the caller guarantees the table's SIZE.
+ * normalise_f32: src [n,H,W,3] u8 -> dst [n,3,Hp,Wp] f32 (16-byte aligned, Wp a multiple of 4): out channel c =
+ *   (in channel (to_rgb ? 2 - c : c) - mean[c]) / stdv[c]; when (out_h, out_w) != (H, W) the normalised values are resized
+ *   bilinearly with torch's align_corners=False rule (scale = float(in) / out, src = scale * (dst + 0.5) - 0.5 clamped at
+ *   0); rows >= out_h and columns >= out_w are written as 0 by the call.  photo != NULL applies the photometric stage to the
+ *   source pixels first, in fp32 without the uint8 cast (the OpenScene order).  mean / stdv: 3 floats each on the HOST.
+ * VIDAR_ERR_BAD_ARG (nothing is launched): a missing pointer, a non-positive size, a window that is not inside the image,
+ *   a ksize that does not belong to (in, out), a skipped pass with in != out, both passes skipped, a workspace that is too
+ *   small, Hp < out_h, Wp < out_w, Wp % 4 != 0, a misaligned dst.
+ * ------------------------------------------------------------------------- */
+#define VIDAR_IMG_PHOTO_FLOATS 12
+int vidar_img_photometric_u8(const uint8_t* src, const float* photo, uint8_t* dst, int n, int H, int W, void* stream);
+int vidar_img_photometric_f32(const uint8_t* src, const float* photo, float* dst, int n, int H, int W, void* stream);
+size_t vidar_img_resample_workspace_bytes(int n, int crop_h, int out_w);
+int vidar_img_resample_u8(const uint8_t* src, uint8_t* dst, int n, int H, int W, int crop_x, int crop_y, int crop_w,
+                          int crop_h, int out_w, int out_h, const int32_t* tab_x, int ksize_x, const int32_t* tab_y,
+                          int ksize_y, int flip, void* workspace, size_t workspace_bytes, void* stream);
+int vidar_img_normalise_f32(const uint8_t* src, const float* photo, float* dst, int n, int H, int W, int out_h, int out_w,
+                            int Hp, int Wp, const float* mean, const float* stdv, int to_rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -564,6 +564,44 @@ def bench_det(which):
         report("det_loss_tail", r.pop("loss_fwd_bwd_hip_ms"), **{k: round(v, 4) if isinstance(v, float) else v for k, v in r.items()})
 
 
+def bench_imgprep(which):
+    """the device image pipeline on one sample (30 images of 900 x 1600, random noise) for the three released pipelines,
+    against the host path (numpy / PIL / torch, this process, its torch threads) on the same images and the same drawn
+    parameters.  Device ms by HIP events (median of 5 x 10); modelled bytes = uint8 in + fp32 out + the uint8 intermediates
+    the kernels actually write and read back.  JPEG decode is not part of either side."""
+    import random
+    import time
+    from vidar_amd.data.augment import CropResizeFlipImage, PhotoMetricDistortionMultiViewImage
+    from vidar_amd.data.device_prep import DeviceImagePrep, host_prep, out_shape
+    n, H, W = 30, 900, 1600
+    raw = torch.from_numpy(np.random.default_rng(0).integers(0, 256, (n, H, W, 3), dtype=np.uint8))
+    dev_raw = raw.cuda()
+    prep = DeviceImagePrep()
+    np.random.seed(0); random.seed(0)
+    photo = PhotoMetricDistortionMultiViewImage().draw(n)
+    _, dims, crop, flip = CropResizeFlipImage().sample({})
+    plans = {"nuscenes_train": dict(photo=photo, resize_dims=dims, crop=crop, flip=flip, img_scale=None),
+             "nuscenes_test": dict(photo=None, resize_dims=None, crop=None, flip=False, img_scale=None),
+             "openscene_train": dict(photo=photo, resize_dims=None, crop=None, flip=False, img_scale=2.0 / 3.0)}
+    for name, plan in plans.items():
+        out = prep(dev_raw, plan)
+        oh, ow = out_shape(plan, H, W)
+        nbytes = raw.numel() + out.numel() * 4
+        if plan["resize_dims"] is not None:
+            nbytes += 2 * raw.numel()                                 # photometric: uint8 plane written, read by the resample
+            if (ow, oh) != (W, H) or plan["flip"]:
+                nbytes += 2 * n * H * ow * 3 * (oh != H)              # horizontal pass' plane, when a vertical pass follows
+                nbytes += 2 * n * oh * ow * 3                         # resampled plane written, read by the normalise
+        ms = float(np.median([timeit(lambda: prep(dev_raw, plan), warm=2, it=10) for _ in range(5)]))
+        k = 2 if name == "nuscenes_train" else 6                      # host: a few images, scaled to the sample
+        t0 = time.perf_counter()
+        host_prep(raw[:k].numpy(), dict(plan, photo=None if plan["photo"] is None else plan["photo"][:k]), prep.mean, prep.std,
+                  prep.to_rgb, prep.size_divisor)
+        host_ms = (time.perf_counter() - t0) * 1e3 * n / k
+        report("imgprep_" + name, ms, nbytes, images=n, out_shape=list(out.shape), host_ms_per_sample=round(host_ms, 1),
+               host_images_timed=k, host_threads=torch.get_num_threads())
+
+
 if __name__ == "__main__":
     import os
     if os.environ.get("VIDAR_MSDA_ITEM_ORDER") is not None:          # A/B of the gather kernels' item order (0 banded, 1 head-major)

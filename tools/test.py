@@ -43,6 +43,8 @@ def main(argv=None):
     ap.add_argument("--eval-stride", type=int, default=None,
                     help="evaluate every N-th usable val index (quick subset); default: the whole split, as the "
                          "reference's data.test does")
+    ap.add_argument("--device-images", action="store_true",
+                    help="with --ann-file: ship uint8 frames and run the image pipeline in HIP kernels (same tensor)")
     args = ap.parse_args(argv)
 
     from vidar_amd import checkpoint as C
@@ -91,12 +93,16 @@ def main(argv=None):
         # a 1/N subset for a quick look
         kw = dataset_kwargs(meta, test_mode=True, test_stride=args.eval_stride)
         kw["future_length"] = n_future
-        ds = ViDARSequenceDataset(args.ann_file, data_root=args.data_root, **kw)
+        from vidar_amd.data.device_prep import DeviceImagePrep
+        from vidar_amd.data.loader import collate, finish_batch
+        prep = DeviceImagePrep() if args.device_images else None
+        ds = ViDARSequenceDataset(args.ann_file, data_root=args.data_root, device_images=args.device_images, **kw)
         n_samples = len(ds) if args.samples <= 0 else min(args.samples, len(ds))
 
         def batch(i):                                                  # noqa: F811  (real data replaces the generator)
             s_ = ds[i]
-            return dict(img=s_["img"][None].to(dev), img_metas=[s_["img_metas"]], gt_points=[s_["gt_points"].to(dev)])
+            img = finish_batch(collate([s_]), dev, prep)["img"] if args.device_images else s_["img"][None].to(dev)
+            return dict(img=img, img_metas=[s_["img_metas"]], gt_points=[s_["gt_points"].to(dev)])
     results = E.multi_gpu_test(model, batch, n_samples)
     if rank == 0:
         summary = E.summarize(results)

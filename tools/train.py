@@ -40,6 +40,9 @@ def main():
     ap.add_argument("--ann-file", help="nuScenes / OpenScene info pkl (data/nuscenes/nuscenes_infos_temporal_train.pkl)")
     ap.add_argument("--data-root", default="")
     ap.add_argument("--workers", type=int, default=4)
+    ap.add_argument("--device-images", action="store_true",
+                    help="with --ann-file: the workers only decode and draw the augmentation, the image pipeline "
+                         "(photometric, crop / resize / flip, normalise, pad) runs in HIP kernels with the host path's bits")
     args = ap.parse_args()
 
     from vidar_amd import checkpoint as C
@@ -126,7 +129,10 @@ def main():
         from vidar_amd.data import ViDARSequenceDataset
         from vidar_amd.data.loader import build_dataloader
         # the recipe's own temporal augmentation / subset stride / GT voxel size (not the reader's defaults)
-        ds = ViDARSequenceDataset(args.ann_file, data_root=args.data_root, augment=True,
+        from vidar_amd.data.device_prep import DeviceImagePrep
+        from vidar_amd.data.loader import finish_batch
+        prep = DeviceImagePrep() if args.device_images else None      # keeps the resample tables of the sizes it has seen
+        ds = ViDARSequenceDataset(args.ann_file, data_root=args.data_root, augment=True, device_images=args.device_images,
                                   **dataset_kwargs(meta, test_mode=False, file_cfg=file_cfg))
         spg = file_cfg.data.samples_per_gpu if file_cfg is not None else meta["data"]["samples_per_gpu"]
         loader = build_dataloader(ds, spg, args.workers, world, rank, args.seed)
@@ -137,7 +143,7 @@ def main():
             def __iter__(self):
                 loader.sampler.set_epoch(self.epoch); self.epoch += 1
                 for b in loader:
-                    yield dict(img=b["img"].to(dev, non_blocking=True), img_metas=b["img_metas"],
+                    yield dict(img=finish_batch(b, dev, prep)["img"], img_metas=b["img_metas"],
                                gt_points=[g.to(dev, non_blocking=True) for g in b["gt_points"]])
         batches = _Epochs()
     else:

@@ -33,10 +33,24 @@ def lib() -> ctypes.CDLL:
         v3 = os.environ.get("VIDAR_DCNV3_VARIANT")              # A/B of the DCNv3 backward's grad_input accumulation (tools)
         if v3 is not None:
             _lib.vidar_dcnv3_set_variant(int(v3))
+        _declare_img(_lib)
         order = os.environ.get("VIDAR_MSDA_ITEM_ORDER")          # A/B of the MSDA gather kernels' item order (tools, bench)
         if order is not None:
             _lib.vidar_msda_set_item_order(int(order))
     return _lib
+
+
+def _declare_img(L):
+    """argument types of the image pipeline (csrc/img_prep.hip): many ints next to pointers and a size_t, so spelled out"""
+    vp, i, f3 = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float)
+    L.vidar_img_photometric_u8.argtypes = [vp, vp, vp, i, i, i, vp]
+    L.vidar_img_photometric_f32.argtypes = [vp, vp, vp, i, i, i, vp]
+    L.vidar_img_resample_workspace_bytes.argtypes = [i, i, i]
+    L.vidar_img_resample_workspace_bytes.restype = ctypes.c_size_t
+    L.vidar_img_resample_u8.argtypes = [vp, vp] + [i] * 9 + [vp, i, vp, i, i, vp, ctypes.c_size_t, vp]
+    L.vidar_img_normalise_f32.argtypes = [vp, vp, vp] + [i] * 7 + [f3, f3, i, vp]
+    for fn in (L.vidar_img_photometric_u8, L.vidar_img_photometric_f32, L.vidar_img_resample_u8, L.vidar_img_normalise_f32):
+        fn.restype = ctypes.c_int
 
 
 def check(rc: int, what: str):

@@ -223,7 +223,12 @@ def union2one(previous_queue: List[dict], future_queue: List[dict], future_lengt
     if len(future_can_bus) < 1 + future_length:
         return None
     out = {k: v for k, v in previous_queue[-1].items() if k not in ("points", "aug_param")}
-    out["img"] = torch.stack([each["img"] for each in previous_queue])
+    if "img_raw" in previous_queue[-1]:      # device-side image pipeline: raw uint8 frames + what the workers drew
+        plans = [each["img_plan"] for each in previous_queue]
+        out["img_raw"] = torch.stack([each["img_raw"] for each in previous_queue])
+        out["img_plan"] = dict(plans[0], photo=None if plans[0]["photo"] is None else np.stack([p["photo"] for p in plans]))
+    else:
+        out["img"] = torch.stack([each["img"] for each in previous_queue])
     out["img_metas"] = metas_map
     out["gt_points"] = torch.from_numpy(np.concatenate(total_pts, 0))
     return out

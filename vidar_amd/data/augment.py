@@ -41,6 +41,31 @@ class CropResizeFlipImage:
         aug_param["CropResizeFlipImage_param"] = (resize, (int(resized_w), int(resized_h)), crop, flip)
         return aug_param["CropResizeFlipImage_param"]
 
+    def draw(self, meta, aug_param, n_imgs=None):
+        """the device path's half of `__call__`: same draws (`sample`), same cam2img / lidar2img update, no pixels.
+        -> (resize, resize_dims, crop, flip)"""
+        resize, resize_dims, crop, flip = self.sample(aug_param)
+        ida = np.eye(3)
+        ida[:2, :2] *= resize
+        ida[:2, 2] = -np.array(crop[:2]) * resize
+        for i in range(len(meta["cam2img"]) if n_imgs is None else n_imgs):
+            meta["cam2img"][i][:3, :3] = np.matmul(ida, meta["cam2img"][i][:3, :3])
+        meta["lidar2img"] = [np.matmul(meta["cam2img"][i], meta["lidar2cam"][i]) for i in range(len(meta["lidar2cam"]))]
+        return resize, resize_dims, crop, flip
+
+    @staticmethod
+    def apply(imgs, param):
+        """the pixel half of `__call__` for drawn parameters: list of HxWx3 arrays -> list of float32 arrays"""
+        from PIL import Image
+        _, resize_dims, crop, flip = param
+        out = []
+        for img in imgs:
+            im = Image.fromarray(np.uint8(img)).crop(crop).resize(resize_dims)
+            if flip:
+                im = im.transpose(method=Image.FLIP_LEFT_RIGHT)
+            out.append(np.array(im).astype(np.float32))
+        return out
+
     def __call__(self, imgs, meta, aug_param):
         """imgs: list of HxWx3 float arrays (BGR, 0..255); meta: needs cam2img + lidar2cam.  -> new list;
         meta['cam2img'] / ['lidar2img'] updated in place (:88-89, :137-138)."""
@@ -123,6 +148,72 @@ class PhotoMetricDistortionMultiViewImage:
         if np.random.randint(2):
             img = img[..., np.random.permutation(3)]
         return img
+
+    # ---- the device path: draw without touching pixels, apply later (vidar_amd/data/device_prep.py) ----
+    # one image's parameters as the float32 row the kernels read (include/vidar_hip.h): shift, gain before the HSV stage,
+    # saturation, hue turn, gain after it, flags, the channel permutation, 3 reserved
+    SHIFT, GAIN_FIRST, SAT, TURN, GAIN_LAST = 1, 2, 4, 8, 16
+
+    def draw_one(self):
+        """consumes numpy's global generator exactly like `_distort` -> float32 [12]"""
+        row = np.zeros(12, np.float32)
+        row[6:9] = (0, 1, 2)
+        flags = 0
+        shift = self._coin_uniform(-self.brightness_delta, self.brightness_delta)
+        if shift is not None:
+            row[0] = shift; flags |= self.SHIFT
+        contrast_first = np.random.randint(2) == 1
+        gain = self._coin_uniform(self.contrast_lower, self.contrast_upper) if contrast_first else None
+        if gain is not None:
+            row[1] = gain; flags |= self.GAIN_FIRST
+        sat = self._coin_uniform(self.saturation_lower, self.saturation_upper)
+        if sat is not None:
+            row[2] = sat; flags |= self.SAT
+        turn = self._coin_uniform(-self.hue_delta, self.hue_delta)
+        if turn is not None:
+            row[3] = turn; flags |= self.TURN
+        gain = None if contrast_first else self._coin_uniform(self.contrast_lower, self.contrast_upper)
+        if gain is not None:
+            row[4] = gain; flags |= self.GAIN_LAST
+        if np.random.randint(2):
+            row[6:9] = np.random.permutation(3)
+        row[5] = flags
+        return row
+
+    def draw(self, n_imgs):
+        """-> float32 [n_imgs, 12], every image its own draws, in order (what `__call__` does to the generator)"""
+        return np.stack([self.draw_one() for _ in range(n_imgs)])
+
+    @classmethod
+    def apply_one(cls, img, row):
+        """`_distort` with drawn parameters: the same numpy operations in the same order (float32 scalars: the value
+        numpy's float32 arithmetic rounds a Python float to)"""
+        img = np.array(img, dtype=np.float32)
+        flags = int(row[5])
+        f32 = lambda k: np.float32(row[k])
+        if flags & cls.SHIFT:
+            img += f32(0)
+        if flags & cls.GAIN_FIRST:
+            img *= f32(1)
+        hsv = bgr2hsv(img)
+        if flags & cls.SAT:
+            hsv[..., 1] *= f32(2)
+        if flags & cls.TURN:
+            hue = hsv[..., 0] + f32(3)
+            hue[hue > 360] -= 360
+            hue[hue < 0] += 360
+            hsv[..., 0] = hue
+        img = hsv2bgr(hsv)
+        if flags & cls.GAIN_LAST:
+            img *= f32(4)
+        perm = [int(k) for k in row[6:9]]
+        if perm != [0, 1, 2]:
+            img = img[..., perm]
+        return img
+
+    @classmethod
+    def apply(cls, imgs, rows):
+        return [cls.apply_one(img, row) for img, row in zip(imgs, rows)]
 
     def __call__(self, imgs):
         """every image of the rig draws its own distortion, in order (numpy's global generator, like the reference's

@@ -6,6 +6,7 @@
                             ViDAR's datasets put every sample in group 0 (mmdet3d `_set_group_flag` [3P]).
   DistributedSampler        samplers/distributed_sampler.py:9-41 (testing): no shuffle, contiguous per-rank shards, padded
                             by repetition.
+  finish_batch              the device half: H2D copy and, for `device_images` samples, the image pipeline's HIP kernels
   collate                   the unwrapping of mmcv DataContainers the reference leaves to mmcv's collate [3P]: images
                             stacked, metas / point clouds as per-sample lists -- the kwargs of ViDAR.forward_train."""
 from __future__ import annotations
@@ -80,12 +81,43 @@ def collate(samples):
     Images of different sizes (CropResizeFlipImage draws a resize per sample) are zero-padded at the bottom /
     right to the largest H and W of the batch, like mmcv's collate does for stacked DataContainers."""
     samples = [s for s in samples if s is not None]
+    if samples and "img_raw" in samples[0]:      # device-side image pipeline: `finish_batch` turns these into `img`
+        return dict(img_raw=[s["img_raw"] for s in samples], img_plan=[s["img_plan"] for s in samples],
+                    img_metas=[s["img_metas"] for s in samples], gt_points=[s["gt_points"] for s in samples])
     imgs = [s["img"] for s in samples]
     H = max(i.shape[-2] for i in imgs); W = max(i.shape[-1] for i in imgs)
     if any(i.shape[-2:] != (H, W) for i in imgs):
         imgs = [torch.nn.functional.pad(i, (0, W - i.shape[-1], 0, H - i.shape[-2])) for i in imgs]
     return dict(img=torch.stack(imgs), img_metas=[s["img_metas"] for s in samples],
                 gt_points=[s["gt_points"] for s in samples])
+
+
+def finish_batch(batch, device, prep=None):
+    """the device half of a batch: `img` on `device`.  A host-path batch is copied; a `device_images` batch has its
+    uint8 frames copied (pinned, non-blocking: a quarter of the fp32 bytes) and put through the image pipeline's kernels
+    (`prep`: a device_prep.DeviceImagePrep), samples of different resized sizes zero-padded at the bottom / right to the
+    batch maximum like `collate` does.  -> the batch with `img` [bs, T, cams, 3, H, W] instead of img_raw / img_plan"""
+    out = {k: v for k, v in batch.items() if k not in ("img_raw", "img_plan")}
+    if "img_raw" not in batch:
+        out["img"] = batch["img"].to(device, non_blocking=True)
+        return out
+    if prep is None:
+        from .device_prep import DeviceImagePrep
+        prep = DeviceImagePrep()
+    imgs = []
+    for raw, plan in zip(batch["img_raw"], batch["img_plan"]):
+        T, cams = raw.shape[:2]
+        if not raw.is_pinned():
+            raw = raw.pin_memory()
+        dev_raw = raw.to(device, non_blocking=True).flatten(0, 1)
+        flat = dict(plan, photo=None if plan["photo"] is None else np.asarray(plan["photo"]).reshape(T * cams, -1))
+        img = prep(dev_raw, flat)
+        imgs.append(img.view(T, cams, *img.shape[1:]))
+    H = max(i.shape[-2] for i in imgs); W = max(i.shape[-1] for i in imgs)
+    if any(i.shape[-2:] != (H, W) for i in imgs):
+        imgs = [torch.nn.functional.pad(i, (0, W - i.shape[-1], 0, H - i.shape[-2])) for i in imgs]
+    out["img"] = torch.stack(imgs)
+    return out
 
 
 def worker_seed(num_workers, rank, worker_id, seed):

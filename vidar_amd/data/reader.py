@@ -180,6 +180,22 @@ def load_raw_images(paths: Sequence) -> list:
     return out
 
 
+def load_raw_images_u8(paths: Sequence) -> list:
+    """`load_raw_images` before its float cast: list of uint8 [H, W, 3] arrays, BGR (the device path ships these)"""
+    from PIL import Image
+    out = []
+    for p in paths:
+        if str(p).endswith(".npy"):
+            a = np.load(p)
+            u8 = a.astype(np.uint8)
+            if not np.array_equal(u8, a):
+                raise ValueError(f"{p}: device_images needs 8-bit images, this array holds other values")
+            out.append(u8)
+        else:
+            out.append(np.ascontiguousarray(np.asarray(Image.open(p).convert("RGB"), dtype=np.uint8)[..., ::-1]))
+    return out
+
+
 def normalise_pad(imgs: Sequence, mean=IMG_NORM["mean"], std=IMG_NORM["std"], to_rgb=IMG_NORM["to_rgb"],
                   size_divisor: int = 32, scale=None):
     """NormalizeMultiviewImage [+ RandomScaleImageMultiViewImage(scales=[scale])] + PadMultiViewImage(size_divisor)
@@ -227,16 +243,29 @@ class TrainAugment:
             imgs = self.photo(imgs)
         return self.crop(imgs, meta, aug_param) if self.crop is not None else imgs
 
+    def draw(self, n_imgs, meta, aug_param):
+        """`__call__` without pixels: the same draws in the same order, the same update of `meta` -> the entries of a
+        device-path plan (vidar_amd/data/device_prep.py)"""
+        plan = dict(photo=self.photo.draw(n_imgs) if self.photo is not None else None)
+        if self.crop is not None:
+            _, resize_dims, crop, flip = self.crop.draw(meta, aug_param, n_imgs)
+            plan.update(resize_dims=tuple(resize_dims), crop=tuple(crop), flip=bool(flip))
+        return plan
+
 
 class ViDARSequenceDataset:
     """`dataset[i]` -> dict(img [T, cams, 3, H, W], img_metas {t: meta}, gt_points [P, 5]): the forward_train /
     forward_test kwargs of one sample (collate = add the batch dimension).
+    `device_images=True`: the workers only decode and draw -- the sample carries `img_raw` (uint8 [T, cams, H, W, 3], BGR)
+    and `img_plan` (the drawn parameters, device_prep.py) instead of `img`, `img_metas` is the host path's, and
+    `loader.finish_batch` computes `img` on the GPU with the host path's bits.
     NuScenesViDARDatasetV1 with the released pipeline (config :279-330, :332-375)."""
 
     def __init__(self, ann_file, data_root="", queue_length=4, future_length=1, test_mode=False,
                  load_interval=1, load_frame_interval=None, rand_frame_interval=(1,),
                  ego_mask=(-0.8, -1.5, 0.8, 2.5), sweeps_num=2, voxel_size=(1.0, 1.0, 1.0),
-                 point_cloud_range=PC_RANGE, max_voxels=50000, dataset="nuscenes", augment=None, img_scale=None):
+                 point_cloud_range=PC_RANGE, max_voxels=50000, dataset="nuscenes", augment=None, img_scale=None,
+                 device_images=False):
         self.infos, self.metadata = load_infos(ann_file, load_interval)
         self.data_root, self.dataset = str(data_root), dataset
         self.queue_length, self.future_length, self.test_mode = queue_length, future_length, test_mode
@@ -248,6 +277,9 @@ class ViDARSequenceDataset:
         self.augment = TrainAugment(crop_resize_flip=dataset == "nuscenes") if augment is True else augment
         # OpenScene resizes the normalised images by 2/3 (RandomScaleImageMultiViewImage) in train AND test pipelines
         self.img_scale = (2.0 / 3.0 if dataset == "nuplan" else None) if img_scale is None else img_scale
+        self.device_images = bool(device_images)
+        if self.device_images and self.augment is not None and not hasattr(self.augment, "draw"):
+            raise TypeError("device_images=True needs an augmentation with a draw(n_imgs, meta, aug_param) method")
         self.usable_index = usable_indices(self.infos, future_length, queue_length, test_mode, load_frame_interval)
 
     def __len__(self):
@@ -271,19 +303,31 @@ class ViDARSequenceDataset:
             pts[:, -1] = 0                                           # on the LAST column (nuplan_loading.py:283-288)
             pts = voxel_point_sampler(pts, self.voxel_size, self.point_cloud_range, self.max_voxels)
         rec = dict(points=torch.from_numpy(np.ascontiguousarray(pts)), img_metas=meta)
-        if with_images:
+        if with_images and self.device_images:
+            from .device_prep import out_shape
+            raw = load_raw_images_u8([self._path(p) for p in meta["img_filename"]])
+            plan = dict(photo=None, resize_dims=None, crop=None, flip=False)
+            if self.augment is not None and not self.test_mode:
+                aug_param = {} if aug_param is None else aug_param
+                plan.update(self.augment.draw(len(raw), meta, aug_param))
+                rec["aug_param"] = aug_param
+            plan["img_scale"] = self.img_scale
+            h, w = out_shape(plan, *raw[0].shape[:2])
+            shape = ((h + 31) // 32 * 32, (w + 31) // 32 * 32, 3)
+            rec["img_raw"], rec["img_plan"], n = torch.from_numpy(np.stack(raw)), plan, len(raw)
+        elif with_images:
             imgs = load_raw_images([self._path(p) for p in meta["img_filename"]])
             if self.augment is not None and not self.test_mode:
                 aug_param = {} if aug_param is None else aug_param
                 imgs = self.augment(imgs, meta, aug_param)
                 rec["aug_param"] = aug_param
             img, shape = normalise_pad(imgs, scale=self.img_scale)
+            rec["img"], n = img, img.shape[0]
+        if with_images:
             if self.img_scale is not None:                           # transform_3d.py:317-323
                 k = np.eye(4); k[0, 0] = k[1, 1] = self.img_scale
                 meta["lidar2img"] = [k @ np.asarray(a) for a in meta["lidar2img"]]
-            n = img.shape[0]
             meta.update(img_shape=[shape] * n, pad_shape=[shape] * n, img_norm_cfg=dict(IMG_NORM))
-            rec["img"] = img
         return rec
 
     def _prepare(self, index, rand_interval=None):
