@@ -28,6 +28,88 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert lib.vidar_dvr_max_d() == 1446 and lib.vidar_dvxlr_max_d() == 1026
 
 
+# the 14 parameter types the header uses -> the kind code of vidar_amd._lib._ABI ("name[6]" parameters count as pointers)
+SCALAR_KINDS = {"int": "i", "float": "f", "int64_t": "l", "size_t": "z", "uint32_t": "u"}
+POINTEES = {"void", "float", "int64_t", "int32_t", "uint8_t"}
+
+
+def header_prototypes():
+    """name -> (return kind, [parameter kinds]) of every prototype of include/vidar_hip.h"""
+    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "vidar_hip.h").read_text(), flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"\b(\w+)\s+(vidar_\w+)\s*\(([^()]*)\)\s*;", text):
+        kinds = []
+        for prm in ([] if params.strip() == "void" else params.split(",")):
+            m = re.fullmatch(r"\s*(const\s+)?(\w+)\s*(\*?)\s*\w+\s*(\[\d*\])?\s*", prm)
+            assert m, f"{name}: cannot read the parameter {prm!r}"
+            const, base, star, array = m.groups()
+            if star or array:
+                assert base in POINTEES, f"{name}: unknown pointer type in {prm!r}"
+                kinds.append("p")
+            else:
+                assert base in SCALAR_KINDS and not const, f"{name}: unknown parameter type in {prm!r}"
+                kinds.append(SCALAR_KINDS[base])
+        assert ret in ("int", "size_t"), f"{name}: unknown return type {ret!r}"
+        assert name not in out, f"{name} is declared twice"
+        out[name] = (SCALAR_KINDS[ret], kinds)
+    return out
+
+
+def test_prototype_table_equals_the_header():
+    from vidar_amd import _lib
+    protos = header_prototypes()
+    assert len(protos) == len(declared_symbols()), sorted(set(declared_symbols()) - set(protos))
+    assert sorted(_lib._ABI) == sorted(protos)
+    for name, (ret, kinds) in protos.items():
+        restype, argtypes = _lib.signature(name)
+        assert restype is _lib._KIND[ret], name
+        assert len(argtypes) == len(kinds), name
+        assert argtypes == [_lib._KIND[k] for k in kinds], name
+    assert (_lib._KIND["p"], _lib._KIND["i"], _lib._KIND["l"]) == (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64)
+    assert (_lib._KIND["z"], _lib._KIND["f"], _lib._KIND["u"]) == (ctypes.c_size_t, ctypes.c_float, ctypes.c_uint32)
+
+
+def test_prototype_table_is_applied_on_load():
+    from vidar_amd._lib import lib
+    L = lib()
+    protos = header_prototypes()
+    for name, (ret, kinds) in protos.items():
+        fn = getattr(L, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(kinds), name
+        assert (fn.restype is ctypes.c_size_t) == (ret == "z"), name
+        assert fn.restype is (ctypes.c_size_t if ret == "z" else ctypes.c_int), name
+    assert sum(ret == "z" for ret, _ in protos.values()) == 12
+
+
+def test_declare_names_a_symbol_the_library_lacks():
+    from vidar_amd._lib import VidarHipError, declare
+    with pytest.raises(VidarHipError, match="vidar_abi_version"):
+        declare(ctypes.CDLL(None))          # the process itself: exports none of the entries
+
+
+def test_64_bit_values_cross_the_boundary():
+    """host-only arithmetic, linear in `rows`: an int64_t argument cut to 32 bits would arrive as 0 and give 0 bytes,
+    a size_t result read as int would wrap"""
+    from vidar_amd._lib import lib
+    f = lib().vidar_drop_add_ln_bwd_workspace_bytes
+    a, b = f(1 << 39), f(1 << 40)
+    assert a > 1 << 32 and b > 1 << 32
+    assert b > a
+
+
+def test_wrong_argument_types_fail_in_python():
+    """1.5 for the `int N` of vidar_dvr_init_f32 never reaches C.  The correctly typed null call that returns 0 with no
+    GPU is made on vidar_dvr_render_forward_f32: it answers M == 0 before any HIP call, while dvr_init clears its output
+    first (hipMemsetAsync: hipErrorNoDevice on a machine without a GPU)."""
+    from vidar_amd._lib import lib
+    L = lib()
+    with pytest.raises(ctypes.ArgumentError):
+        L.vidar_dvr_init_f32(None, None, None, 1.5, 0, 1, 1, 1, 1, None)
+    assert L.vidar_dvr_render_forward_f32(None, None, None, None, None, None, 1, 0, 1, 1, 1, 1, 1, 0, None) == 0
+    with pytest.raises(ctypes.ArgumentError):
+        L.vidar_dvr_render_forward_f32(None, None, None, None, None, None, 1.5, 0, 1, 1, 1, 1, 1, 0, None)
+
+
 def test_no_cpu_fallback():
     """CPU tensors are rejected (CHECK_CUDA semantics), nothing silently runs on the host."""
     from vidar_amd.third_lib import dvxlr

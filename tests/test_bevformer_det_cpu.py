@@ -398,12 +398,12 @@ DET_ENTRY_POINTS = ("vidar_det_match_cost_f32", "vidar_det_loss_workspace_bytes"
 
 def test_abi_declares_and_exports_the_detection_loss_entry_points():
     from vidar_amd import build
+    from vidar_amd._lib import declare
     header = (ROOT / "include" / "vidar_hip.h").read_text()
-    lib = ctypes.CDLL(str(build.build(verbose=False)))
+    lib = declare(ctypes.CDLL(str(build.build(verbose=False))))
     for name in DET_ENTRY_POINTS:
         assert name + "(" in header and hasattr(lib, name), name
     f = lib.vidar_det_loss_workspace_bytes
-    f.restype = ctypes.c_size_t
     assert f(6, 1, 900) == 6 * 15 * 2 * 8 and f(6, 2, 900) == 6 * 29 * 2 * 8 and f(0, 1, 900) == 0    # fp64 partials
 
 

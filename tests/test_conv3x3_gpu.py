@@ -2,8 +2,6 @@
 fp32 matrix cores) against an fp64 convolution of the same inputs on the CPU: the floating-point reference of a
 floating-point kernel, tolerance 1e-5 of the output scale (fp32 products are exact in the matrix core; only the order of the
 C * 9 additions differs).  Through the C-ABI, and through the autograd Function the backbone uses."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -55,15 +53,14 @@ def test_empty_batch_and_limits():
     out = torch.empty(1, 27, 4, 4, device="cuda")
     ws = torch.empty(8 * 9 * 32 * 4, dtype=torch.uint8, device="cuda")
     f = lib().vidar_conv3x3_few_f32
-    n = ctypes.c_size_t(ws.numel())
+    n = ws.numel()
     assert f(ptr(x), ptr(w), None, ptr(out), 0, 8, 4, 4, 27, ptr(ws), n, stream_of(x)) == 0           # nothing to do
     assert f(ptr(x), ptr(w), None, ptr(out), 1, 8, 4, 4, 33, ptr(ws), n, stream_of(x)) == -22         # > 32 outputs
     assert f(ptr(x), ptr(w), None, ptr(out), 1, 12, 4, 4, 27, ptr(ws), n, stream_of(x)) == -22        # C % 8
     assert f(ptr(x), ptr(w), None, ptr(out), 1, 8, 4, 192, 27, ptr(ws), n, stream_of(x)) == -22       # row too wide
-    assert f(ptr(x), ptr(w), None, ptr(out), 1, 8, 4, 4, 27, ptr(ws), ctypes.c_size_t(16), stream_of(x)) == -22
+    assert f(ptr(x), ptr(w), None, ptr(out), 1, 8, 4, 4, 27, ptr(ws), 16, stream_of(x)) == -22
     assert f(ptr(x), ptr(w), None, ptr(out), 1, 8, 4, 4, 27, None, n, stream_of(x)) == -22
     g = lib().vidar_conv3x3_few_workspace_bytes
-    g.restype = ctypes.c_size_t
     assert g(256) == 256 * 9 * 32 * 4 and g(0) == 0
 
 

@@ -217,8 +217,9 @@ def test_init_weights_reads_a_prefixed_checkpoint(tmp_path):
 
 def test_abi_declares_and_exports_the_dcnv3_entry_points():
     from vidar_amd import build
+    from vidar_amd._lib import declare
     header = (ROOT / "include" / "vidar_hip.h").read_text()
-    lib = ctypes.CDLL(str(build.build(verbose=False)))
+    lib = declare(ctypes.CDLL(str(build.build(verbose=False))))
     for name in ("vidar_dcnv3_forward_f32", "vidar_dcnv3_backward_f32", "vidar_dcnv3_backward_workspace_bytes"):
         assert name + "(" in header and hasattr(lib, name), name
 

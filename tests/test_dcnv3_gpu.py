@@ -348,7 +348,6 @@ def test_window_too_large_for_lds_takes_the_plain_form(variant, ref_modules):
 
 def test_unaligned_buffers_take_the_scalar_form():
     """gc % 4 == 0 but input / grad_output / output views start one element into their storage (4-byte aligned only)"""
-    import ctypes
     from vidar_amd._lib import lib, ptr
     from vidar_amd.third_lib import dcnv3
     geo = (3, 3, 1, 1, 1, 1, 1, 1, 2, 16, 1.0)
@@ -360,8 +359,8 @@ def test_unaligned_buffers_take_the_scalar_form():
     assert torch.equal(dcnv3.dcnv3_forward(xs, off, mask, *geo, 256), want)
     # an unaligned OUTPUT buffer through the C entry point
     buf = torch.empty(want.numel() + 1, device="cuda")
-    rc = lib().vidar_dcnv3_forward_f32(ptr(x), ptr(off), ptr(mask), ctypes.c_void_p(buf.data_ptr() + 4), 2, 9, 11, 3, 3, 1, 1, 1, 1, 1, 1,
-                                       2, 16, ctypes.c_float(1.0), None)
+    rc = lib().vidar_dcnv3_forward_f32(ptr(x), ptr(off), ptr(mask), buf.data_ptr() + 4, 2, 9, 11, 3, 3, 1, 1, 1, 1, 1, 1,
+                                       2, 16, 1.0, None)
     torch.cuda.synchronize()
     assert rc == 0 and torch.equal(buf[1:].view(want.shape), want)
     a = dcnv3.dcnv3_backward(x, off, mask, *geo, gout, 256)
@@ -372,18 +371,17 @@ def test_unaligned_buffers_take_the_scalar_form():
 
 
 def test_bad_arguments_are_answered_without_a_launch():
-    import ctypes
     from vidar_amd._lib import BAD_ARG, lib, ptr
     L = lib()
     t = torch.zeros(64, device="cuda")
-    f = ctypes.c_float(1.0)
+    f = 1.0
 
     def fwd(N, H, W, kh, kw, sh, sw, ph, pw, dh, dw, G, gc):
         return L.vidar_dcnv3_forward_f32(ptr(t), ptr(t), ptr(t), ptr(t), N, H, W, kh, kw, sh, sw, ph, pw, dh, dw, G, gc, f, None)
 
     def bwd(N, H, W, kh, kw, sh, sw, ph, pw, dh, dw, G, gc):
         return L.vidar_dcnv3_backward_f32(ptr(t), ptr(t), ptr(t), ptr(t), ptr(t), ptr(t), ptr(t), N, H, W, kh, kw, sh, sw, ph, pw,
-                                          dh, dw, G, gc, f, None, ctypes.c_size_t(0), None)
+                                          dh, dw, G, gc, f, None, 0, None)
     bad = [(1, 40, 40, 25, 41, 1, 1, 20, 20, 1, 1, 1, 4),            # kh*kw = 1025 points
            (1, 4, 4, 7, 7, 1, 1, 1, 1, 1, 1, 1, 4),                  # kernel extent beyond the padded input
            (1, 4, 4, 3, 3, 1, 1, 0, 0, 2, 2, 1, 4),                  # dilated extent 5 > 4

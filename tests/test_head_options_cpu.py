@@ -59,16 +59,17 @@ def test_named_configs_still_build_with_their_512(name):
 
 def test_abi_exports_the_distance_pair():
     from vidar_amd import build
-    lib = ctypes.CDLL(str(build.build(verbose=False)))
+    from vidar_amd._lib import declare
+    lib = declare(ctypes.CDLL(str(build.build(verbose=False))))
     for n in ("vidar_ray_dist_fwd_f32", "vidar_ray_dist_bwd_f32", "vidar_ray_max_k", "vidar_ray_force_streamed"):
         assert hasattr(lib, n), n
     assert lib.vidar_ray_max_k() >= 2050
     # out-of-range K is still a bad argument (checked before anything touches a device)
     null = ctypes.c_void_p(0)
     for K in (0, -1, lib.vidar_ray_max_k() + 1):
-        rc = lib.vidar_ray_argmax_f32(null, null, null, null, null, null, 1, 0, 16, 200, 200, K, ctypes.c_float(1.0), null)
+        rc = lib.vidar_ray_argmax_f32(null, null, null, null, null, null, 1, 0, 16, 200, 200, K, 1.0, null)
         assert rc == -22, (K, rc)
-    assert lib.vidar_ray_argmax_f32(null, null, null, null, null, null, 1, 0, 16, 200, 200, 1026, ctypes.c_float(1.0), null) == 0
+    assert lib.vidar_ray_argmax_f32(null, null, null, null, null, null, 1, 0, 16, 200, 200, 1026, 1.0, null) == 0
 
 
 def test_new_ray_kernels_meet_the_resource_limits():

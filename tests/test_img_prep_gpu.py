@@ -26,7 +26,8 @@ def _dev(a):
 
 
 def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+    from vidar_amd._lib import ptr
+    return ptr(t)
 
 
 def _table(n_in, n_out):

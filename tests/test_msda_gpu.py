@@ -186,10 +186,8 @@ def test_full_size_matches_oracle(name, scatter):
 
 def test_binned_workspace_contract():
     """workspace too small -> invalid argument; unsupported level count -> 0 bytes (caller falls back)."""
-    import ctypes
     from vidar_amd._lib import lib, ptr, stream_of
     f = lib().vidar_msda_bwd_workspace_bytes
-    f.restype = ctypes.c_size_t
     assert f(2, 400, 8, 400, 1, 4) > 0
     assert f(1, 400, 8, 400, 17, 1) == 0
     value, sh, loc, w = M.make_case(0, 2, [(20, 20)], 400, P=4)
@@ -198,7 +196,7 @@ def test_binned_workspace_contract():
     gv, gl, gw = torch.empty_like(a[0]), torch.empty_like(a[3]), torch.empty_like(a[4])
     ws = torch.empty(8, dtype=torch.int64, device="cuda")
     rc = lib().vidar_msda_bwd_f32(ptr(a[0]), ptr(a[1]), ptr(a[2]), ptr(a[3]), ptr(a[4]), ptr(go), ptr(gv), ptr(gl),
-                                  ptr(gw), 2, 400, 8, 32, 400, 1, 4, ptr(ws), ctypes.c_size_t(64), stream_of(go))
+                                  ptr(gw), 2, 400, 8, 32, 400, 1, 4, ptr(ws), 64, stream_of(go))
     assert rc == -22
 
 

@@ -70,15 +70,14 @@ def test_other_widths_take_the_torch_path():
                                        (100003, 128)])
 def test_colsum_matches_fp64_column_sums(rows, cols):
     """vidar_colsum_f32: the bias gradient of the Linear layers (sum over rows), against an fp64 sum"""
-    import ctypes
     from vidar_amd._lib import lib, check, ptr, stream_of
     g = torch.Generator().manual_seed(rows + cols)
     x = torch.randn(rows, cols, generator=g).cuda()
     out = torch.full((cols,), float("nan"), device="cuda")
-    check(lib().vidar_colsum_f32(ptr(x), ptr(out), ctypes.c_int64(rows), cols, stream_of(x)), "colsum")
+    check(lib().vidar_colsum_f32(ptr(x), ptr(out), rows, cols, stream_of(x)), "colsum")
     ref = x.double().sum(0)
     torch.testing.assert_close(out.double(), ref, rtol=1e-5, atol=2e-4 * max(1.0, rows ** 0.5))
-    assert lib().vidar_colsum_f32(ptr(x), ptr(out), ctypes.c_int64(rows), 12, stream_of(x)) != 0    # 3 groups: not a power of two
+    assert lib().vidar_colsum_f32(ptr(x), ptr(out), rows, 12, stream_of(x)) != 0    # 3 groups: not a power of two
 
 
 def test_bricks_linear_gradients_equal_nn_linear():

@@ -19,6 +19,7 @@ import torch
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 from tools.kbench import timeit  # noqa: E402
+from vidar_amd._lib import ptr, signature, stream_of  # noqa: E402
 
 VARIANTS = (0, 1, 2, 4, 8, 16, 6, 14)
 NAMES = {0: "full kernel", 1: "no border masks", 2: "no LDS operand reads", 4: "no fetch / staging", 8: "no barrier",
@@ -39,11 +40,10 @@ def main():
             so = ROOT / "tools" / "_abl" / f"conv_abl_{k}.so"
             if not so.exists():
                 continue
-            L = ctypes.CDLL(str(so))
-            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            p = lambda t: ctypes.c_void_p(t.data_ptr())
+            conv = ctypes.CDLL(str(so)).vidar_conv3x3_few_f32        # a variant library exports this one entry only
+            conv.restype, conv.argtypes = signature("vidar_conv3x3_few_f32")
             for chunk in (8,):
-                fn = lambda: L.vidar_conv3x3_few_f32(p(x), p(w), p(b), p(out), N, C, H, W, 27, p(ws), ctypes.c_size_t(ws.numel()), st)
+                fn = lambda: conv(ptr(x), ptr(w), ptr(b), ptr(out), N, C, H, W, 27, ptr(ws), ws.numel(), stream_of(x))
                 assert fn() == 0
                 ref = torch.nn.functional.conv2d(x, w, b, padding=1)
                 err = float((out - ref).abs().max() / ref.abs().max())

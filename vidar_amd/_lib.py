@@ -1,5 +1,10 @@
 """ctypes loader for libvidar_hip.so.  There is NO fallback: if the library is missing or a call
-fails the product raises, it never routes to a CPU/eager path."""
+fails the product raises, it never routes to a CPU/eager path.
+
+The C ABI is stated once, in `_ABI` below: `declare` turns it into the `argtypes` / `restype` of every entry point, so
+call sites pass plain Python ints and floats, tensors' pointers through `ptr`, and a value of the wrong type raises
+`ctypes.ArgumentError` instead of being truncated.  A new C entry is declared in include/vidar_hip.h AND in `_ABI`;
+tests/test_abi_cpu.py fails until the two agree."""
 from __future__ import annotations
 
 import ctypes
@@ -26,31 +31,116 @@ def lib() -> ctypes.CDLL:
             raise VidarHipError(
                 f"{LIB_PATH} not found: build it with `python -m vidar_amd.build` "
                 f"(or __graft_entry__.build()); vidar_amd has no CPU fallback")
-        _lib = ctypes.CDLL(str(LIB_PATH))
+        _lib = declare(ctypes.CDLL(str(LIB_PATH)))
         dcn = os.environ.get("VIDAR_DCN_VARIANT")                # A/B of the DCNv2 col2im gather (LDS window / global loads)
         if dcn is not None:
             _lib.vidar_dcn_set_variant(int(dcn))
         v3 = os.environ.get("VIDAR_DCNV3_VARIANT")              # A/B of the DCNv3 backward's grad_input accumulation (tools)
         if v3 is not None:
             _lib.vidar_dcnv3_set_variant(int(v3))
-        _declare_img(_lib)
         order = os.environ.get("VIDAR_MSDA_ITEM_ORDER")          # A/B of the MSDA gather kernels' item order (tools, bench)
         if order is not None:
             _lib.vidar_msda_set_item_order(int(order))
     return _lib
 
 
-def _declare_img(L):
-    """argument types of the image pipeline (csrc/img_prep.hip): many ints next to pointers and a size_t, so spelled out"""
-    vp, i, f3 = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float)
-    L.vidar_img_photometric_u8.argtypes = [vp, vp, vp, i, i, i, vp]
-    L.vidar_img_photometric_f32.argtypes = [vp, vp, vp, i, i, i, vp]
-    L.vidar_img_resample_workspace_bytes.argtypes = [i, i, i]
-    L.vidar_img_resample_workspace_bytes.restype = ctypes.c_size_t
-    L.vidar_img_resample_u8.argtypes = [vp, vp] + [i] * 9 + [vp, i, vp, i, i, vp, ctypes.c_size_t, vp]
-    L.vidar_img_normalise_f32.argtypes = [vp, vp, vp] + [i] * 7 + [f3, f3, i, vp]
-    for fn in (L.vidar_img_photometric_u8, L.vidar_img_photometric_f32, L.vidar_img_resample_u8, L.vidar_img_normalise_f32):
-        fn.restype = ctypes.c_int
+# Every prototype of include/vidar_hip.h: "<return kind> <parameter kinds in order>", a count in front of a kind repeating it.
+#   p = pointer (any pointee, device or host; None = NULL)   i = int   l = int64_t   z = size_t   f = float   u = uint32_t
+_KIND = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_int64, "z": ctypes.c_size_t, "f": ctypes.c_float,
+         "u": ctypes.c_uint32}
+_ABI = {
+    "vidar_abi_version": "i",
+    "vidar_marker": "i i p",
+    "vidar_dvr_max_d": "i",
+    "vidar_dvr_render_forward_f32": "i 6p 8i p",
+    "vidar_dvr_render_f32": "i 7p 8i p",
+    "vidar_dvr_init_f32": "i 3p 6i p",
+    "vidar_dvxlr_max_d": "i",
+    "vidar_dvr_set_sort_min_waves": "i i",
+    "vidar_dvr_set_traversal": "i i",
+    "vidar_dvxlr_set_pad_mode": "i i",
+    "vidar_dvxlr_render_f32": "i 8p 7i p",
+    "vidar_dvxlr_get_grad_sigma_workspace_bytes": "z 6i",
+    "vidar_dvxlr_get_grad_sigma_f32": "i 4p 7i p z p",
+    "vidar_dvxlr2_render_f32": "i 11p 7i p",
+    "vidar_dvxlr2_get_grad_sigma_f32": "i 7p 7i p z p",
+    "vidar_knn1_d3_workspace_bytes": "z 2i",
+    "vidar_knn1_d3_fwd": "i 7p 3i p",
+    "vidar_knn1_d3_bwd": "i 8p 3i p",
+    "vidar_msda_fwd_f32": "i 6p 7i p",
+    "vidar_msda_bwd_workspace_bytes": "z 6i",
+    "vidar_msda_set_item_order": "i i",
+    "vidar_msda_bwd_f32": "i 9p 7i p z p",
+    "vidar_msda_fused_fwd_f32": "i 9p 11i p",
+    "vidar_msda_fused_bwd_f32": "i 9p 9i p z p",
+    "vidar_drop_add_ln_fwd_f32": "i 8p l i 2f u p",
+    "vidar_drop_add_ln_bwd_f32": "i 10p l i f u p",
+    "vidar_drop_add_ln_bwd_workspace_bytes": "z l",
+    "vidar_relu_drop_fwd_f32": "i 2p l f u p",
+    "vidar_relu_drop_bwd_f32": "i 3p l f p",
+    "vidar_colsum_f32": "i 2p l i p",
+    "vidar_sca_plan_f32": "i 10p 2f 5i p",
+    "vidar_sca_rows_f32": "i 5p 6i p",
+    "vidar_sca_combine_f32": "i 4p 5i p",
+    "vidar_latent_render_bwd_workspace_bytes": "z 5i",
+    "vidar_latent_render_prob_fwd_f32": "i 2p 5i f i p",
+    "vidar_latent_render_prob_bwd_f32": "i 3p 5i f i p z p",
+    "vidar_latent_render_gather_fwd_f32": "i 4p 5i 2f p",
+    "vidar_latent_render_gather_bwd_f32": "i 7p 5i 2f p z p",
+    "vidar_ray_bwd_workspace_bytes": "z 4i",
+    "vidar_ray_ce_fwd_f32": "i 7p 6i f p",
+    "vidar_ray_ce_bwd_f32": "i 7p 6i f p z p",
+    "vidar_ray_gumbel_fwd_f32": "i 7p 6i f p",
+    "vidar_ray_gumbel_bwd_f32": "i 7p 6i f p z p",
+    "vidar_ray_argmax_f32": "i 6p 6i f p",
+    "vidar_ray_dist_fwd_f32": "i 9p 6i f p",
+    "vidar_ray_dist_bwd_f32": "i 7p 6i f p z p",
+    "vidar_ray_max_k": "i",
+    "vidar_ray_force_streamed": "i i",
+    "vidar_gemm_f32": "i p l i p l i p l 4i 3l 2p i p 2l 3i 2p z p",
+    "vidar_gemm_splits": "i 6i",
+    "vidar_gemm_workspace_bytes": "z 6i",
+    "vidar_gemm_set_variant": "i i",
+    "vidar_dcn_set_variant": "i i",
+    "vidar_dcn_im2col_f32": "i 4p 11i p",
+    "vidar_dcn_col2im_f32": "i 7p 11i p z p",
+    "vidar_dcn_col2im_workspace_bytes": "z 7i",
+    "vidar_conv3x3_few_workspace_bytes": "z i",
+    "vidar_conv3x3_few_f32": "i 4p 5i p z p",
+    "vidar_affine_act_fwd_f32": "i 5p 4i p",
+    "vidar_stem_bn_relu_pool_f32": "i 4p 4i p",
+    "vidar_affine_act_bwd_f32": "i 5p 4i p",
+    "vidar_dcnv3_set_variant": "i i",
+    "vidar_dcnv3_forward_f32": "i 4p 13i f p",
+    "vidar_dcnv3_backward_workspace_bytes": "z 13i",
+    "vidar_dcnv3_backward_f32": "i 7p 13i f p z p",
+    "vidar_det_match_cost_f32": "i 6p 4f 5i p",
+    "vidar_det_loss_workspace_bytes": "z 3i",
+    "vidar_det_loss_fwd_f32": "i 8p 2f 5i p z p",
+    "vidar_det_loss_bwd_f32": "i 10p 2f 5i p",
+    "vidar_img_photometric_u8": "i 3p 3i p",
+    "vidar_img_photometric_f32": "i 3p 3i p",
+    "vidar_img_resample_workspace_bytes": "z 3i",
+    "vidar_img_resample_u8": "i 2p 9i p i p 2i p z p",
+    "vidar_img_normalise_f32": "i 3p 7i 2p i p",
+}
+
+
+def signature(name):
+    """(restype, argtypes) of the entry `name` as `_ABI` states them"""
+    ret, *runs = _ABI[name].split()
+    return _KIND[ret], [_KIND[r[-1]] for r in runs for _ in range(int(r[:-1] or 1))]
+
+
+def declare(cdll):
+    """Set `argtypes` and `restype` of every entry of `_ABI` on `cdll` (an open libvidar_hip.so); returns `cdll`."""
+    for name in _ABI:
+        try:
+            fn = getattr(cdll, name)
+        except AttributeError:
+            raise VidarHipError(f"{name} is not exported by {cdll._name}: rebuild the library") from None
+        fn.restype, fn.argtypes = signature(name)
+    return cdll
 
 
 def check(rc: int, what: str):
@@ -62,26 +152,27 @@ def check(rc: int, what: str):
 
 
 def ptr(t):
-    """Device pointer of a torch tensor (None -> NULL)."""
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+    """Device pointer of a torch tensor (None -> NULL) as a plain address: the declared pointer parameters take it as it
+    is, and no c_void_p object is built per argument (a step makes thousands of these calls).  Only for entries that
+    `declare` has typed -- an undeclared ctypes function would cut a bare int to 32 bits."""
+    return None if t is None else t.data_ptr()
 
 
 def workspace(nbytes_fn, *dims, like):
     """Caller-owned device scratch for an op: `nbytes_fn(*dims)` bytes from torch's caching allocator on `like`'s
     device (so it lives on the op's device and stream and is counted by torch's memory statistics).
-    -> (tensor or None, pointer, size_t): keep the tensor alive until the call has been enqueued."""
+    -> (tensor or None, pointer, byte count): keep the tensor alive until the call has been enqueued."""
     import torch
-    nbytes_fn.restype = ctypes.c_size_t
-    n = int(nbytes_fn(*dims))
+    n = nbytes_fn(*dims)
     if n == 0:
-        return None, None, ctypes.c_size_t(0)
+        return None, None, 0
     ws = torch.empty(n, dtype=torch.uint8, device=like.device)
-    return ws, ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(n)
+    return ws, ptr(ws), n
 
 
 def stream_of(t):
     import torch
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 # --------------------------------------------------------------------------------------------------

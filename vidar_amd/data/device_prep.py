@@ -183,7 +183,7 @@ class DeviceImagePrep:
                 ty, ky = self._table(ch, oh, dev) if need_y else (None, 0)
                 out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
                 ws, ws_ptr, ws_n = workspace(L.vidar_img_resample_workspace_bytes, n, ch, ow, like=raw_u8) \
-                    if need_x and need_y else (None, None, ctypes.c_size_t(0))
+                    if need_x and need_y else (None, None, 0)
                 check(L.vidar_img_resample_u8(ptr(src), ptr(out), n, H, W, x0, y0, cw, ch, ow, oh, ptr(tx), kx, ptr(ty), ky,
                                               int(flip), ws_ptr, ws_n, st), "img_resample")
                 src, h, w = out, oh, ow

@@ -16,12 +16,11 @@ bf16x3 step as a second, labelled record).  There is no CPU path: the functions 
 from __future__ import annotations
 
 import contextlib
-import ctypes
 import os
 
 import torch
 
-from ._lib import lib, check, ptr, stream_of, TIMER
+from ._lib import lib, check, ptr, stream_of, workspace, TIMER
 
 F32, BF16X3 = 0, 1
 K_MAJOR, MN_MAJOR = 0, 1
@@ -110,20 +109,13 @@ def gemm_raw(A, lda, a_layout, B, ldb, b_layout, C, ldc, M, N, K, *, batch=1, sA
              vec_axis=0, residual=None, ldr=0, sR=0, relu=False, precision=F32, reduce=False, a_rowsum=None, name="gemm"):
     """one call of vidar_gemm_f32 on torch tensors (pointers are taken as they are: the caller states the geometry)"""
     L = lib()
-    ws, nbytes = None, 0
-    if reduce:
-        f = L.vidar_gemm_workspace_bytes
-        f.restype = ctypes.c_size_t
-        nbytes = int(f(int(M), int(N), int(K), int(batch), int(precision), 2 if a_rowsum is not None else 1))
-        if nbytes:
-            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=C.device)
+    ws, ws_ptr, nbytes = workspace(L.vidar_gemm_workspace_bytes, M, N, K, batch, precision, 2 if a_rowsum is not None else 1,
+                                   like=C) if reduce else (None, None, 0)
     flops = 2.0 * M * N * K * batch
     with TIMER.span(name, flops):
-        check(L.vidar_gemm_f32(ptr(A), ctypes.c_int64(lda), int(a_layout), ptr(B), ctypes.c_int64(ldb), int(b_layout),
-                               ptr(C), ctypes.c_int64(ldc), int(M), int(N), int(K), int(batch), ctypes.c_int64(sA),
-                               ctypes.c_int64(sB), ctypes.c_int64(sC), ptr(scale), ptr(shift), int(vec_axis),
-                               ptr(residual), ctypes.c_int64(ldr), ctypes.c_int64(sR), int(bool(relu)), int(precision),
-                               int(bool(reduce)), ptr(a_rowsum), ptr(ws), ctypes.c_size_t(nbytes), stream_of(C)),
+        check(L.vidar_gemm_f32(ptr(A), lda, a_layout, ptr(B), ldb, b_layout, ptr(C), ldc, M, N, K, batch, sA, sB, sC,
+                               ptr(scale), ptr(shift), vec_axis, ptr(residual), ldr, sR, bool(relu), precision,
+                               bool(reduce), ptr(a_rowsum), ws_ptr, nbytes, stream_of(C)),
               "vidar_gemm_f32")
     return C
 
@@ -179,7 +171,7 @@ def _colsum(g2):
     n = g2.shape[1]
     if n % 4 == 0 and (n // 4) & (n // 4 - 1) == 0 and n <= 4096 and g2.data_ptr() % 16 == 0 and g2.is_contiguous():
         gb = torch.empty(n, dtype=torch.float32, device=g2.device)
-        check(lib().vidar_colsum_f32(ptr(g2), ptr(gb), ctypes.c_int64(g2.shape[0]), int(n), stream_of(g2)), "colsum")
+        check(lib().vidar_colsum_f32(ptr(g2), ptr(gb), g2.shape[0], n, stream_of(g2)), "colsum")
         return gb
     return g2.sum(0)
 

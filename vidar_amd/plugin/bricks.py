@@ -64,7 +64,6 @@ class _LinearColsum(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        import ctypes
         from .._lib import lib, check, ptr, stream_of
         x2, w = ctx.saved_tensors
         g2 = g if g.is_contiguous() else g.contiguous()
@@ -85,8 +84,7 @@ class _LinearColsum(torch.autograd.Function):
                 return gx, gw, gb
             gw = (x2.t() @ g2).t()
         gb = torch.empty(g2.shape[1], dtype=torch.float32, device=g2.device)
-        check(lib().vidar_colsum_f32(ptr(g2), ptr(gb), ctypes.c_int64(g2.shape[0]), int(g2.shape[1]), stream_of(g2)),
-              "colsum")
+        check(lib().vidar_colsum_f32(ptr(g2), ptr(gb), g2.shape[0], g2.shape[1], stream_of(g2)), "colsum")
         return gx, gw, gb
 
 
@@ -123,25 +121,21 @@ class _ReluDropout(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, p, seed):
-        import ctypes
         from .._lib import lib, check, ptr, stream_of
         x = x.contiguous()
         y = torch.empty_like(x)
-        check(lib().vidar_relu_drop_fwd_f32(ptr(x), ptr(y), ctypes.c_int64(x.numel()), ctypes.c_float(p),
-                                            ctypes.c_uint32(seed), stream_of(x)), "relu_drop_fwd")
+        check(lib().vidar_relu_drop_fwd_f32(ptr(x), ptr(y), x.numel(), p, seed, stream_of(x)), "relu_drop_fwd")
         ctx.save_for_backward(y)
         ctx.p = p
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        import ctypes
         from .._lib import lib, check, ptr, stream_of
         y, = ctx.saved_tensors
         gy = gy.contiguous()
         gx = torch.empty_like(gy)
-        check(lib().vidar_relu_drop_bwd_f32(ptr(gy), ptr(y), ptr(gx), ctypes.c_int64(gy.numel()), ctypes.c_float(ctx.p),
-                                            stream_of(gy)), "relu_drop_bwd")
+        check(lib().vidar_relu_drop_bwd_f32(ptr(gy), ptr(y), ptr(gx), gy.numel(), ctx.p, stream_of(gy)), "relu_drop_bwd")
         return gx, None, None
 
 
@@ -264,34 +258,29 @@ def can_fuse_norm(norm, x):
 class _DropAddLayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, gamma, beta, p, eps, seed):
-        import ctypes
         from .._lib import lib, check, ptr, stream_of
         x, residual = x.contiguous(), residual.contiguous()
         rows = x.numel() // 256
         y = torch.empty_like(x); s = torch.empty_like(x)
         mean = torch.empty(rows, device=x.device); rstd = torch.empty(rows, device=x.device)
         check(lib().vidar_drop_add_ln_fwd_f32(ptr(x), ptr(residual), ptr(gamma), ptr(beta), ptr(y), ptr(s), ptr(mean),
-                                              ptr(rstd), ctypes.c_int64(rows), 256, ctypes.c_float(p),
-                                              ctypes.c_float(eps), ctypes.c_uint32(seed), stream_of(x)), "drop_add_ln_fwd")
+                                              ptr(rstd), rows, 256, p, eps, seed, stream_of(x)), "drop_add_ln_fwd")
         ctx.save_for_backward(s, gamma, mean, rstd)
         ctx.cfg = (p, seed, rows)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        import ctypes
-        from .._lib import lib, check, ptr, stream_of
+        from .._lib import lib, check, ptr, stream_of, workspace
         s, gamma, mean, rstd = ctx.saved_tensors
         p, seed, rows = ctx.cfg
         gy = gy.contiguous()
         gx = torch.empty_like(s); gres = torch.empty_like(s)
         dgamma = torch.empty_like(gamma); dbeta = torch.empty_like(gamma)
-        f = lib().vidar_drop_add_ln_bwd_workspace_bytes
-        f.restype = ctypes.c_size_t
-        ws = torch.empty((int(f(ctypes.c_int64(rows))) + 3) // 4, device=s.device)
+        ws, ws_ptr, _ = workspace(lib().vidar_drop_add_ln_bwd_workspace_bytes, rows, like=s)
         check(lib().vidar_drop_add_ln_bwd_f32(ptr(gy), ptr(s), ptr(gamma), ptr(mean), ptr(rstd), ptr(gx), ptr(gres),
-                                              ptr(dgamma), ptr(dbeta), ptr(ws), ctypes.c_int64(rows), 256, ctypes.c_float(p),
-                                              ctypes.c_uint32(seed), stream_of(s)), "drop_add_ln_bwd")
+                                              ptr(dgamma), ptr(dbeta), ws_ptr, rows, 256, p, seed, stream_of(s)),
+              "drop_add_ln_bwd")
         return gx, gres, dgamma, dbeta, None, None, None
 
 

@@ -11,7 +11,6 @@ gt_counts = (G_0 .. G_{B-1}) known on the host; cost layout as in include/vidar_
 a [Q, G_b] row-major block at offset Q * start_b)."""
 from __future__ import annotations
 
-import ctypes
 import os
 
 import numpy as np
@@ -64,8 +63,7 @@ def match_cost(cls, box, gt_box_norm, gt_label, gt_start_dev, total_g, alpha, ga
     assert box.shape == (NL, B, Q, CODE) and gt_label.dtype == torch.int32 and gt_start_dev.dtype == torch.int32
     cost = torch.empty((NL, Q * total_g), device=cls.device, dtype=torch.float32)
     check(lib().vidar_det_match_cost_f32(ptr(cls), ptr(box), ptr(gt_box_norm), ptr(gt_label), ptr(gt_start_dev), ptr(cost),
-                                         ctypes.c_float(alpha), ctypes.c_float(gamma), ctypes.c_float(cls_weight),
-                                         ctypes.c_float(reg_weight), NL, B, Q, C, int(total_g), stream_of(cls)),
+                                         alpha, gamma, cls_weight, reg_weight, NL, B, Q, C, int(total_g), stream_of(cls)),
           "det_match_cost")
     return cost
 
@@ -163,11 +161,11 @@ class DetLossFunction(torch.autograd.Function):
         gt_box_norm, code_weights = gt_box_norm.float().contiguous(), code_weights.float().contiguous()
         assert box.shape == (NL, B, Q, CODE) and labels.dtype == torch.int32 and matched.dtype == torch.int32
         assert gt_start_dev.dtype == torch.int32 and code_weights.numel() == CODE
-        total_g = int(gt_box_norm.shape[0])
+        total_g = gt_box_norm.shape[0]
         sums = torch.empty((NL, 2), device=cls.device, dtype=torch.float32)
         ws, ws_ptr, ws_n = workspace(lib().vidar_det_loss_workspace_bytes, NL, B, Q, like=cls)
         check(lib().vidar_det_loss_fwd_f32(ptr(cls), ptr(box), ptr(labels), ptr(matched), ptr(gt_box_norm), ptr(gt_start_dev),
-                                           ptr(code_weights), ptr(sums), ctypes.c_float(alpha), ctypes.c_float(gamma), NL, B,
+                                           ptr(code_weights), ptr(sums), alpha, gamma, NL, B,
                                            Q, C, total_g, ws_ptr, ws_n, stream_of(cls)), "det_loss_fwd")
         ctx.save_for_backward(cls, box, labels, matched, gt_box_norm, gt_start_dev, code_weights)
         ctx.cfg = (float(alpha), float(gamma))
@@ -183,8 +181,8 @@ class DetLossFunction(torch.autograd.Function):
         g = g.float().contiguous()
         d_cls, d_box = torch.empty_like(cls), torch.empty_like(box)
         check(lib().vidar_det_loss_bwd_f32(ptr(cls), ptr(box), ptr(labels), ptr(matched), ptr(gt_box_norm), ptr(gt_start_dev),
-                                           ptr(code_weights), ptr(g), ptr(d_cls), ptr(d_box), ctypes.c_float(alpha),
-                                           ctypes.c_float(gamma), NL, B, Q, C, int(gt_box_norm.shape[0]), stream_of(cls)),
+                                           ptr(code_weights), ptr(g), ptr(d_cls), ptr(d_box), alpha, gamma,
+                                           NL, B, Q, C, gt_box_norm.shape[0], stream_of(cls)),
               "det_loss_bwd")
         return d_cls, d_box, None, None, None, None, None, None, None
 

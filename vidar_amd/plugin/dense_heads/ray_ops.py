@@ -6,7 +6,6 @@ kernels, every other value the streamed ones."""
 from __future__ import annotations
 
 import contextlib
-import ctypes
 
 import torch
 from torch.autograd import Function
@@ -18,13 +17,13 @@ K_SAMPLES = 512
 
 
 def max_k():
-    return int(lib().vidar_ray_max_k())
+    return lib().vidar_ray_max_k()
 
 
 @contextlib.contextmanager
 def force_streamed(on=True):
     """Test / benchmark hook: K == 512 runs the streamed kernels too inside the block (same bits)."""
-    was = lib().vidar_ray_force_streamed(int(bool(on)))
+    was = lib().vidar_ray_force_streamed(bool(on))
     try:
         yield
     finally:
@@ -48,8 +47,7 @@ class _RayCE(Function):
         ce = torch.empty(R, device=sigma.device); lse = torch.empty_like(ce); valid = torch.empty_like(ce)
         with TIMER.span("ray_ce_fwd", 4 * (sigma.numel() + R * 7)):
           check(lib().vidar_ray_ce_fwd_f32(ptr(sigma), ptr(origin), ptr(gt), ptr(tindex), ptr(ce),
-                                         ptr(lse), ptr(valid), F_, R, Z, Y, X, K,
-                                         ctypes.c_float(step), stream_of(sigma)), "ray_ce_fwd")
+                                         ptr(lse), ptr(valid), F_, R, Z, Y, X, K, step, stream_of(sigma)), "ray_ce_fwd")
         ctx.save_for_backward(sigma, origin, gt, tindex, lse)
         ctx.cfg = (step, K)
         ctx.mark_non_differentiable(valid)
@@ -65,8 +63,8 @@ class _RayCE(Function):
         ws, wsp, wsn = workspace(lib().vidar_ray_bwd_workspace_bytes, F_, Z, Y, X, like=sigma)
         with TIMER.span("ray_ce_bwd", 4 * (2 * sigma.numel() + R * 6)):
           check(lib().vidar_ray_ce_bwd_f32(ptr(sigma), ptr(origin), ptr(gt), ptr(tindex), ptr(lse),
-                                         ptr(_f(grad_ce)), ptr(g), F_, R, Z, Y, X, K,
-                                         ctypes.c_float(step), wsp, wsn, stream_of(sigma)), "ray_ce_bwd")
+                                         ptr(_f(grad_ce)), ptr(g), F_, R, Z, Y, X, K, step,
+                                         wsp, wsn, stream_of(sigma)), "ray_ce_bwd")
         return g, None, None, None, None, None
 
 
@@ -80,8 +78,8 @@ class _RayGumbel(Function):
         dist = torch.empty(R, device=sigma.device); aux = torch.empty((R, 3), device=sigma.device)
         with TIMER.span("ray_gumbel_fwd", 4 * (sigma.numel() + R * (K + 8))):
           check(lib().vidar_ray_gumbel_fwd_f32(ptr(sigma), ptr(origin), ptr(pts), ptr(tindex),
-                                             ptr(noise), ptr(dist), ptr(aux), F_, R, Z, Y, X, K,
-                                             ctypes.c_float(step), stream_of(sigma)), "ray_gumbel_fwd")
+                                             ptr(noise), ptr(dist), ptr(aux), F_, R, Z, Y, X, K, step,
+                                             stream_of(sigma)), "ray_gumbel_fwd")
         ctx.save_for_backward(sigma, origin, pts, tindex, aux)
         ctx.cfg = (step, K)
         return dist
@@ -96,8 +94,8 @@ class _RayGumbel(Function):
         ws, wsp, wsn = workspace(lib().vidar_ray_bwd_workspace_bytes, F_, Z, Y, X, like=sigma)
         with TIMER.span("ray_gumbel_bwd", 4 * (2 * sigma.numel() + R * 8)):
           check(lib().vidar_ray_gumbel_bwd_f32(ptr(sigma), ptr(origin), ptr(pts), ptr(tindex), ptr(aux),
-                                             ptr(_f(grad_dist)), ptr(g), F_, R, Z, Y, X, K,
-                                             ctypes.c_float(step), wsp, wsn, stream_of(sigma)), "ray_gumbel_bwd")
+                                             ptr(_f(grad_dist)), ptr(g), F_, R, Z, Y, X, K, step,
+                                             wsp, wsn, stream_of(sigma)), "ray_gumbel_bwd")
         return g, None, None, None, None, None, None
 
 
@@ -112,8 +110,8 @@ class _RayDist(Function):
         aux = torch.empty((R, 3), device=sigma.device)
         with TIMER.span("ray_dist_fwd", 4 * (sigma.numel() + R * (K + 11))):
           check(lib().vidar_ray_dist_fwd_f32(ptr(sigma), ptr(origin), ptr(gt), ptr(tindex), ptr(noise),
-                                           ptr(dist), ptr(gt_len), ptr(aux), ptr(valid), F_, R, Z, Y, X, K,
-                                           ctypes.c_float(step), stream_of(sigma)), "ray_dist_fwd")
+                                           ptr(dist), ptr(gt_len), ptr(aux), ptr(valid), F_, R, Z, Y, X, K, step,
+                                           stream_of(sigma)), "ray_dist_fwd")
         ctx.save_for_backward(sigma, origin, gt, tindex, aux)
         ctx.cfg = (step, K)
         ctx.mark_non_differentiable(gt_len, valid)
@@ -129,8 +127,8 @@ class _RayDist(Function):
         ws, wsp, wsn = workspace(lib().vidar_ray_bwd_workspace_bytes, F_, Z, Y, X, like=sigma)
         with TIMER.span("ray_dist_bwd", 4 * (2 * sigma.numel() + R * 8)):
           check(lib().vidar_ray_dist_bwd_f32(ptr(sigma), ptr(origin), ptr(gt), ptr(tindex), ptr(aux),
-                                           ptr(_f(grad_dist)), ptr(g), F_, R, Z, Y, X, K,
-                                           ctypes.c_float(step), wsp, wsn, stream_of(sigma)), "ray_dist_bwd")
+                                           ptr(_f(grad_dist)), ptr(g), F_, R, Z, Y, X, K, step,
+                                           wsp, wsn, stream_of(sigma)), "ray_dist_bwd")
         return g, None, None, None, None, None, None
 
 
@@ -166,6 +164,5 @@ def ray_argmax(sigma, origin, pts, tindex, step=1.0, K=K_SAMPLES):
     F_, R, Z, Y, X = _dims(sigma, pts)
     pred = torch.empty(R, device=sigma.device); gt = torch.empty_like(pred)
     check(lib().vidar_ray_argmax_f32(ptr(sigma), ptr(origin), ptr(pts), ptr(tindex), ptr(pred),
-                                     ptr(gt), F_, R, Z, Y, X, int(K), ctypes.c_float(step),
-                                     stream_of(sigma)), "ray_argmax")
+                                     ptr(gt), F_, R, Z, Y, X, int(K), step, stream_of(sigma)), "ray_argmax")
     return pred, gt

@@ -130,8 +130,8 @@ class BEVFormerEncoder(TransformerLayerSequence):
         shape0 = metas_per_frame[0][0]["img_shape"][0]
         rng = (ctypes.c_float * 6)(*[float(v) for v in self.pc_range])
         check(lib().vidar_sca_plan_f32(ptr(ref_3d), ptr(l2i_d), ptr(ref_cam), ptr(mask), ptr(count), ptr(idx),
-                                       ptr(valid), ptr(lens), ptr(slot_of), rng, ctypes.c_float(float(shape0[0])),
-                                       ctypes.c_float(float(shape0[1])), F, B, N, Q, D, stream_of(ref_cam)),
+                                       ptr(valid), ptr(lens), ptr(slot_of), rng, shape0[0], shape0[1],
+                                       F, B, N, Q, D, stream_of(ref_cam)),
               "sca_plan")
         max_len = lens.max(dim=1).values.tolist()            # the one host read of the step
         # round the padded length up to a multiple of 256: the GEMMs of the cross attention then see a small set

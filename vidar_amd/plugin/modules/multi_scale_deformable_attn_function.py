@@ -7,7 +7,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ..._lib import lib, check, ptr, stream_of, TIMER
+from ..._lib import lib, check, ptr, stream_of, workspace, TIMER
 
 
 def msda_fwd_bytes(B, Nv, H, C, Nq, L, P):
@@ -39,31 +39,25 @@ BINNED_MIN_SAMPLES = 1 << 18
 
 
 def _bwd_workspace(value, B, Nv, H, Nq, L, P, binned):
-    import ctypes
+    """-> (tensor or None, pointer, byte count) of the binned scatter's scratch; (None, None, 0) = atomic scatter"""
     if binned is None:
         binned = B * Nq * H * L * P >= BINNED_MIN_SAMPLES
     if not binned:
-        return None, 0
-    f = lib().vidar_msda_bwd_workspace_bytes
-    f.restype = ctypes.c_size_t
-    n = int(f(B, Nv, H, Nq, L, P))
-    if n == 0:
-        return None, 0
-    return torch.empty((n + 7) // 8, dtype=torch.int64, device=value.device), n
+        return None, None, 0
+    return workspace(lib().vidar_msda_bwd_workspace_bytes, B, Nv, H, Nq, L, P, like=value)
 
 
 def _msda_backward(value, shapes, lsi, loc, w, grad_out, binned=None):
-    import ctypes
     B, Nv, H, C = value.shape
     _, Nq, _, L, P, _ = loc.shape
     gv = torch.empty_like(value)
     gl = torch.empty_like(loc)
     gw = torch.empty_like(w)
-    ws, nbytes = _bwd_workspace(value, B, Nv, H, Nq, L, P, binned)
+    ws, ws_ptr, nbytes = _bwd_workspace(value, B, Nv, H, Nq, L, P, binned)
     with TIMER.span(f"msda_bwd[L={L},P={P}]", msda_bwd_bytes(B, Nv, H, C, Nq, L, P)):
         check(lib().vidar_msda_bwd_f32(ptr(value), ptr(shapes), ptr(lsi), ptr(loc), ptr(w),
                                        ptr(grad_out), ptr(gv), ptr(gl), ptr(gw), B, Nv, H, C, Nq, L, P,
-                                       ptr(ws), ctypes.c_size_t(nbytes), stream_of(value)),
+                                       ws_ptr, nbytes, stream_of(value)),
               "ms_deform_attn_backward")
     return gv, gl, gw
 
@@ -165,7 +159,7 @@ class FusedDeformAttnFunction(Function):
         with TIMER.span(f"msda_fwd[L={L},P={P}]", msda_fwd_bytes(Bq, Nv, H, C, Nq, L, P)):
             check(lib().vidar_msda_fused_fwd_f32(ptr(value), ptr(shapes), ptr(lsi), ptr(off_raw), ptr(logit_raw),
                                                  ptr(ref), ptr(loc), ptr(w), ptr(out), bs, Qn, Nv, H, C, Nq, L, P,
-                                                 R, mode, int(merge), stream_of(value)), "ms_deform_attn_forward (fused)")
+                                                 R, mode, merge, stream_of(value)), "ms_deform_attn_forward (fused)")
         ctx.save_for_backward(value, shapes, lsi, loc, w)
         ctx.cfg = (bs, Qn, L, P, off_raw.shape, logit_raw.shape, merge)
         return out
@@ -173,7 +167,6 @@ class FusedDeformAttnFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output):
-        import ctypes
         value, shapes, lsi, loc, w = ctx.saved_tensors
         bs, Qn, L, P, off_shape, logit_shape, merge = ctx.cfg
         Bq, Nv, H, C = value.shape
@@ -182,11 +175,11 @@ class FusedDeformAttnFunction(Function):
         gv = torch.empty_like(value)
         g_off = torch.empty(off_shape, dtype=torch.float32, device=value.device)
         g_logit = torch.empty(logit_shape, dtype=torch.float32, device=value.device)
-        ws, nbytes = _bwd_workspace(value, Bq, Nv, H, Nq, L, P, None)
+        ws, ws_ptr, nbytes = _bwd_workspace(value, Bq, Nv, H, Nq, L, P, None)
         with TIMER.span(f"msda_bwd[L={L},P={P}]", msda_bwd_bytes(Bq, Nv, H, C, Nq, L, P)):
             check(lib().vidar_msda_fused_bwd_f32(ptr(value), ptr(shapes), ptr(lsi), ptr(loc), ptr(w), ptr(go),
                                                  ptr(gv), ptr(g_off), ptr(g_logit), bs, Qn, Nv, H, C, Nq, L, P,
-                                                 int(merge), ptr(ws), ctypes.c_size_t(nbytes), stream_of(value)),
+                                                 merge, ws_ptr, nbytes, stream_of(value)),
                   "ms_deform_attn_backward (fused)")
         dv, do, dl = ctx.in_dtypes
         return gv.to(dv), None, None, g_off.to(do), g_logit.to(dl), None, None, None, None, None, None

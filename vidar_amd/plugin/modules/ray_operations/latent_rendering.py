@@ -5,7 +5,6 @@ The ray-march (":96-150") runs in two fused gfx950 kernels + adjoints (csrc/late
 the three Linear layers stay GEMMs (rocBLAS/hipBLASLt through torch)."""
 from __future__ import annotations
 
-import ctypes
 
 import numpy as np
 import torch
@@ -34,7 +33,7 @@ class _PathProb(Function):
         step = _step(grid_step, H, W)
         with TIMER.span("lr_prob_fwd", 4 * occ.numel() * 2):
           check(lib().vidar_latent_render_prob_fwd_f32(ptr(occ), ptr(prob), bs, H, W, Z, grid_num,
-                                                     ctypes.c_float(step), act, stream_of(occ)),
+                                                     step, act, stream_of(occ)),
               "latent_render_prob_fwd")
         ctx.save_for_backward(occ)
         ctx.cfg = (grid_num, step, act)
@@ -51,7 +50,7 @@ class _PathProb(Function):
         with TIMER.span("lr_prob_bwd", 4 * occ.numel() * 3):
           check(lib().vidar_latent_render_prob_bwd_f32(ptr(occ), ptr(grad_prob.float().contiguous()),
                                                      ptr(g), bs, H, W, Z, grid_num,
-                                                     ctypes.c_float(step), act, wsp, wsn, stream_of(occ)),
+                                                     step, act, wsp, wsn, stream_of(occ)),
               "latent_render_prob_bwd")
         return g, None, None, None
 
@@ -65,8 +64,7 @@ class _RayGather(Function):
         step = _step(grid_step, H, W)
         with TIMER.span("lr_gather_fwd", 4 * prob.numel() * 4):
           check(lib().vidar_latent_render_gather_fwd_f32(ptr(prob), ptr(a), ptr(feat), ptr(msum), bs, H,
-                                                       W, Z, grid_num, ctypes.c_float(step),
-                                                       ctypes.c_float(eps), stream_of(prob)),
+                                                       W, Z, grid_num, step, eps, stream_of(prob)),
               "latent_render_gather_fwd")
         ctx.save_for_backward(prob, a, feat, msum)
         ctx.cfg = (grid_num, step, eps)
@@ -84,8 +82,7 @@ class _RayGather(Function):
           check(lib().vidar_latent_render_gather_bwd_f32(ptr(prob), ptr(a), ptr(feat), ptr(msum),
                                                        ptr(grad_feat.float().contiguous()), ptr(gp),
                                                        ptr(ga), bs, H, W, Z, grid_num,
-                                                       ctypes.c_float(step), ctypes.c_float(eps),
-                                                       wsp, wsn, stream_of(prob)), "latent_render_gather_bwd")
+                                                       step, eps, wsp, wsn, stream_of(prob)), "latent_render_gather_bwd")
         return gp, ga, None, None, None
 
 

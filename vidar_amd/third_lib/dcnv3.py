@@ -5,8 +5,6 @@ accepted and ignored.  No CPU path: host tensors raise RuntimeError like the ref
 on the CPU")."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from .._lib import lib, check, ptr, stream_of, workspace
@@ -48,7 +46,7 @@ def dcnv3_forward(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, p
     out = torch.empty((N, Ho, Wo, input.shape[3]), dtype=torch.float32, device=input.device)
     with torch.cuda.device(input.device):
         check(lib().vidar_dcnv3_forward_f32(ptr(input), ptr(offset), ptr(mask), ptr(out), N, H, W, *g,
-                                            ctypes.c_float(float(offset_scale)), stream_of(input)), "DCNv3.dcnv3_forward")
+                                            float(offset_scale), stream_of(input)), "DCNv3.dcnv3_forward")
     return out
 
 
@@ -68,6 +66,6 @@ def dcnv3_backward(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, 
         ws, wp, wn = workspace(L.vidar_dcnv3_backward_workspace_bytes, N, H, W, *g, like=input)
         check(L.vidar_dcnv3_backward_f32(ptr(input), ptr(offset), ptr(mask), ptr(grad_output), ptr(grad_input),
                                          ptr(grad_offset), ptr(grad_mask), N, H, W, *g,
-                                         ctypes.c_float(float(offset_scale)), wp, wn, stream_of(input)),
+                                         float(offset_scale), wp, wn, stream_of(input)),
               "DCNv3.dcnv3_backward")
     return [grad_input, grad_offset, grad_mask]

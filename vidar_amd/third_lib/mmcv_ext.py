@@ -5,8 +5,6 @@ temporal_self_attention.py:20-21, encoder.py:20-21, vidar_decoder.py:20-21), sam
 and the `im2col_step` keyword of its call sites (function.py:42-48, :74-84, :118-124, :150-160)."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from .._lib import lib, check, ptr, stream_of
@@ -63,9 +61,9 @@ def ms_deform_attn_backward(value, value_spatial_shapes, value_level_start_index
              grad_attn_weight), (value_spatial_shapes, value_level_start_index))
     B, Nv, H, C, Nq, L, P = _dims(value, sampling_locations)
     from ..plugin.modules.multi_scale_deformable_attn_function import _bwd_workspace
-    ws, nbytes = _bwd_workspace(value, B, Nv, H, Nq, L, P, None)
+    ws, ws_ptr, nbytes = _bwd_workspace(value, B, Nv, H, Nq, L, P, None)
     check(lib().vidar_msda_bwd_f32(ptr(value), ptr(value_spatial_shapes), ptr(value_level_start_index),
                                    ptr(sampling_locations), ptr(attention_weights), ptr(grad_output),
                                    ptr(grad_value), ptr(grad_sampling_loc), ptr(grad_attn_weight), B, Nv, H, C,
-                                   Nq, L, P, ptr(ws), ctypes.c_size_t(nbytes), stream_of(value)),
+                                   Nq, L, P, ws_ptr, nbytes, stream_of(value)),
           "ms_deform_attn_backward")
