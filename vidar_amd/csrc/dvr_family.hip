@@ -34,6 +34,7 @@
 #include "vidar_common.h"
 #include "dvr_march.h"
 #include "dvr_par_kernels.h"
+#include "scatter_copies.h"
 
 namespace {
 
@@ -232,9 +233,9 @@ __global__ __launch_bounds__(256) void dvxlr_scatter_kernel(
   const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
   const int c = blockIdx.x * (256 / kWave) + wave;
   if (c >= M) return;
-  // rays of one frame share their first voxels (the sensor origin): workgroup i adds into private copy i mod n
-  grad_sigma += (size_t)(blockIdx.x % ncopies) * copy_stride;
-  if (V2) grad_regul += (size_t)(blockIdx.x % ncopies) * copy_stride;
+  // rays of one frame share their first voxels (the sensor origin): private copies, scatter_copies.h
+  grad_sigma += scatter_copy_of_block(ncopies) * copy_stride;
+  if (V2) grad_regul += scatter_copy_of_block(ncopies) * copy_stride;
   const float t = tindex[(size_t)n * M + c];
   if (t < 0.f || t != t) return;
   const long ti = (long)t;
@@ -264,16 +265,6 @@ __global__ __launch_bounds__(256) void dvxlr_scatter_kernel(
   }
 }
 
-constexpr int kScatterCopies = 8;
-__global__ __launch_bounds__(256) void dvxlr_sum_copies_kernel(const float* __restrict__ copies, float* __restrict__ out,
-                                                               size_t n) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  float a = copies[i];
-  for (int c = 1; c < kScatterCopies; ++c) a += copies[(size_t)c * n + i];
-  out[i] = a;
-}
-
 // ----------------------------------------------------------------------------------------------
 // init (occupancy rasterisation, dvr.cu:14-63 == dvxlr.cu:12-61)
 // ----------------------------------------------------------------------------------------------
@@ -297,6 +288,23 @@ __global__ __launch_bounds__(256) void dvr_init_kernel(const float* __restrict__
 inline int hip_ret() { return vidar_last_error(); }
 inline bool bad_dims(int N, int M, int T, int Z, int Y, int X) {
   return N < 0 || M < 0 || T <= 0 || Z <= 0 || Y <= 0 || X <= 0;
+}
+
+// get_grad_sigma (grad_regul == nullptr) and get_grad_sigma_v2: private copies of the volume(s) if the workspace allows
+// (scatter_copies.h); N == 0, M == 0 and L == 0 leave zeroed outputs
+template <bool V2>
+int dvxlr_scatter_launch(const float* elementwise_mult, const float* indices, const float* tindex,
+                         const float* indicator, const float* grad_ray_pred, float* grad_sigma,
+                         float* grad_regul, int N, int M, int L, int T, int Z, int Y, int X, void* workspace,
+                         size_t workspace_bytes, hipStream_t s_) {
+  if (bad_dims(N, M, T, Z, Y, X) || L < 0) return VIDAR_ERR_BAD_ARG;
+  const size_t n = (size_t)N * T * Z * Y * X;
+  return scatter_with_copies(grad_sigma, grad_regul, n, N == 0 || M == 0 || L == 0, workspace, workspace_bytes, s_,
+                             [&](float* acc, float* acc2, int ncopies) {
+    Vol g{T, T, Z, Y, X};
+    hipLaunchKernelGGL(dvxlr_scatter_kernel<V2>, dim3((M + 3) / 4, N), dim3(256), 0, s_, elementwise_mult, indices,
+                       tindex, indicator, grad_ray_pred, acc, acc2, M, L, g, ncopies, n);
+  });
 }
 
 }  // namespace
@@ -467,7 +475,7 @@ int vidar_dvxlr2_render_f32(const float* sigma, const float* origin, const float
 
 size_t vidar_dvxlr_get_grad_sigma_workspace_bytes(int N, int T, int Z, int Y, int X, int volumes) {
   if (bad_dims(N, 0, T, Z, Y, X) || volumes < 1 || volumes > 2) return 0;
-  return sizeof(float) * (size_t)N * T * Z * Y * X * kScatterCopies * volumes;   // 1: get_grad_sigma, 2: _v2 (two volumes)
+  return scatter_workspace_bytes((size_t)N * T * Z * Y * X, volumes);   // 1: get_grad_sigma, 2: _v2 (two volumes)
 }
 
 int vidar_dvxlr_get_grad_sigma_f32(const float* elementwise_mult, const float* indices,
@@ -475,22 +483,8 @@ int vidar_dvxlr_get_grad_sigma_f32(const float* elementwise_mult, const float* i
                                    int Z, int Y, int X, void* workspace, size_t workspace_bytes,
                                    void* stream) {
   VIDAR_ENTER();
-  if (bad_dims(N, M, T, Z, Y, X) || L < 0) return VIDAR_ERR_BAD_ARG;
-  const size_t n = (size_t)N * T * Z * Y * X;
-  const bool copies = workspace != nullptr && workspace_bytes >= sizeof(float) * n * kScatterCopies;
-  float* acc = copies ? (float*)workspace : grad_sigma;
-  hipStream_t s_ = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(acc, 0, sizeof(float) * n * (copies ? kScatterCopies : 1), s_);
-  if (e != hipSuccess) return (int)e;
-  if (N == 0 || M == 0 || L == 0) return copies ? (int)hipMemsetAsync(grad_sigma, 0, sizeof(float) * n, s_) : 0;
-  Vol g{T, T, Z, Y, X};
-  dim3 grid((M + 3) / 4, N);
-  hipLaunchKernelGGL(dvxlr_scatter_kernel<false>, grid, dim3(256), 0, s_, elementwise_mult, indices, tindex,
-                     (const float*)nullptr, (const float*)nullptr, acc, (float*)nullptr, M, L, g,
-                     copies ? kScatterCopies : 1, n);
-  if (copies)
-    hipLaunchKernelGGL(dvxlr_sum_copies_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s_, acc, grad_sigma, n);
-  return vidar_last_error();
+  return dvxlr_scatter_launch<false>(elementwise_mult, indices, tindex, nullptr, nullptr, grad_sigma, nullptr, N, M, L,
+                                     T, Z, Y, X, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int vidar_dvxlr2_get_grad_sigma_f32(const float* elementwise_mult, const float* indices,
@@ -499,36 +493,9 @@ int vidar_dvxlr2_get_grad_sigma_f32(const float* elementwise_mult, const float* 
                                     float* grad_sigma_regul, int N, int M, int L, int T, int Z, int Y,
                                     int X, void* workspace, size_t workspace_bytes, void* stream) {
   VIDAR_ENTER();
-  if (bad_dims(N, M, T, Z, Y, X) || L < 0) return VIDAR_ERR_BAD_ARG;
-  const size_t n = (size_t)N * T * Z * Y * X;
-  const bool copies = workspace != nullptr && workspace_bytes >= vidar_dvxlr_get_grad_sigma_workspace_bytes(N, T, Z, Y, X, 2);
-  float* acc = copies ? (float*)workspace : grad_sigma;
-  float* acc2 = copies ? (float*)workspace + n * kScatterCopies : grad_sigma_regul;
-  hipStream_t s_ = (hipStream_t)stream;
-  hipError_t e;
-  if (copies) {
-    e = hipMemsetAsync(acc, 0, sizeof(float) * n * kScatterCopies * 2, s_);
-  } else {
-    e = hipMemsetAsync(acc, 0, sizeof(float) * n, s_);
-    if (e == hipSuccess) e = hipMemsetAsync(acc2, 0, sizeof(float) * n, s_);
-  }
-  if (e != hipSuccess) return (int)e;
-  if (N == 0 || M == 0 || L == 0) {
-    if (!copies) return 0;
-    e = hipMemsetAsync(grad_sigma, 0, sizeof(float) * n, s_);
-    if (e == hipSuccess) e = hipMemsetAsync(grad_sigma_regul, 0, sizeof(float) * n, s_);
-    return (int)e;
-  }
-  Vol g{T, T, Z, Y, X};
-  dim3 grid((M + 3) / 4, N);
-  hipLaunchKernelGGL(dvxlr_scatter_kernel<true>, grid, dim3(256), 0, s_, elementwise_mult, indices, tindex, indicator,
-                     grad_ray_pred, acc, acc2, M, L, g, copies ? kScatterCopies : 1, n);
-  if (copies) {
-    const dim3 rg((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(dvxlr_sum_copies_kernel, rg, dim3(256), 0, s_, acc, grad_sigma, n);
-    hipLaunchKernelGGL(dvxlr_sum_copies_kernel, rg, dim3(256), 0, s_, acc2, grad_sigma_regul, n);
-  }
-  return vidar_last_error();
+  return dvxlr_scatter_launch<true>(elementwise_mult, indices, tindex, indicator, grad_ray_pred, grad_sigma,
+                                    grad_sigma_regul, N, M, L, T, Z, Y, X, workspace, workspace_bytes,
+                                    (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -24,6 +24,7 @@
 
 #include "vidar_hip.h"
 #include "vidar_common.h"
+#include "scatter_copies.h"
 
 namespace {
 
@@ -31,16 +32,11 @@ constexpr int kZ = 16;
 constexpr int kThreads = 256;
 constexpr int kCellsPerBlock = kThreads / 64;
 
-// Every ray starts at the BEV centre, so the first waypoints of all H*W rays scatter onto the same few cells and the
-// atomics on those addresses serialise: the backward kernels add into kCopies private copies of the gradient maps
-// (workgroup i -> copy i mod n; neighbouring workgroups = neighbouring cells = nearly the same ray), kept in the
-// CALLER's workspace (vidar_latent_render_bwd_workspace_bytes; without one they add straight into the outputs), and a
-// small kernel sums the copies -- n times fewer atomics per hot address for the same total number.  Measured on MI355X
-// (profiles/r04_staged_variants_kernel_times.log): lr_prob_bwd 0.66 -> 0.48 ms, lr_gather_bwd 1.32 -> 1.08 ms with 8
-// copies, memset and sum included: the kernels were serialised on the hot addresses, not bound by the atomic rate.
-constexpr int kCopies = 8;
+// Every ray starts at the BEV centre, so the first waypoints of all H*W rays scatter onto the same few cells: the
+// backward kernels add into private copies of the gradient maps (scatter_copies.h; the kernels were serialised on the
+// hot addresses, not bound by the atomic rate).
 // which private copy this workgroup adds into, as an offset in maps of [bs, Q, 16] (0 when the variant is off)
-__device__ __forceinline__ size_t copy_of_block(int ncopies) { return (size_t)(blockIdx.x % ncopies) * gridDim.y; }
+__device__ __forceinline__ size_t copy_of_block(int ncopies) { return scatter_copy_of_block(ncopies) * gridDim.y; }
 
 struct Geo {
   int H, W, G;
@@ -300,17 +296,6 @@ __global__ __launch_bounds__(kThreads) void lr_gather_bwd_kernel(
   }
 }
 
-__global__ __launch_bounds__(256) void lr_sum_copies_kernel(const float4* __restrict__ copies, float4* __restrict__ out,
-                                                            size_t n4) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  float4 a = copies[i];
-  for (int c = 1; c < kCopies; ++c) {
-    const float4 v = copies[(size_t)c * n4 + i];
-    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-  }
-  out[i] = a;
-}
 inline bool lr_bad(int bs, int H, int W, int Z, int G, int act) {
   return bs < 0 || H <= 0 || W <= 0 || Z != kZ || G <= 0 || (act != 0 && act != 1);
 }
@@ -322,7 +307,7 @@ extern "C" {
 
 size_t vidar_latent_render_bwd_workspace_bytes(int bs, int H, int W, int Z, int maps) {
   if (bs <= 0 || H <= 0 || W <= 0 || Z <= 0 || maps < 1 || maps > 2) return 0;
-  return sizeof(float) * (size_t)maps * bs * H * W * Z * kCopies;   // maps: 1 = prob_bwd (grad_occ), 2 = gather_bwd
+  return scatter_workspace_bytes((size_t)bs * H * W * Z, maps);   // maps: 1 = prob_bwd (grad_occ), 2 = gather_bwd
 }
 
 int vidar_latent_render_prob_fwd_f32(const float* occ, float* path_prob, int bs, int H, int W, int Z,
@@ -341,21 +326,14 @@ int vidar_latent_render_prob_bwd_f32(const float* occ, const float* grad_path_pr
                                      void* workspace, size_t workspace_bytes, void* stream) {
   VIDAR_ENTER();
   if (lr_bad(bs, H, W, Z, grid_num, act)) return VIDAR_ERR_BAD_ARG;
-  if (bs == 0) return 0;
+  if (bs == 0) return 0;   // before anything is touched
   hipStream_t s = (hipStream_t)stream;
   Geo g{H, W, grid_num, step, act, 0.f};
-  const size_t n = (size_t)bs * H * W * Z;
-  const bool copies = workspace != nullptr && workspace_bytes >= sizeof(float) * n * kCopies &&
-                      (((uintptr_t)workspace | (uintptr_t)grad_occ) & 15u) == 0;
-  float* acc = copies ? (float*)workspace : grad_occ;
-  hipError_t e = hipMemsetAsync(acc, 0, sizeof(float) * n * (copies ? kCopies : 1), s);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(lr_prob_bwd_kernel, lr_grid(bs, H * W), dim3(kThreads), 0, s, occ, grad_path_prob, acc, H * W, g,
-                     copies ? kCopies : 1);
-  if (copies)
-    hipLaunchKernelGGL(lr_sum_copies_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s,
-                       (const float4*)acc, (float4*)grad_occ, n / 4);
-  return vidar_last_error();
+  return scatter_with_copies<float4>(grad_occ, nullptr, (size_t)bs * H * W * Z, false, workspace, workspace_bytes, s,
+                                     [&](float* acc, float*, int ncopies) {
+    hipLaunchKernelGGL(lr_prob_bwd_kernel, lr_grid(bs, H * W), dim3(kThreads), 0, s, occ, grad_path_prob, acc, H * W, g,
+                       ncopies);
+  });
 }
 
 int vidar_latent_render_gather_fwd_f32(const float* path_prob, const float* lora_a, float* feat,
@@ -377,30 +355,14 @@ int vidar_latent_render_gather_bwd_f32(const float* path_prob, const float* lora
                                        void* workspace, size_t workspace_bytes, void* stream) {
   VIDAR_ENTER();
   if (lr_bad(bs, H, W, Z, grid_num, 0)) return VIDAR_ERR_BAD_ARG;
-  if (bs == 0) return 0;
+  if (bs == 0) return 0;   // before anything is touched
   hipStream_t s = (hipStream_t)stream;
   Geo g{H, W, grid_num, step, 0, eps};
-  const size_t n = (size_t)bs * H * W * Z;
-  const bool copies = workspace != nullptr && workspace_bytes >= vidar_latent_render_bwd_workspace_bytes(bs, H, W, Z, 2) &&
-                      (((uintptr_t)workspace | (uintptr_t)grad_path_prob | (uintptr_t)grad_lora_a) & 15u) == 0;
-  float* sp = copies ? (float*)workspace : grad_path_prob;
-  float* sa = copies ? (float*)workspace + n * kCopies : grad_lora_a;
-  hipError_t e;
-  if (copies) {
-    e = hipMemsetAsync(sp, 0, sizeof(float) * 2 * n * kCopies, s);
-  } else {
-    e = hipMemsetAsync(sp, 0, sizeof(float) * n, s);
-    if (e == hipSuccess) e = hipMemsetAsync(sa, 0, sizeof(float) * n, s);
-  }
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(lr_gather_bwd_kernel, lr_grid(bs, H * W), dim3(kThreads), 0, s, path_prob, lora_a, feat, msum,
-                     grad_feat, sp, sa, H * W, g, copies ? kCopies : 1);
-  if (copies) {
-    const dim3 rg((unsigned)((n / 4 + 255) / 256));
-    hipLaunchKernelGGL(lr_sum_copies_kernel, rg, dim3(256), 0, s, (const float4*)sp, (float4*)grad_path_prob, n / 4);
-    hipLaunchKernelGGL(lr_sum_copies_kernel, rg, dim3(256), 0, s, (const float4*)sa, (float4*)grad_lora_a, n / 4);
-  }
-  return vidar_last_error();
+  return scatter_with_copies<float4>(grad_path_prob, grad_lora_a, (size_t)bs * H * W * Z, false, workspace,
+                                     workspace_bytes, s, [&](float* sp, float* sa, int ncopies) {
+    hipLaunchKernelGGL(lr_gather_bwd_kernel, lr_grid(bs, H * W), dim3(kThreads), 0, s, path_prob, lora_a, feat, msum,
+                       grad_feat, sp, sa, H * W, g, ncopies);
+  });
 }
 
 }  // extern "C"

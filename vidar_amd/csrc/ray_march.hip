@@ -11,14 +11,17 @@
 // sampled logits, -inf masks, softmax); here one wave owns one ray, its 512 waypoints live in
 // registers (8 per lane) and only O(1) values per ray ever reach HBM.
 //
-// Waypoint count K = ray_grid_num, two forms:
+// Waypoint count K = ray_grid_num.  Every op's arithmetic is written once, as a `*_body<K512>` that the kernels
+// instantiate in two forms:
 //   K == 512        register-resident (the released configs): the kernels without a suffix.
 //   1 <= K <= kKMax streamed (`*_any_kernel`): the wave walks the ray in passes of 64 waypoints (32 in the backward) and
-//                   keeps O(1) state per lane -- pass 1 finds the max logit (and the best perturbed logit, its index and
-//                   length), pass 2 samples the logits AGAIN for the exp sums (the "mass beyond the sample" needs
-//                   pred_dist, known only after pass 1).  Waypoints k >= K are never sampled and never read noise.
-//                   Every lane adds its waypoints in the same order as the register form, so K = 512 through the
-//                   streamed form gives the same bits (tests/test_ray_options_gpu.py; vidar_ray_force_streamed).
+//                   keeps O(1) state per lane.
+// A forward body visits the waypoints twice (struct Waypoints): visit 1 finds the max logit (and the best perturbed
+// logit, its index and length), visit 2 adds the exp sums (the "mass beyond the sample" needs pred_dist, known only
+// after visit 1).  The register form samples in visit 1 and replays its 8 registers per lane in visit 2; the streamed
+// form samples the logits AGAIN.  Waypoints k >= K are never sampled and never read noise.  Every lane adds its
+// waypoints in the same order in both forms, so K = 512 through the streamed form gives the same bits
+// (tests/test_ray_options_gpu.py; vidar_ray_force_streamed).
 //   kKMax = 65536: nothing in the streamed kernels depends on K but the trip count ((k + 0.5f) is exact in fp32 far past
 //   it, noise offsets are size_t); the bound only keeps a corrupt argument from becoming a minutes-long launch.  The
 //   longest ray of the 200 x 200 x 16 volume is its 283-voxel diagonal = 2264 waypoints at step 0.125.
@@ -35,6 +38,7 @@
 
 #include "vidar_hip.h"
 #include "vidar_common.h"
+#include "scatter_copies.h"
 
 namespace {
 
@@ -147,89 +151,86 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 constexpr float kNegInf = -__builtin_inff();
 
-// Every ray of a frame starts at the sensor origin, so the first waypoints of all rays of a frame scatter onto the same
-// 8-27 voxels (210 000 rays x ~3 waypoints x 8 corners onto ~190 addresses in one ray_ce_bwd launch) and the atomics on
-// those addresses serialise: the backward kernels add into kRayCopies private copies of the gradient volume
-// (workgroup i -> copy i mod n) kept in the CALLER's workspace (vidar_ray_bwd_workspace_bytes; without one they add
-// straight into grad_sigma) and a small kernel sums them.  Measured on MI355X
-// (profiles/r04_staged_variants_kernel_times.log): ray_ce_bwd 0.69 -> 0.41 ms, ray_gumbel_bwd 0.41 -> 0.29 ms with 8
-// copies, memset and sum included.  (Leaving the 512-waypoint loops after the run of live waypoints -- the waypoints
-// inside the volume are ONE run of consecutive k, tests/test_ray_early_exit_cpu.py -- was measured too: no change,
-// the masked passes cost almost nothing next to the atomics; removed.)
-constexpr int kRayCopies = 8;
-
-
-// logits of the K waypoints owned by this lane
-__device__ __forceinline__ void lane_logits(const float* __restrict__ vol, const Ray& r,
-                                            const VolDims& v, float step, int lane,
-                                            float (&f)[kPerLane]) {
+// running (value, index, length) arg-max; the first index wins ties, like torch.max
+// kNoIndex only has to be larger than every index any form can produce: it is never used but in `k < i`
+constexpr int kNoIndex = 0x7fffffff;
+struct Best {
+  float v = kNegInf;
+  int i = kNoIndex;
+  float len = 0.f;
+  __device__ __forceinline__ void take(float z, int k, float l) {
+    if (z > v || (z == v && k < i)) { v = z; i = k; len = l; }
+  }
+};
+__device__ __forceinline__ void wave_argmax(Best& b) {
 #pragma unroll
-  for (int j = 0; j < kPerLane; ++j) {
+  for (int s = 32; s >= 1; s >>= 1)
+    b.take(__shfl_xor(b.v, s, kWave), __shfl_xor(b.i, s, kWave), __shfl_xor(b.len, s, kWave));
+}
+
+// The K waypoints of one ray as the forward bodies walk them: every lane visits its waypoints k = lane, lane + 64, ...
+// TWICE, in that order in both forms (which is what makes their sums the same bits).
+//   K512 (K == kK): the first visit samples logit and length into 8 registers per lane, the second replays them;
+//   streamed:       both visits sample; waypoints k >= K are never sampled.
+// MASKED: the training ops' sampler (outside the open volume -> -inf); otherwise the decode's: plain zero padding, and
+// an exact zero -- outside, or a zero of the volume -- counts as -inf (vidar_head_base.py:728).
+template <bool K512, bool MASKED>
+struct Waypoints {
+  const float* vol;
+  const Ray& ray;
+  const VolDims& v;
+  float step;
+  int lane, K;
+  float f[K512 ? kPerLane : 1], len[K512 ? kPerLane : 1];
+
+  __device__ __forceinline__ void sample(int k, float& logit, float& length) const {
     float sx, sy, sz;
-    waypoint(r, lane + j * kWave, step, sx, sy, sz);
-    const Tri t = make_tri(sx, sy, sz, v);
-    f[j] = t.masked ? kNegInf : tri_load(vol, t);
+    waypoint(ray, k, step, sx, sy, sz);
+    const Tri t = make_tri<MASKED>(sx, sy, sz, v);
+    length = dist_to(ray, sx, sy, sz);
+    if (MASKED) {
+      logit = t.masked ? kNegInf : tri_load(vol, t);
+    } else {
+      const float val = (sx == sx) ? tri_load(vol, t) : 0.f;
+      logit = (val == 0.f) ? kNegInf : val;
+    }
   }
-}
-
-// logit (and length) of waypoint k, for the streamed kernels
-__device__ __forceinline__ float logit_at(const float* __restrict__ vol, const Ray& r, const VolDims& v,
-                                          float step, int k, float& len) {
-  float sx, sy, sz;
-  waypoint(r, k, step, sx, sy, sz);
-  const Tri t = make_tri(sx, sy, sz, v);
-  len = dist_to(r, sx, sy, sz);
-  return t.masked ? kNegInf : tri_load(vol, t);
-}
-
-// (value, index, length) arg-max across the wave, first index wins ties
-__device__ __forceinline__ void wave_argmax(float& best, int& bi, float& blen) {
+  // fn(k, logit, length)
+  template <class Fn>
+  __device__ __forceinline__ void first(Fn fn) {
+    if (K512) {
 #pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) {
-    const float ob = __shfl_xor(best, s, kWave);
-    const int oi = __shfl_xor(bi, s, kWave);
-    const float ol = __shfl_xor(blen, s, kWave);
-    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; blen = ol; }
+      for (int j = 0; j < kPerLane; ++j) {
+        sample(lane + j * kWave, f[j], len[j]);
+        fn(lane + j * kWave, f[j], len[j]);
+      }
+    } else {
+      for (int k = lane; k < K; k += kWave) {
+        sample(k, f[0], len[0]);
+        fn(k, f[0], len[0]);
+      }
+    }
   }
-}
+  template <class Fn>
+  __device__ __forceinline__ void second(Fn fn) {
+    if (K512) {
+#pragma unroll
+      for (int j = 0; j < kPerLane; ++j) fn(lane + j * kWave, f[j], len[j]);
+    } else {
+      first(fn);
+    }
+  }
+};
+
+// END_POINT, in the bodies below: the ray's end point is an entry of its own in front of the K waypoints (lane 0 carries
+// it), and rays whose end point leaves the open volume are dropped (:464-467).  ray_ce and ray_dist; ray_gumbel and
+// ray_argmax see the waypoints only and drop no ray.
 
 // ---------------------------------------------------------------------------------------------
 // GT-ray march + cross entropy on the end-point sample
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void ray_ce_fwd_kernel(
-    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ gt,
-    const float* __restrict__ tindex, float* __restrict__ ce, float* __restrict__ lse_out,
-    float* __restrict__ valid, int R, VolDims v, float step) {
-  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
-  if (r >= R) return;
-  const int lane = threadIdx.x % kWave;
-  const Ray ray = load_ray(origin, gt, tindex, r, v);
-  const Tri t0 = make_tri(ray.px, ray.py, ray.pz, v);
-  const bool ok = ray.f >= 0 && !t0.masked;      // rays whose end point leaves the volume are dropped (:464-467)
-  float out_ce = 0.f, out_lse = 0.f;
-  if (ok) {
-    const float* vol = sigma + (size_t)ray.f * v.Z * v.Y * v.X;
-    const float f0 = tri_load(vol, t0);
-    float f[kPerLane];
-    lane_logits(vol, ray, v, step, lane, f);
-    float m = f0;
-#pragma unroll
-    for (int j = 0; j < kPerLane; ++j) m = fmaxf(m, f[j]);
-    m = wave_max(m);
-    float s = (lane == 0) ? expf(f0 - m) : 0.f;
-#pragma unroll
-    for (int j = 0; j < kPerLane; ++j) s += expf(f[j] - m);   // exp(-inf) == 0
-    s = wave_sum(s);
-    out_lse = m + logf(s);
-    out_ce = out_lse - f0;
-  }
-  if (lane == 0) {
-    ce[r] = out_ce; lse_out[r] = out_lse; valid[r] = ok ? 1.f : 0.f;
-  }
-}
-
-// streamed form, any K
-__global__ __launch_bounds__(kThreads) void ray_ce_fwd_any_kernel(
+template <bool K512>
+__device__ __forceinline__ void ray_ce_fwd_body(
     const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ gt,
     const float* __restrict__ tindex, float* __restrict__ ce, float* __restrict__ lse_out,
     float* __restrict__ valid, int R, VolDims v, float step, int K) {
@@ -243,11 +244,12 @@ __global__ __launch_bounds__(kThreads) void ray_ce_fwd_any_kernel(
   if (ok) {
     const float* vol = sigma + (size_t)ray.f * v.Z * v.Y * v.X;
     const float f0 = tri_load(vol, t0);
-    float m = f0, len;
-    for (int k = lane; k < K; k += kWave) m = fmaxf(m, logit_at(vol, ray, v, step, k, len));
+    Waypoints<K512, true> w{vol, ray, v, step, lane, K};
+    float m = f0;
+    w.first([&](int, float f, float) { m = fmaxf(m, f); });
     m = wave_max(m);
     float s = (lane == 0) ? expf(f0 - m) : 0.f;
-    for (int k = lane; k < K; k += kWave) s += expf(logit_at(vol, ray, v, step, k, len) - m);
+    w.second([&](int, float f, float) { s += expf(f - m); });   // exp(-inf) == 0
     s = wave_sum(s);
     out_lse = m + logf(s);
     out_ce = out_lse - f0;
@@ -257,327 +259,67 @@ __global__ __launch_bounds__(kThreads) void ray_ce_fwd_any_kernel(
   }
 }
 
-// K512: the fixed 16 passes of the register form's K; otherwise ceil(K / 32) passes with a tail predicate
-template <bool K512>
-__device__ __forceinline__ void ray_ce_bwd_body(
-    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ gt,
-    const float* __restrict__ tindex, const float* __restrict__ lse_in,
-    const float* __restrict__ grad_ce, float* __restrict__ grad_sigma, int R, VolDims v,
-    float step, int ncopies, int K) {
-  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
-  if (r >= R) return;
-  const int lane = threadIdx.x % kWave;
-  const float g = grad_ce[r];
-  if (g == 0.f) return;
-  const Ray ray = load_ray(origin, gt, tindex, r, v);
-  const Tri t0 = make_tri(ray.px, ray.py, ray.pz, v);
-  if (ray.f < 0 || t0.masked) return;
-  const size_t slice = (size_t)ray.f * v.Z * v.Y * v.X;
-  const float* vol = sigma + slice;
-  float* gvol = grad_sigma + (size_t)(blockIdx.x % ncopies) * v.F * v.Z * v.Y * v.X + slice;
-  const float lse = lse_in[r];
-  if (lane == 0) tri_scatter(gvol, t0, g * (expf(tri_load(vol, t0) - lse) - 1.f));
-  const int cx = lane & 1;
-  const int passes = K512 ? 2 * kPerLane : (K + kWave / 2 - 1) / (kWave / 2);
-  for (int j = 0; j < passes; ++j) {                   // 32 waypoints per pass, a lane pair per waypoint
-    const int k = (lane >> 1) + j * (kWave / 2);
-    if (!K512 && k >= K) break;                        // only in the last pass
-    float sx, sy, sz;
-    waypoint(ray, k, step, sx, sy, sz);
-    const Tri t = make_tri(sx, sy, sz, v);
-    if (!t.masked) tri_scatter_x(gvol, t, g * expf(tri_load(vol, t) - lse), cx);
-  }
-}
-__global__ __launch_bounds__(kThreads) void ray_ce_bwd_kernel(
-    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ gt,
-    const float* __restrict__ tindex, const float* __restrict__ lse_in,
-    const float* __restrict__ grad_ce, float* __restrict__ grad_sigma, int R, VolDims v,
-    float step, int ncopies) {
-  ray_ce_bwd_body<true>(sigma, origin, gt, tindex, lse_in, grad_ce, grad_sigma, R, v, step, ncopies, kK);
-}
-__global__ __launch_bounds__(kThreads) void ray_ce_bwd_any_kernel(
-    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ gt,
-    const float* __restrict__ tindex, const float* __restrict__ lse_in,
-    const float* __restrict__ grad_ce, float* __restrict__ grad_sigma, int R, VolDims v,
-    float step, int ncopies, int K) {
-  ray_ce_bwd_body<false>(sigma, origin, gt, tindex, lse_in, grad_ce, grad_sigma, R, v, step, ncopies, K);
-}
-
 // ---------------------------------------------------------------------------------------------
-// dense rays: hard gumbel sample of the hit waypoint + straight-through "mass beyond" factor
+// hard gumbel sample of the hit entry + straight-through "mass beyond" factor (_custom_gumbel_softmax_distance)
+//   ray_gumbel: the K waypoints of the dense rays, noise [R, K]
+//   ray_dist:   the K + 1 entries {end point, K waypoints} of the GT rays (use_dist_loss, :575-585), noise [R, K + 1] in
+//               that order; entry 0 is the sample AT the end point with length |p - o|; also gt_len[r], valid[r]
 // aux[r] = {pred_dist, prob_next, lse}
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void ray_gumbel_fwd_kernel(
+template <bool K512, bool END_POINT>
+__device__ __forceinline__ void ray_sample_fwd_body(
     const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
-    const float* __restrict__ tindex, const float* __restrict__ noise, float* __restrict__ dist,
-    float* __restrict__ aux, int R, VolDims v, float step) {
-  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
-  if (r >= R) return;
-  const int lane = threadIdx.x % kWave;
-  const Ray ray = load_ray(origin, pts, tindex, r, v);
-  float o_dist = 0.f, o_pd = 0.f, o_pn = 0.f, o_lse = 0.f;
-  if (ray.f >= 0) {
-    const float* vol = sigma + (size_t)ray.f * v.Z * v.Y * v.X;
-    float f[kPerLane], len[kPerLane];
-    lane_logits(vol, ray, v, step, lane, f);
-    // arg-max of logits + gumbel noise (first index wins ties, like torch.max)
-    float best = kNegInf; int bi = kK; float blen = 0.f;
-    float m = kNegInf;
-#pragma unroll
-    for (int j = 0; j < kPerLane; ++j) {
-      const int k = lane + j * kWave;
-      float sx, sy, sz;
-      waypoint(ray, k, step, sx, sy, sz);
-      len[j] = dist_to(ray, sx, sy, sz);
-      const float z = f[j] + noise[(size_t)r * kK + k];
-      if (z > best || (z == best && k < bi)) { best = z; bi = k; blen = len[j]; }
-      m = fmaxf(m, f[j]);
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-      const float ob = __shfl_xor(best, s, kWave);
-      const int oi = __shfl_xor(bi, s, kWave);
-      const float ol = __shfl_xor(blen, s, kWave);
-      if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; blen = ol; }
-    }
-    m = wave_max(m);
-    const float pd = blen;
-    float se = 0.f, sn = 0.f;
-#pragma unroll
-    for (int j = 0; j < kPerLane; ++j) {
-      const float e = expf(f[j] - m);
-      se += e;
-      sn += (len[j] > pd) ? e : 0.f;
-    }
-    se = wave_sum(se); sn = wave_sum(sn);
-    const float pn = sn / se;
-    o_pd = pd; o_pn = pn; o_lse = m + logf(se);
-    o_dist = ((1.f - pn) + pn) * pd;
-  }
-  if (lane == 0) {
-    dist[r] = o_dist;
-    aux[(size_t)r * 3 + 0] = o_pd; aux[(size_t)r * 3 + 1] = o_pn; aux[(size_t)r * 3 + 2] = o_lse;
-  }
-}
-
-// streamed form, any K
-__global__ __launch_bounds__(kThreads) void ray_gumbel_fwd_any_kernel(
-    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
-    const float* __restrict__ tindex, const float* __restrict__ noise, float* __restrict__ dist,
-    float* __restrict__ aux, int R, VolDims v, float step, int K) {
-  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
-  if (r >= R) return;
-  const int lane = threadIdx.x % kWave;
-  const Ray ray = load_ray(origin, pts, tindex, r, v);
-  float o_dist = 0.f, o_pd = 0.f, o_pn = 0.f, o_lse = 0.f;
-  if (ray.f >= 0) {
-    const float* vol = sigma + (size_t)ray.f * v.Z * v.Y * v.X;
-    float best = kNegInf; int bi = kKMax; float blen = 0.f;
-    float m = kNegInf;
-    for (int k = lane; k < K; k += kWave) {
-      float len;
-      const float f = logit_at(vol, ray, v, step, k, len);
-      const float z = f + noise[(size_t)r * K + k];
-      if (z > best || (z == best && k < bi)) { best = z; bi = k; blen = len; }
-      m = fmaxf(m, f);
-    }
-    wave_argmax(best, bi, blen);
-    m = wave_max(m);
-    const float pd = blen;
-    float se = 0.f, sn = 0.f;
-    for (int k = lane; k < K; k += kWave) {
-      float len;
-      const float e = expf(logit_at(vol, ray, v, step, k, len) - m);
-      se += e;
-      sn += (len > pd) ? e : 0.f;
-    }
-    se = wave_sum(se); sn = wave_sum(sn);
-    const float pn = sn / se;
-    o_pd = pd; o_pn = pn; o_lse = m + logf(se);
-    o_dist = ((1.f - pn) + pn) * pd;
-  }
-  if (lane == 0) {
-    dist[r] = o_dist;
-    aux[(size_t)r * 3 + 0] = o_pd; aux[(size_t)r * 3 + 1] = o_pn; aux[(size_t)r * 3 + 2] = o_lse;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// GT rays: the same hard gumbel sample over the K + 1 logits {end point, K waypoints} (use_dist_loss, :575-585).
-// Entry 0 is the sample AT the end point with length |p - o| (lane 0 carries it), entries 1..K the waypoints;
-// noise [R, K + 1] in that order.  Rays are dropped as in ray_ce.  Streamed, any K.  aux[r] = {pred_dist, prob_next, lse}
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void ray_dist_fwd_kernel(
-    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ gt,
     const float* __restrict__ tindex, const float* __restrict__ noise, float* __restrict__ dist,
     float* __restrict__ gt_len, float* __restrict__ aux, float* __restrict__ valid, int R, VolDims v, float step,
     int K) {
   const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
   if (r >= R) return;
   const int lane = threadIdx.x % kWave;
-  const Ray ray = load_ray(origin, gt, tindex, r, v);
+  const Ray ray = load_ray(origin, pts, tindex, r, v);
   const Tri t0 = make_tri(ray.px, ray.py, ray.pz, v);
-  const bool ok = ray.f >= 0 && !t0.masked;
+  const bool ok = ray.f >= 0 && !(END_POINT && t0.masked);
   float o_dist = 0.f, o_len = 0.f, o_pd = 0.f, o_pn = 0.f, o_lse = 0.f;
   if (ok) {
     const float* vol = sigma + (size_t)ray.f * v.Z * v.Y * v.X;
-    const float* nz = noise + (size_t)r * ((size_t)K + 1);
-    const float f0 = tri_load(vol, t0);
-    const float len0 = dist_to(ray, ray.px, ray.py, ray.pz);
-    float best = kNegInf; int bi = kKMax + 1; float blen = 0.f;
-    if (lane == 0) { best = f0 + nz[0]; bi = 0; blen = len0; }
-    float m = f0;
-    for (int k = lane; k < K; k += kWave) {
-      float len;
-      const float f = logit_at(vol, ray, v, step, k, len);
-      const float z = f + nz[k + 1];
-      if (z > best || (z == best && k + 1 < bi)) { best = z; bi = k + 1; blen = len; }
-      m = fmaxf(m, f);
+    const float* nz = noise + (size_t)r * ((size_t)K + END_POINT);
+    Waypoints<K512, true> w{vol, ray, v, step, lane, K};
+    // arg-max of logits + gumbel noise
+    Best best;
+    float m = kNegInf, f0 = 0.f, len0 = 0.f;
+    if (END_POINT) {
+      m = f0 = tri_load(vol, t0);
+      len0 = dist_to(ray, ray.px, ray.py, ray.pz);
+      if (lane == 0) best = Best{f0 + nz[0], 0, len0};
     }
-    wave_argmax(best, bi, blen);
+    w.first([&](int k, float f, float len) {
+      best.take(f + nz[k + END_POINT], k + END_POINT, len);
+      m = fmaxf(m, f);
+    });
+    wave_argmax(best);
     m = wave_max(m);
-    const float pd = blen;
-    const float e0 = (lane == 0) ? expf(f0 - m) : 0.f;
+    const float pd = best.len;
+    const float e0 = (END_POINT && lane == 0) ? expf(f0 - m) : 0.f;
     float se = e0, sn = (len0 > pd) ? e0 : 0.f;
-    for (int k = lane; k < K; k += kWave) {
-      float len;
-      const float e = expf(logit_at(vol, ray, v, step, k, len) - m);
+    w.second([&](int, float f, float len) {
+      const float e = expf(f - m);
       se += e;
       sn += (len > pd) ? e : 0.f;
-    }
+    });
     se = wave_sum(se); sn = wave_sum(sn);
     const float pn = sn / se;
     o_pd = pd; o_pn = pn; o_lse = m + logf(se); o_len = len0;
     o_dist = ((1.f - pn) + pn) * pd;
   }
   if (lane == 0) {
-    dist[r] = o_dist; gt_len[r] = o_len; valid[r] = ok ? 1.f : 0.f;
+    dist[r] = o_dist;
     aux[(size_t)r * 3 + 0] = o_pd; aux[(size_t)r * 3 + 1] = o_pn; aux[(size_t)r * 3 + 2] = o_lse;
+    if (END_POINT) { gt_len[r] = o_len; valid[r] = ok ? 1.f : 0.f; }
   }
 }
 
-// d dist / d logit_k = pd * p_k * (ind_k - pn) on every live entry, the end point included
-__global__ __launch_bounds__(kThreads) void ray_dist_bwd_kernel(
-    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ gt,
-    const float* __restrict__ tindex, const float* __restrict__ aux, const float* __restrict__ grad_dist,
-    float* __restrict__ grad_sigma, int R, VolDims v, float step, int ncopies, int K) {
-  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
-  if (r >= R) return;
-  const int lane = threadIdx.x % kWave;
-  const float g = grad_dist[r];
-  if (g == 0.f) return;
-  const Ray ray = load_ray(origin, gt, tindex, r, v);
-  const Tri t0 = make_tri(ray.px, ray.py, ray.pz, v);
-  if (ray.f < 0 || t0.masked) return;
-  const size_t slice = (size_t)ray.f * v.Z * v.Y * v.X;
-  const float* vol = sigma + slice;
-  float* gvol = grad_sigma + (size_t)(blockIdx.x % ncopies) * v.F * v.Z * v.Y * v.X + slice;
-  const float pd = aux[(size_t)r * 3 + 0], pn = aux[(size_t)r * 3 + 1], lse = aux[(size_t)r * 3 + 2];
-  if (lane == 0) {
-    const float ind0 = dist_to(ray, ray.px, ray.py, ray.pz) > pd ? 1.f : 0.f;
-    tri_scatter(gvol, t0, g * pd * expf(tri_load(vol, t0) - lse) * (ind0 - pn));
-  }
-  const int cx = lane & 1;
-  const int passes = (K + kWave / 2 - 1) / (kWave / 2);
-  for (int j = 0; j < passes; ++j) {                   // 32 waypoints per pass, a lane pair per waypoint
-    const int k = (lane >> 1) + j * (kWave / 2);
-    if (k >= K) break;
-    float sx, sy, sz;
-    waypoint(ray, k, step, sx, sy, sz);
-    const Tri t = make_tri(sx, sy, sz, v);
-    if (t.masked) continue;
-    const float p = expf(tri_load(vol, t) - lse);
-    const float ind = dist_to(ray, sx, sy, sz) > pd ? 1.f : 0.f;
-    tri_scatter_x(gvol, t, g * pd * p * (ind - pn), cx);
-  }
-}
-
+// test-time decode (:697-731): arg-max waypoint -> distance
 template <bool K512>
-__device__ __forceinline__ void ray_gumbel_bwd_body(
-    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
-    const float* __restrict__ tindex, const float* __restrict__ aux,
-    const float* __restrict__ grad_dist, float* __restrict__ grad_sigma, int R, VolDims v,
-    float step, int ncopies, int K) {
-  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
-  if (r >= R) return;
-  const int lane = threadIdx.x % kWave;
-  const float g = grad_dist[r];
-  if (g == 0.f) return;
-  const Ray ray = load_ray(origin, pts, tindex, r, v);
-  if (ray.f < 0) return;
-  const size_t slice = (size_t)ray.f * v.Z * v.Y * v.X;
-  const float* vol = sigma + slice;
-  float* gvol = grad_sigma + (size_t)(blockIdx.x % ncopies) * v.F * v.Z * v.Y * v.X + slice;
-  const float pd = aux[(size_t)r * 3 + 0], pn = aux[(size_t)r * 3 + 1], lse = aux[(size_t)r * 3 + 2];
-  const int cx = lane & 1;
-  const int passes = K512 ? 2 * kPerLane : (K + kWave / 2 - 1) / (kWave / 2);
-  for (int j = 0; j < passes; ++j) {                   // 32 waypoints per pass, a lane pair per waypoint
-    const int k = (lane >> 1) + j * (kWave / 2);
-    if (!K512 && k >= K) break;                        // only in the last pass
-    float sx, sy, sz;
-    waypoint(ray, k, step, sx, sy, sz);
-    const Tri t = make_tri(sx, sy, sz, v);
-    if (t.masked) continue;
-    const float p = expf(tri_load(vol, t) - lse);
-    const float ind = dist_to(ray, sx, sy, sz) > pd ? 1.f : 0.f;
-    tri_scatter_x(gvol, t, g * pd * p * (ind - pn), cx);
-  }
-}
-__global__ __launch_bounds__(kThreads) void ray_gumbel_bwd_kernel(
-    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
-    const float* __restrict__ tindex, const float* __restrict__ aux,
-    const float* __restrict__ grad_dist, float* __restrict__ grad_sigma, int R, VolDims v,
-    float step, int ncopies) {
-  ray_gumbel_bwd_body<true>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, v, step, ncopies, kK);
-}
-__global__ __launch_bounds__(kThreads) void ray_gumbel_bwd_any_kernel(
-    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
-    const float* __restrict__ tindex, const float* __restrict__ aux,
-    const float* __restrict__ grad_dist, float* __restrict__ grad_sigma, int R, VolDims v,
-    float step, int ncopies, int K) {
-  ray_gumbel_bwd_body<false>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, v, step, ncopies, K);
-}
-
-// test-time decode: exact zeros are masked to -inf (:728), arg-max waypoint -> distance
-__global__ __launch_bounds__(kThreads) void ray_argmax_kernel(
-    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
-    const float* __restrict__ tindex, float* __restrict__ pred_dist, float* __restrict__ gt_dist,
-    int R, VolDims v, float step) {
-  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
-  if (r >= R) return;
-  const int lane = threadIdx.x % kWave;
-  const Ray ray = load_ray(origin, pts, tindex, r, v);
-  float o_pred = 0.f, o_gt = 0.f;
-  if (ray.f >= 0) {
-    const float* vol = sigma + (size_t)ray.f * v.Z * v.Y * v.X;
-    float best = kNegInf; int bi = kK; float blen = 0.f;
-#pragma unroll
-    for (int j = 0; j < kPerLane; ++j) {
-      const int k = lane + j * kWave;
-      float sx, sy, sz;
-      waypoint(ray, k, step, sx, sy, sz);
-      // the reference samples with plain zero padding here (no open-volume mask): outside -> 0 -> -inf
-      const Tri t = make_tri<false>(sx, sy, sz, v);
-      const float val = (sx == sx) ? tri_load(vol, t) : 0.f;
-      const float z = (val == 0.f) ? kNegInf : val;
-      const float l = dist_to(ray, sx, sy, sz);
-      if (z > best || (z == best && k < bi)) { best = z; bi = k; blen = l; }
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-      const float ob = __shfl_xor(best, s, kWave);
-      const int oi = __shfl_xor(bi, s, kWave);
-      const float ol = __shfl_xor(blen, s, kWave);
-      if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; blen = ol; }
-    }
-    o_pred = blen;
-    o_gt = dist_to(ray, ray.px, ray.py, ray.pz);
-  }
-  if (lane == 0) { pred_dist[r] = o_pred; gt_dist[r] = o_gt; }
-}
-
-// streamed form, any K
-__global__ __launch_bounds__(kThreads) void ray_argmax_any_kernel(
+__device__ __forceinline__ void ray_argmax_body(
     const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
     const float* __restrict__ tindex, float* __restrict__ pred_dist, float* __restrict__ gt_dist,
     int R, VolDims v, float step, int K) {
@@ -587,23 +329,136 @@ __global__ __launch_bounds__(kThreads) void ray_argmax_any_kernel(
   const Ray ray = load_ray(origin, pts, tindex, r, v);
   float o_pred = 0.f, o_gt = 0.f;
   if (ray.f >= 0) {
-    const float* vol = sigma + (size_t)ray.f * v.Z * v.Y * v.X;
-    float best = kNegInf; int bi = kKMax; float blen = 0.f;
-    for (int k = lane; k < K; k += kWave) {
-      float sx, sy, sz;
-      waypoint(ray, k, step, sx, sy, sz);
-      const Tri t = make_tri<false>(sx, sy, sz, v);
-      const float val = (sx == sx) ? tri_load(vol, t) : 0.f;
-      const float z = (val == 0.f) ? kNegInf : val;
-      const float l = dist_to(ray, sx, sy, sz);
-      if (z > best || (z == best && k < bi)) { best = z; bi = k; blen = l; }
-    }
-    wave_argmax(best, bi, blen);
-    o_pred = blen;
+    Waypoints<K512, false> w{sigma + (size_t)ray.f * v.Z * v.Y * v.X, ray, v, step, lane, K};
+    Best best;
+    w.first([&](int k, float z, float len) { best.take(z, k, len); });
+    wave_argmax(best);
+    o_pred = best.len;
     o_gt = dist_to(ray, ray.px, ray.py, ray.pz);
   }
   if (lane == 0) { pred_dist[r] = o_pred; gt_dist[r] = o_gt; }
 }
+
+// ---------------------------------------------------------------------------------------------
+// The backwards: d loss / d logit of every live entry, scattered through the entry's trilinear weights.
+// A Coef is built from what the forward saved for ray r and gives g * d loss_r / d logit of an entry with softmax
+// probability p = exp(logit - lse) and length len; `target` marks the cross-entropy label (the end point).
+// ---------------------------------------------------------------------------------------------
+struct CeCoef {       // saved: lse [R]
+  float lse;
+  __device__ __forceinline__ CeCoef(const float* __restrict__ saved, int r) : lse(saved[r]) {}
+  __device__ __forceinline__ float operator()(float g, float p, float, bool target) const {
+    return target ? g * (p - 1.f) : g * p;
+  }
+};
+struct SampleCoef {   // saved: aux [R, 3]; d dist / d logit = pd * p * (ind - pn) on every entry, the end point included
+  float pd, pn, lse;
+  __device__ __forceinline__ SampleCoef(const float* __restrict__ saved, int r)
+      : pd(saved[(size_t)r * 3 + 0]), pn(saved[(size_t)r * 3 + 1]), lse(saved[(size_t)r * 3 + 2]) {}
+  __device__ __forceinline__ float operator()(float g, float p, float len, bool) const {
+    const float ind = len > pd ? 1.f : 0.f;
+    return g * pd * p * (ind - pn);
+  }
+};
+
+// K512: the fixed 16 passes of the register form's K; otherwise ceil(K / 32) passes with a tail predicate.
+// The adds go into private copies of the volume (scatter_copies.h).  (Leaving the 512-waypoint loop after the run of
+// live waypoints -- the waypoints inside the volume are ONE run of consecutive k, tests/test_ray_early_exit_cpu.py --
+// was measured too: no change, the masked passes cost almost nothing next to the atomics; removed.)
+template <bool K512, bool END_POINT, class Coef>
+__device__ __forceinline__ void ray_bwd_body(
+    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
+    const float* __restrict__ tindex, const float* __restrict__ saved, const float* __restrict__ grad,
+    float* __restrict__ grad_sigma, int R, VolDims v, float step, int ncopies, int K) {
+  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
+  if (r >= R) return;
+  const int lane = threadIdx.x % kWave;
+  const float g = grad[r];
+  if (g == 0.f) return;
+  const Ray ray = load_ray(origin, pts, tindex, r, v);
+  const Tri t0 = make_tri(ray.px, ray.py, ray.pz, v);
+  if (ray.f < 0 || (END_POINT && t0.masked)) return;
+  const size_t slice = (size_t)ray.f * v.Z * v.Y * v.X;
+  const float* vol = sigma + slice;
+  float* gvol = grad_sigma + scatter_copy_of_block(ncopies) * v.F * v.Z * v.Y * v.X + slice;
+  const Coef coef(saved, r);
+  if (END_POINT && lane == 0)
+    tri_scatter(gvol, t0, coef(g, expf(tri_load(vol, t0) - coef.lse), dist_to(ray, ray.px, ray.py, ray.pz), true));
+  const int cx = lane & 1;
+  const int passes = K512 ? 2 * kPerLane : (K + kWave / 2 - 1) / (kWave / 2);
+  for (int j = 0; j < passes; ++j) {                   // 32 waypoints per pass, a lane pair per waypoint
+    const int k = (lane >> 1) + j * (kWave / 2);
+    if (!K512 && k >= K) break;                        // only in the last pass
+    float sx, sy, sz;
+    waypoint(ray, k, step, sx, sy, sz);
+    const Tri t = make_tri(sx, sy, sz, v);
+    if (t.masked) continue;
+    tri_scatter_x(gvol, t, coef(g, expf(tri_load(vol, t) - coef.lse), dist_to(ray, sx, sy, sz), false), cx);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The kernels: one instantiation of a body each.  The ones without a suffix are the register form (K == kK);
+// ray_dist runs the streamed form for every K.
+// ---------------------------------------------------------------------------------------------
+#define RAY_IN const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts, \
+               const float* __restrict__ tindex
+#define RAY_KERNEL __global__ __launch_bounds__(kThreads) void
+
+RAY_KERNEL ray_ce_fwd_kernel(RAY_IN, float* __restrict__ ce, float* __restrict__ lse, float* __restrict__ valid, int R,
+                             VolDims v, float step) {
+  ray_ce_fwd_body<true>(sigma, origin, pts, tindex, ce, lse, valid, R, v, step, kK);
+}
+RAY_KERNEL ray_ce_fwd_any_kernel(RAY_IN, float* __restrict__ ce, float* __restrict__ lse, float* __restrict__ valid,
+                                 int R, VolDims v, float step, int K) {
+  ray_ce_fwd_body<false>(sigma, origin, pts, tindex, ce, lse, valid, R, v, step, K);
+}
+RAY_KERNEL ray_ce_bwd_kernel(RAY_IN, const float* __restrict__ lse, const float* __restrict__ grad_ce,
+                             float* __restrict__ grad_sigma, int R, VolDims v, float step, int ncopies) {
+  ray_bwd_body<true, true, CeCoef>(sigma, origin, pts, tindex, lse, grad_ce, grad_sigma, R, v, step, ncopies, kK);
+}
+RAY_KERNEL ray_ce_bwd_any_kernel(RAY_IN, const float* __restrict__ lse, const float* __restrict__ grad_ce,
+                                 float* __restrict__ grad_sigma, int R, VolDims v, float step, int ncopies, int K) {
+  ray_bwd_body<false, true, CeCoef>(sigma, origin, pts, tindex, lse, grad_ce, grad_sigma, R, v, step, ncopies, K);
+}
+
+RAY_KERNEL ray_gumbel_fwd_kernel(RAY_IN, const float* __restrict__ noise, float* __restrict__ dist,
+                                 float* __restrict__ aux, int R, VolDims v, float step) {
+  ray_sample_fwd_body<true, false>(sigma, origin, pts, tindex, noise, dist, nullptr, aux, nullptr, R, v, step, kK);
+}
+RAY_KERNEL ray_gumbel_fwd_any_kernel(RAY_IN, const float* __restrict__ noise, float* __restrict__ dist,
+                                     float* __restrict__ aux, int R, VolDims v, float step, int K) {
+  ray_sample_fwd_body<false, false>(sigma, origin, pts, tindex, noise, dist, nullptr, aux, nullptr, R, v, step, K);
+}
+RAY_KERNEL ray_gumbel_bwd_kernel(RAY_IN, const float* __restrict__ aux, const float* __restrict__ grad_dist,
+                                 float* __restrict__ grad_sigma, int R, VolDims v, float step, int ncopies) {
+  ray_bwd_body<true, false, SampleCoef>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, v, step, ncopies, kK);
+}
+RAY_KERNEL ray_gumbel_bwd_any_kernel(RAY_IN, const float* __restrict__ aux, const float* __restrict__ grad_dist,
+                                     float* __restrict__ grad_sigma, int R, VolDims v, float step, int ncopies, int K) {
+  ray_bwd_body<false, false, SampleCoef>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, v, step, ncopies, K);
+}
+
+RAY_KERNEL ray_dist_fwd_kernel(RAY_IN, const float* __restrict__ noise, float* __restrict__ dist,
+                               float* __restrict__ gt_len, float* __restrict__ aux, float* __restrict__ valid, int R,
+                               VolDims v, float step, int K) {
+  ray_sample_fwd_body<false, true>(sigma, origin, pts, tindex, noise, dist, gt_len, aux, valid, R, v, step, K);
+}
+RAY_KERNEL ray_dist_bwd_kernel(RAY_IN, const float* __restrict__ aux, const float* __restrict__ grad_dist,
+                               float* __restrict__ grad_sigma, int R, VolDims v, float step, int ncopies, int K) {
+  ray_bwd_body<false, true, SampleCoef>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, v, step, ncopies, K);
+}
+
+RAY_KERNEL ray_argmax_kernel(RAY_IN, float* __restrict__ pred_dist, float* __restrict__ gt_dist, int R, VolDims v,
+                             float step) {
+  ray_argmax_body<true>(sigma, origin, pts, tindex, pred_dist, gt_dist, R, v, step, kK);
+}
+RAY_KERNEL ray_argmax_any_kernel(RAY_IN, float* __restrict__ pred_dist, float* __restrict__ gt_dist, int R, VolDims v,
+                                 float step, int K) {
+  ray_argmax_body<false>(sigma, origin, pts, tindex, pred_dist, gt_dist, R, v, step, K);
+}
+#undef RAY_KERNEL
+#undef RAY_IN
 
 inline bool rm_bad(int F, int R, int Z, int Y, int X, int K) {
   return F <= 0 || R < 0 || Z <= 0 || Y <= 0 || X <= 0 || K < 1 || K > kKMax;
@@ -611,25 +466,24 @@ inline bool rm_bad(int F, int R, int Z, int Y, int X, int K) {
 std::atomic<int> g_force_streamed{0};   // vidar_ray_force_streamed
 inline bool rm_k512(int K) { return K == kK && !g_force_streamed.load(std::memory_order_relaxed); }
 inline dim3 rm_grid(int R) { return dim3((R + kRaysPerBlock - 1) / kRaysPerBlock); }
+inline size_t rm_cells(const VolDims& v) { return (size_t)v.F * v.Z * v.Y * v.X; }
 
-}  // namespace
-
-namespace {
-__global__ __launch_bounds__(256) void ray_sum_copies_kernel(const float* __restrict__ copies, float* __restrict__ out,
-                                                             size_t n) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  float a = copies[i];
-  for (int c = 1; c < kRayCopies; ++c) a += copies[(size_t)c * n + i];
-  out[i] = a;
+// launch `k512` (register form) or `any` (streamed, takes K as its last argument) on a wave per ray
+template <class K512Kernel, class AnyKernel, class... Args>
+inline void rm_launch(K512Kernel k512, AnyKernel any, int R, int K, hipStream_t s, Args... args) {
+  if (rm_k512(K))
+    hipLaunchKernelGGL(k512, rm_grid(R), dim3(kThreads), 0, s, args...);
+  else
+    hipLaunchKernelGGL(any, rm_grid(R), dim3(kThreads), 0, s, args..., K);
 }
+
 }  // namespace
 
 extern "C" {
 
 size_t vidar_ray_bwd_workspace_bytes(int F, int Z, int Y, int X) {
   if (F <= 0 || Z <= 0 || Y <= 0 || X <= 0) return 0;
-  return sizeof(float) * (size_t)F * Z * Y * X * kRayCopies;
+  return scatter_workspace_bytes(rm_cells(VolDims{F, Z, Y, X}), 1);
 }
 
 int vidar_ray_max_k(void) { return kKMax; }
@@ -645,38 +499,12 @@ int vidar_ray_ce_fwd_f32(const float* sigma, const float* origin, const float* g
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   if (R == 0) return 0;
   VolDims v{F, Z, Y, X};
-  if (rm_k512(K))
-    hipLaunchKernelGGL(ray_ce_fwd_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream, sigma,
-                       origin, gt_pts, tindex, ce, lse, valid, R, v, step);
-  else
-    hipLaunchKernelGGL(ray_ce_fwd_any_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream, sigma,
-                       origin, gt_pts, tindex, ce, lse, valid, R, v, step, K);
+  rm_launch(ray_ce_fwd_kernel, ray_ce_fwd_any_kernel, R, K, (hipStream_t)stream, sigma, origin, gt_pts, tindex, ce, lse,
+            valid, R, v, step);
   return vidar_last_error();
 }
 
-}  // extern "C"
-
-namespace {
-// the shared shell of the three backward entries: zero the accumulator (private copies if the workspace is big enough),
-// launch, sum the copies
-template <class Launch>
-int rm_backward(float* grad_sigma, int F, int R, int Z, int Y, int X, void* workspace, size_t workspace_bytes,
-                hipStream_t s, Launch launch) {
-  const size_t n = (size_t)F * Z * Y * X;
-  const bool copies = workspace != nullptr && workspace_bytes >= vidar_ray_bwd_workspace_bytes(F, Z, Y, X);
-  float* acc = copies ? (float*)workspace : grad_sigma;
-  hipError_t e = hipMemsetAsync(acc, 0, sizeof(float) * n * (copies ? kRayCopies : 1), s);
-  if (e != hipSuccess) return (int)e;
-  if (R == 0) return copies ? (int)hipMemsetAsync(grad_sigma, 0, sizeof(float) * n, s) : 0;
-  launch(acc, copies ? kRayCopies : 1);
-  if (copies)
-    hipLaunchKernelGGL(ray_sum_copies_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, acc, grad_sigma, n);
-  return vidar_last_error();
-}
-}  // namespace
-
-extern "C" {
-
+// the three backwards: private copies of grad_sigma if the workspace allows (scatter_copies.h); R == 0 leaves zeros
 int vidar_ray_ce_bwd_f32(const float* sigma, const float* origin, const float* gt_pts,
                          const float* tindex, const float* lse, const float* grad_ce,
                          float* grad_sigma, int F, int R, int Z, int Y, int X, int K, float step,
@@ -685,13 +513,10 @@ int vidar_ray_ce_bwd_f32(const float* sigma, const float* origin, const float* g
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   VolDims v{F, Z, Y, X};
-  return rm_backward(grad_sigma, F, R, Z, Y, X, workspace, workspace_bytes, s, [&](float* acc, int ncopies) {
-    if (rm_k512(K))
-      hipLaunchKernelGGL(ray_ce_bwd_kernel, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, gt_pts, tindex, lse,
-                         grad_ce, acc, R, v, step, ncopies);
-    else
-      hipLaunchKernelGGL(ray_ce_bwd_any_kernel, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, gt_pts, tindex, lse,
-                         grad_ce, acc, R, v, step, ncopies, K);
+  return scatter_with_copies(grad_sigma, nullptr, rm_cells(v), R == 0, workspace, workspace_bytes, s,
+                             [&](float* acc, float*, int ncopies) {
+    rm_launch(ray_ce_bwd_kernel, ray_ce_bwd_any_kernel, R, K, s, sigma, origin, gt_pts, tindex, lse, grad_ce, acc, R, v,
+              step, ncopies);
   });
 }
 
@@ -702,12 +527,8 @@ int vidar_ray_gumbel_fwd_f32(const float* sigma, const float* origin, const floa
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   if (R == 0) return 0;
   VolDims v{F, Z, Y, X};
-  if (rm_k512(K))
-    hipLaunchKernelGGL(ray_gumbel_fwd_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream,
-                       sigma, origin, pts, tindex, noise, dist, aux, R, v, step);
-  else
-    hipLaunchKernelGGL(ray_gumbel_fwd_any_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream,
-                       sigma, origin, pts, tindex, noise, dist, aux, R, v, step, K);
+  rm_launch(ray_gumbel_fwd_kernel, ray_gumbel_fwd_any_kernel, R, K, (hipStream_t)stream, sigma, origin, pts, tindex,
+            noise, dist, aux, R, v, step);
   return vidar_last_error();
 }
 
@@ -719,13 +540,10 @@ int vidar_ray_gumbel_bwd_f32(const float* sigma, const float* origin, const floa
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   VolDims v{F, Z, Y, X};
-  return rm_backward(grad_sigma, F, R, Z, Y, X, workspace, workspace_bytes, s, [&](float* acc, int ncopies) {
-    if (rm_k512(K))
-      hipLaunchKernelGGL(ray_gumbel_bwd_kernel, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, pts, tindex, aux,
-                         grad_dist, acc, R, v, step, ncopies);
-    else
-      hipLaunchKernelGGL(ray_gumbel_bwd_any_kernel, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, pts, tindex, aux,
-                         grad_dist, acc, R, v, step, ncopies, K);
+  return scatter_with_copies(grad_sigma, nullptr, rm_cells(v), R == 0, workspace, workspace_bytes, s,
+                             [&](float* acc, float*, int ncopies) {
+    rm_launch(ray_gumbel_bwd_kernel, ray_gumbel_bwd_any_kernel, R, K, s, sigma, origin, pts, tindex, aux, grad_dist, acc,
+              R, v, step, ncopies);
   });
 }
 
@@ -749,7 +567,8 @@ int vidar_ray_dist_bwd_f32(const float* sigma, const float* origin, const float*
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   VolDims v{F, Z, Y, X};
-  return rm_backward(grad_sigma, F, R, Z, Y, X, workspace, workspace_bytes, s, [&](float* acc, int ncopies) {
+  return scatter_with_copies(grad_sigma, nullptr, rm_cells(v), R == 0, workspace, workspace_bytes, s,
+                             [&](float* acc, float*, int ncopies) {
     hipLaunchKernelGGL(ray_dist_bwd_kernel, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, gt_pts, tindex, aux,
                        grad_dist, acc, R, v, step, ncopies, K);
   });
@@ -762,12 +581,8 @@ int vidar_ray_argmax_f32(const float* sigma, const float* origin, const float* p
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   if (R == 0) return 0;
   VolDims v{F, Z, Y, X};
-  if (rm_k512(K))
-    hipLaunchKernelGGL(ray_argmax_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream, sigma,
-                       origin, pts, tindex, pred_dist, gt_dist, R, v, step);
-  else
-    hipLaunchKernelGGL(ray_argmax_any_kernel, rm_grid(R), dim3(kThreads), 0, (hipStream_t)stream, sigma,
-                       origin, pts, tindex, pred_dist, gt_dist, R, v, step, K);
+  rm_launch(ray_argmax_kernel, ray_argmax_any_kernel, R, K, (hipStream_t)stream, sigma, origin, pts, tindex, pred_dist,
+            gt_dist, R, v, step);
   return vidar_last_error();
 }
 
