@@ -273,13 +273,17 @@ int vidar_sca_combine_f32(const float* src, const int32_t* slot_of, const float*
 /* ---------------------------------------------------------------------------
  * LatentRendering ray-march (fused).  Replaces the torch op chain of
  * projects/mmdet3d_plugin/bevformer/modules/ray_operations/latent_rendering.py:96-150.
- * All maps are channel-last [bs, H*W, Z] f32 with Z == 16 (pred_height == embed_dims/reduction).
+ * All maps are channel-last f32: [bs, H*W, Z] for the Z = pred_height height bins, 1 <= Z <= 64, and [bs, H*W, A] for
+ * the A = embed_dims/reduction LoRA channels, A = Z*J <= 256; LoRA channel ch belongs to bin ch / J (:148-150).
  * step = grid_step / (min(H,W)//2) rounded to f32 (:102-104); act: 0 = 'sigmoid', 1 = 'exp' (:117-123).
  *   prob   : occ logits -> path_prob = prod_{k<G,valid}(1 - act(occ(n_k))) * act(occ(n_cell))   (:96-129)
  *   gather : feat = sum_k a(n_k) m_k / (sum_k m_k + eps), m_k = path_prob(n_k)*valid2_k          (:131-150)
+ *            lora_a, feat and their gradients have A channels, path_prob, msum and grad_path_prob Z; the entries
+ *            without `grouped` are the case A == Z.  Any other Z or A: VIDAR_ERR_BAD_ARG, nothing is launched.
  * Backward entry points zero their gradient outputs and accumulate with fp32 atomics; `workspace`
  * (vidar_latent_render_bwd_workspace_bytes, caller-owned scratch, 16-byte aligned) holds 8 private copies of the
- * gradient maps as for the ray ops below, NULL = add straight into the outputs.
+ * gradient maps as for the ray ops below, NULL = add straight into the outputs.  The grouped backward's two maps differ
+ * in size: its workspace is vidar_latent_render_bwd_workspace_bytes(bs, H, W, max(Z, A), 2).
  * ------------------------------------------------------------------------- */
 size_t vidar_latent_render_bwd_workspace_bytes(int bs, int H, int W, int Z, int maps /* 1: prob_bwd, 2: gather_bwd */);
 int vidar_latent_render_prob_fwd_f32(const float* occ, float* path_prob, int bs, int H, int W, int Z,
@@ -295,6 +299,14 @@ int vidar_latent_render_gather_bwd_f32(const float* path_prob, const float* lora
                                        float* grad_path_prob, float* grad_lora_a, int bs, int H,
                                        int W, int Z, int grid_num, float step, float eps,
                                        void* workspace, size_t workspace_bytes, void* stream);
+int vidar_latent_render_gather_grouped_fwd_f32(const float* path_prob, const float* lora_a, float* feat, float* msum,
+                                               int bs, int H, int W, int Z, int A, int grid_num, float step,
+                                               float eps, void* stream);
+int vidar_latent_render_gather_grouped_bwd_f32(const float* path_prob, const float* lora_a, const float* feat,
+                                               const float* msum, const float* grad_feat, float* grad_path_prob,
+                                               float* grad_lora_a, int bs, int H, int W, int Z, int A, int grid_num,
+                                               float step, float eps, void* workspace, size_t workspace_bytes,
+                                               void* stream);
 
 /* ---------------------------------------------------------------------------
  * ViDAR head ray-march over the predicted occupancy volume (fused).  Replaces the torch op chains

@@ -333,24 +333,72 @@ def bench_norm(which):
         report(f"drop_add_ln bwd {name}", ms, 4 * nb)
 
 
+def _lr_geometry(H, W, G, step, dev):
+    """waypoints of every cell's ray in [-1, 1] (the cell itself last), their lengths and the border bound"""
+    ys, xs = torch.meshgrid((torch.arange(H, device=dev) + 0.5) / H, (torch.arange(W, device=dev) + 0.5) / W, indexing="ij")
+    grids = torch.stack((xs.reshape(-1), ys.reshape(-1)), -1)[None]
+    r = grids - 0.5
+    rn = torch.nan_to_num(r / r.norm(dim=-1, keepdim=True))
+    steps = (torch.arange(G, device=dev) + 0.5) * (step / (min(H, W) // 2))
+    path = torch.cat([0.5 + rn[:, :, None] * steps.view(1, 1, -1, 1), grids[:, :, None]], 2) * 2 - 1
+    bound = torch.minimum(1 / rn[..., 0:1].abs(), 1 / rn[..., 1:2].abs())
+    return path, path.norm(dim=-1, keepdim=True), bound
+
+
+def _lr_torch(occ, a, G, step):
+    """the op chain the two kernels replace, through F.grid_sample on the GPU: occ [1,H,W,Z], a [1,H,W,A] -> prob, feat"""
+    import torch.nn.functional as F
+    bs, H, W, Z = occ.shape
+    A = a.shape[-1]
+    path, length, bound = _lr_geometry(H, W, G, step, occ.device)
+    p = torch.sigmoid(F.grid_sample(occ.permute(0, 3, 1, 2), path, align_corners=False).permute(0, 2, 3, 1))
+    trans = torch.cumprod(1 - p * (length < length[..., -1:, :]), dim=2)
+    prob = (trans[..., -1, :] * p[..., -1, :]).view(bs, H, W, Z)
+    path = path[..., :-1, :].contiguous()
+    av = F.grid_sample(a.permute(0, 3, 1, 2), path, align_corners=False).view(bs, Z, A // Z, H * W, G)
+    m = F.grid_sample(prob.permute(0, 3, 1, 2), path, align_corners=False) * (length[..., :-1, 0] < bound).view(bs, 1, H * W, G)
+    m = (m / (m.sum(-1, keepdim=True) + 1e-3)).view(bs, Z, 1, H * W, G)
+    return prob, (av * m).sum(-1).view(bs, A, H * W).permute(0, 2, 1).reshape(bs, H, W, A)
+
+
 def bench_lr(which):
+    """the four LatentRendering kernels at 200 x 200, 256 waypoints: the released 16 bins / 16 LoRA channels first (the
+    rows every earlier log has), then other (Z, A) with the same chain through F.grid_sample next to them.  Algorithmic
+    bytes: every map read or written once (Z floats per cell for occ / prob / msum and their gradients, A for a / feat)."""
     from vidar_amd.plugin.modules.ray_operations.latent_rendering import _PathProb, _RayGather
-    for step in (1.0, 0.5):
-        occ = torch.randn(1, 200, 200, 16, device="cuda", requires_grad=True)
-        a = torch.randn(1, 200, 200, 16, device="cuda", requires_grad=True)
-        Q = 40000
-        ms = timeit(lambda: _PathProb.apply(occ, 256, step, 0))
-        report(f"lr_prob_fwd step={step}", ms, 4 * Q * 32)
+    Q = 40000
+
+    def rows(Z, A, step, tag="", it=10):
+        occ = torch.randn(1, 200, 200, Z, device="cuda", requires_grad=True)
+        a = torch.randn(1, 200, 200, A, device="cuda", requires_grad=True)
+        ms = timeit(lambda: _PathProb.apply(occ, 256, step, 0), it=it)
+        report(f"lr_prob_fwd{tag} step={step}", ms, 4 * Q * 2 * Z)
         p = _PathProb.apply(occ, 256, step, 0)
         g = torch.randn_like(p)
-        ms = timeit(lambda: torch.autograd.grad(p, occ, g, retain_graph=True))
-        report(f"lr_prob_bwd step={step}", ms, 4 * Q * 48)
+        ms = timeit(lambda: torch.autograd.grad(p, occ, g, retain_graph=True), it=it)
+        report(f"lr_prob_bwd{tag} step={step}", ms, 4 * Q * 3 * Z)
         pd = p.detach().requires_grad_(True)
-        ms = timeit(lambda: _RayGather.apply(pd, a, 256, step, 1e-3))
-        report(f"lr_gather_fwd step={step}", ms, 4 * Q * 64)
+        ms = timeit(lambda: _RayGather.apply(pd, a, 256, step, 1e-3), it=it)
+        report(f"lr_gather_fwd{tag} step={step}", ms, 4 * Q * (2 * Z + 2 * A))
         f = _RayGather.apply(pd, a, 256, step, 1e-3)
-        ms = timeit(lambda: torch.autograd.grad(f, [pd, a], g, retain_graph=True))
-        report(f"lr_gather_bwd step={step}", ms, 4 * Q * 112)
+        ga = torch.randn_like(f)
+        ms = timeit(lambda: torch.autograd.grad(f, [pd, a], ga, retain_graph=True), it=it)
+        report(f"lr_gather_bwd{tag} step={step}", ms, 4 * Q * (3 * Z + 4 * A))
+        return occ, a, g, ga
+
+    for step in (1.0, 0.5):
+        rows(16, 16, step)
+    for Z, A in ((1, 16), (4, 16), (32, 32), (16, 64)):
+        for step in (1.0, 0.5):
+            occ, a, g, ga = rows(Z, A, step, f" Z={Z} A={A}", it=20)
+            fwd_bytes, bwd_bytes = 4 * Q * (4 * Z + 2 * A), 4 * Q * (6 * Z + 4 * A)
+            ms = timeit(lambda: _lr_torch(occ.detach(), a.detach(), 256, step), warm=1, it=3)
+            report(f"lr fwd (both stages) grid_sample Z={Z} A={A} step={step}", ms, fwd_bytes)
+            prob, feat = _lr_torch(occ, a, 256, step)
+            ms = timeit(lambda: torch.autograd.grad([prob, feat], [occ, a], [g, ga], retain_graph=True), warm=1, it=3)
+            report(f"lr bwd (both stages) grid_sample Z={Z} A={A} step={step}", ms, bwd_bytes)
+            del prob, feat
+            torch.cuda.empty_cache()
 
 
 def bench_ray(which):

@@ -87,6 +87,8 @@ _ABI = {
     "vidar_latent_render_prob_bwd_f32": "i 3p 5i f i p z p",
     "vidar_latent_render_gather_fwd_f32": "i 4p 5i 2f p",
     "vidar_latent_render_gather_bwd_f32": "i 7p 5i 2f p z p",
+    "vidar_latent_render_gather_grouped_fwd_f32": "i 4p 6i 2f p",
+    "vidar_latent_render_gather_grouped_bwd_f32": "i 7p 6i 2f p z p",
     "vidar_ray_bwd_workspace_bytes": "z 4i",
     "vidar_ray_ce_fwd_f32": "i 7p 6i f p",
     "vidar_ray_ce_bwd_f32": "i 7p 6i f p z p",

@@ -44,9 +44,11 @@ VARIANTS = {
 }
 
 
-def _latent_render(step):
-    return dict(embed_dims=DIM, pred_height=16, num_pred_fcs=0, grid_step=step, grid_num=256,
-                reduction=16, act="sigmoid")
+def _latent_render(step, override=None):
+    """the released LatentRendering entry (16 height bins, 16 LoRA channels); `override`: constructor arguments to
+    replace, e.g. dict(pred_height=4) or dict(reduction=8, pred_height=32)"""
+    return dict(dict(embed_dims=DIM, pred_height=16, num_pred_fcs=0, grid_step=step, grid_num=256,
+                     reduction=16, act="sigmoid"), **(override or {}))
 
 
 # InternImage-T / -S / -B as the image backbone (`with_backbone="internimage_t"` ...): the released model sizes, the three
@@ -58,9 +60,9 @@ INTERNIMAGE = {
 }
 
 
-def model_config(name, bev_h=200, bev_w=200, with_backbone=False):
+def model_config(name, bev_h=200, bev_w=200, with_backbone=False, latent_render=None):
     v = VARIANTS[name]
-    lr = _latent_render(v["lr_step"])
+    lr = _latent_render(v["lr_step"], latent_render)
     pos = dict(type="LearnedPositionalEncoding", num_feats=DIM // 2, row_num_embed=bev_h,
                col_num_embed=bev_w)
     pred_attn = dict(type="PredictionMSDeformableAttention", embed_dims=DIM, num_levels=1)
@@ -144,16 +146,16 @@ CLASS_NAMES = ("car", "truck", "construction_vehicle", "bus", "trailer", "barrie
                "traffic_cone")
 
 
-def finetune_model_config(name, bev_h=200, bev_w=200, with_backbone=False, num_query=900):
+def finetune_model_config(name, bev_h=200, bev_w=200, with_backbone=False, num_query=900, latent_render=None):
     """model dict of a detection fine-tune recipe: the encoder half of `model_config(pretrain)` (LatentRendering step of
     the fine-tune file), a 6-layer DetectionTransformerDecoder, focal / L1 losses and the Hungarian assigner."""
     f = FINETUNE[name]
-    base = model_config(f["pretrain"], bev_h, bev_w, with_backbone)
+    base = model_config(f["pretrain"], bev_h, bev_w, with_backbone, latent_render)
     src = base["pts_bbox_head"]
     transformer = dict(src["transformer"])
     transformer.pop("num_cams", None)                         # the fine-tune files leave the default (6)
     enc = transformer["encoder"]
-    enc["transformerlayers"]["latent_render"] = _latent_render(f["lr_step"])
+    enc["transformerlayers"]["latent_render"] = _latent_render(f["lr_step"], latent_render)
     enc["transformerlayers"]["attn_cfgs"][1].pop("num_cams", None)
     transformer.pop("rotate_center", None)
     if (bev_h, bev_w) != (200, 200):
@@ -186,11 +188,14 @@ def finetune_model_config(name, bev_h=200, bev_w=200, with_backbone=False, num_q
     return model
 
 
-def get_config(name, bev_h=200, bev_w=200, with_backbone=False):
+def get_config(name, bev_h=200, bev_w=200, with_backbone=False, latent_render=None):
+    """`latent_render`: constructor arguments of LatentRendering that replace the released ones (pred_height, reduction,
+    num_pred_fcs, ...) in the encoder layers and, where the recipe has them, the future-decoder layers."""
     if name in FINETUNE:
         f = FINETUNE[name]
-        out = get_config(f["pretrain"], bev_h, bev_w, with_backbone)
-        out.update(name=name, model=finetune_model_config(name, bev_h, bev_w, with_backbone), task="detection",
+        out = get_config(f["pretrain"], bev_h, bev_w, with_backbone, latent_render)
+        out.update(name=name, model=finetune_model_config(name, bev_h, bev_w, with_backbone, latent_render=latent_render),
+                   task="detection",
                    class_names=CLASS_NAMES, load_from=f"work_dirs/{f['pretrain']}/latest.pth",
                    work_dir=f"work_dirs/fine-tune/{f['pretrain']}")
         out["queue_length"] = 3          # the detection dataset's queue_length 4 counts the current frame: 3 history frames
@@ -198,7 +203,7 @@ def get_config(name, bev_h=200, bev_w=200, with_backbone=False):
     v = VARIANTS[name]
     h, w = v["img_hw"]
     shapes = [((h // s) + (1 if h % s else 0), (w // s) + (1 if w % s else 0)) for s in (8, 16, 32, 64)]
-    return dict(name=name, model=model_config(name, bev_h, bev_w, with_backbone), queue_length=4,
+    return dict(name=name, model=model_config(name, bev_h, bev_w, with_backbone, latent_render), queue_length=4,
                 future_frames=v["future_frames"], num_cams=v["cams"], img_hw=v["img_hw"],
                 fpn_shapes=shapes, optimizer=dict(lr=2e-4, weight_decay=0.01), grad_clip=35.0,
                 data=dict(samples_per_gpu=1, workers_per_gpu=4, **v["data"]))

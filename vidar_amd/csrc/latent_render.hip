@@ -9,18 +9,23 @@
 //   stage 2 (":131-150")  feat[b,q,z]      = sum_k a(n_k) m_k / (sum_k m_k + eps),  m_k = path_prob(n_k) [|n_k| < bound_q]
 // where n_k = 2 * rhat_q * (k + 0.5) * step are the G waypoints of the ray from the BEV centre
 // through cell q (normalised [-1,1] coordinates), sampled bilinearly with zero padding and
-// align_corners=False, and z runs over the 16 height bins (= the 16 LoRA channels).
+// align_corners=False.  z runs over the Z = pred_height height bins (1 .. 64); stage 2 carries A = Z * J <= 256 LoRA
+// channels and weights channel ch with the path probability of bin ch / J (the reference's view(bs, pred_height, -1, ..)).
 //
-// Layout in HBM: all maps are channel-last [bs, h*w, 16] f32 -- exactly what the producing
-// nn.Linear emits -- so one bilinear corner of all 16 bins is one 64-byte segment.
-// Mapping: one wave per BEV cell; lane = (k mod 16, quarter of the 16 bins as a float4); the ray is
-// walked 16 waypoints per iteration and reduced over the 16 k-lanes with xor shuffles.  Cells are
+// Layout in HBM: all maps are channel-last [bs, h*w, Z or A] f32 -- exactly what the producing
+// nn.Linear emits -- so one bilinear corner of all channels is one contiguous segment (64 bytes at 16 channels).
+// Mapping: one wave per BEV cell; forward lane = (waypoint slot, float4 of channels) -- at 16 channels (k mod 16,
+// quarter of the 16 bins) -- the ray is walked 64 / (channel lanes) waypoints per iteration and reduced over the
+// waypoint slots with xor shuffles.  Rows that are no multiple of 4 floats take one channel per lane.  Cells are
 // assigned to workgroups in row-major order, 4 cells per 256-thread workgroup.
 // Backward kernels recompute the forward samples and scatter with fp32 hardware atomics, with the
-// lane map (waypoint k mod 4, height bin) so that one atomic instruction covers a corner's 64 bytes.
+// lane map (waypoint slot, channel) -- at 16 channels (k mod 4, height bin) -- so that one atomic instruction covers a
+// corner's contiguous bytes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+
+#include <type_traits>
 
 #include "vidar_hip.h"
 #include "vidar_common.h"
@@ -28,14 +33,15 @@
 
 namespace {
 
-constexpr int kZ = 16;
+constexpr int kMaxZ = 64;    // height bins
+constexpr int kMaxA = 256;   // LoRA channels
 constexpr int kThreads = 256;
 constexpr int kCellsPerBlock = kThreads / 64;
 
 // Every ray starts at the BEV centre, so the first waypoints of all H*W rays scatter onto the same few cells: the
 // backward kernels add into private copies of the gradient maps (scatter_copies.h; the kernels were serialised on the
 // hot addresses, not bound by the atomic rate).
-// which private copy this workgroup adds into, as an offset in maps of [bs, Q, 16] (0 when the variant is off)
+// which private copy this workgroup adds into, as an offset in units of [Q, channels] maps (0 when the variant is off)
 __device__ __forceinline__ size_t copy_of_block(int ncopies) { return scatter_copy_of_block(ncopies) * gridDim.y; }
 
 struct Geo {
@@ -90,16 +96,67 @@ __device__ __forceinline__ Tap make_tap(float nx, float ny, const Geo& g) {
   return t;
 }
 
-__device__ __forceinline__ float4 tap_load(const float* __restrict__ map, const Tap& t, int zq) {
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+// V channels of one lane: V = 4 is read and written as one float4 (rows of a multiple of 4 floats), V = 1 as a scalar
+template <int V>
+struct Vec {
+  float e[V];
+};
+template <int V>
+__device__ __forceinline__ Vec<V> vec_fill(float x) {
+  Vec<V> v;
+#pragma unroll
+  for (int i = 0; i < V; ++i) v.e[i] = x;
+  return v;
+}
+template <int V>
+__device__ __forceinline__ Vec<V> vec_load(const float* __restrict__ p) {
+  Vec<V> v;
+  if constexpr (V == 4) {
+    const float4 f = *reinterpret_cast<const float4*>(p);
+    v.e[0] = f.x; v.e[1] = f.y; v.e[2] = f.z; v.e[3] = f.w;
+  } else {
+    v.e[0] = *p;
+  }
+  return v;
+}
+template <int V>
+__device__ __forceinline__ void vec_store(float* __restrict__ p, const Vec<V>& v) {
+  if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v.e[0], v.e[1], v.e[2], v.e[3]);
+  else *p = v.e[0];
+}
+
+// bilinear sample of channels ch .. ch+V-1 of a channel-last map with C channels
+template <int V>
+__device__ __forceinline__ Vec<V> tap_load(const float* __restrict__ map, const Tap& t, int C, int ch) {
+  Vec<V> acc = vec_fill<V>(0.f);
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     if (t.o[c] >= 0) {
-      const float4 v = *reinterpret_cast<const float4*>(map + (size_t)t.o[c] * kZ + zq * 4);
-      acc.x += t.w[c] * v.x; acc.y += t.w[c] * v.y; acc.z += t.w[c] * v.z; acc.w += t.w[c] * v.w;
+      const Vec<V> v = vec_load<V>(map + (size_t)t.o[c] * C + ch);
+#pragma unroll
+      for (int i = 0; i < V; ++i) acc.e[i] += t.w[c] * v.e[i];
     }
   }
   return acc;
+}
+__device__ __forceinline__ void tap_scatter1(float* __restrict__ map, const Tap& t, int C, int ch, float g) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+    if (t.o[c] >= 0) unsafeAtomicAdd(map + (size_t)t.o[c] * C + ch, t.w[c] * g);
+}
+// stage 2: the path probability that weights LoRA channels ch .. ch+V-1, i.e. of the bins (ch+i) / J
+template <int V>
+__device__ __forceinline__ Vec<V> tap_load_bins(const float* __restrict__ pm, const Tap& t, int Z, int ch, int J) {
+  if (J == 1) return tap_load<V>(pm, t, Z, ch);
+  Vec<V> m;
+  int prev = -1;
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    const int bin = (ch + i) / J;
+    m.e[i] = (i > 0 && bin == prev) ? m.e[i > 0 ? i - 1 : 0] : tap_load<1>(pm, t, Z, bin).e[0];
+    prev = bin;
+  }
+  return m;
 }
 
 __device__ __forceinline__ float act_f(float x, int act) {
@@ -111,45 +168,37 @@ __device__ __forceinline__ float act_d(float x, float p, int act) {
   if (act == 0) return p * (1.f - p);
   return x > 0.f ? (1.f - p) : 0.f;
 }
-__device__ __forceinline__ float4 act4(const float4& v, int act) {
-  return make_float4(act_f(v.x, act), act_f(v.y, act), act_f(v.z, act), act_f(v.w, act));
-}
 
-// reduce over the 16 k-lanes (lane bits 2..5); every lane ends with the full result
-__device__ __forceinline__ float4 kprod(float4 v) {
+// Lane map of every kernel: lane = (waypoint slot, channel lane); LPW = lanes per waypoint, 1 / 4 / 16 / 64, that covers
+// the channels (or 64 with a loop over channel chunks), the remaining 64 / LPW lane bits walk the ray.
+// reduce over the waypoint slots (lane bits log2(LPW) .. 5); every lane ends with the full result
+template <int LPW, int V>
+__device__ __forceinline__ Vec<V> kprod(Vec<V> v) {
 #pragma unroll
-  for (int m = 4; m < 64; m <<= 1) {
-    v.x *= __shfl_xor(v.x, m, 64); v.y *= __shfl_xor(v.y, m, 64);
-    v.z *= __shfl_xor(v.z, m, 64); v.w *= __shfl_xor(v.w, m, 64);
+  for (int m = LPW; m < 64; m <<= 1) {
+#pragma unroll
+    for (int i = 0; i < V; ++i) v.e[i] *= __shfl_xor(v.e[i], m, 64);
   }
   return v;
 }
-__device__ __forceinline__ float4 ksum(float4 v) {
+template <int LPW, int V>
+__device__ __forceinline__ Vec<V> ksum(Vec<V> v) {
 #pragma unroll
-  for (int m = 4; m < 64; m <<= 1) {
-    v.x += __shfl_xor(v.x, m, 64); v.y += __shfl_xor(v.y, m, 64);
-    v.z += __shfl_xor(v.z, m, 64); v.w += __shfl_xor(v.w, m, 64);
+  for (int m = LPW; m < 64; m <<= 1) {
+#pragma unroll
+    for (int i = 0; i < V; ++i) v.e[i] += __shfl_xor(v.e[i], m, 64);
   }
   return v;
 }
-
-
-// ---- backward mapping: lane = (waypoint k mod 4, height bin z): one atomic instruction covers the
-// ---- 64 contiguous bytes of a tap corner (atomics cost per instruction x line, see msda.hip) ------
-__device__ __forceinline__ float tap_load1(const float* __restrict__ map, const Tap& t, int z) {
-  float acc = 0.f;
+// stage 2 backward: sum over the lanes of this waypoint slot that follow in the same height bin (`ahead` of them, a
+// contiguous run), so that the first lane of a bin holds the bin's sum.  Every lane of the slot takes part.
+template <int LPW>
+__device__ __forceinline__ float group_sum(float v, int ahead) {
 #pragma unroll
-  for (int c = 0; c < 4; ++c)
-    if (t.o[c] >= 0) acc += t.w[c] * map[(size_t)t.o[c] * kZ + z];
-  return acc;
-}
-__device__ __forceinline__ void tap_scatter1(float* __restrict__ map, const Tap& t, int z, float g) {
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-    if (t.o[c] >= 0) unsafeAtomicAdd(map + (size_t)t.o[c] * kZ + z, t.w[c] * g);
-}
-__device__ __forceinline__ float kprod1(float v) {
-  v *= __shfl_xor(v, 16, 64); v *= __shfl_xor(v, 32, 64);
+  for (int d = 1; d < LPW; d <<= 1) {
+    const float o = __shfl_down(v, d, 64);
+    if (d <= ahead) v += o;
+  }
   return v;
 }
 
@@ -162,144 +211,302 @@ __device__ __forceinline__ void waypoint(const Cell& c, const Geo& g, int k, flo
 }
 
 // ---------------------------------------------------------------------------------------------
-// stage 1 forward: occ [bs,Q,16] -> path_prob [bs,Q,16]
+// All four kernel bodies: one wave per BEV cell.  ZC != 0 states the channel counts at compile time (the released 16 / 16
+// shape); ZC == 0 takes them from the launch.  Channel lanes past the channel count neither load nor scatter.
+// stage 1 forward: occ [bs,Q,Z] -> path_prob [bs,Q,Z]; lane = (waypoint slot, V bins)
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void lr_prob_fwd_kernel(const float* __restrict__ occ,
-                                                               float* __restrict__ prob, int Q,
-                                                               Geo g) {
+template <int LPW, int V, int ZC>
+__device__ __forceinline__ void lr_prob_fwd(const float* __restrict__ occ, float* __restrict__ prob, int Q, int Zr,
+                                            const Geo& g) {
+  const int Z = ZC ? ZC : Zr;
   const int b = blockIdx.y;
   const int q = blockIdx.x * kCellsPerBlock + threadIdx.x / 64;
   if (q >= Q) return;
-  const int lane = threadIdx.x & 63, zq = lane & 3, ks = lane >> 2;
-  const float* map = occ + (size_t)b * Q * kZ;
+  const int lane = threadIdx.x & 63, z = (lane & (LPW - 1)) * V, ks = lane / LPW;
+  const bool on = z < Z;
+  const float* map = occ + (size_t)b * Q * Z;
   const Cell c = make_cell(q, g);
-  float4 pr = make_float4(1.f, 1.f, 1.f, 1.f);
-  for (int k = ks; k < g.G; k += 16) {
+  Vec<V> pr = vec_fill<V>(1.f);
+  for (int k = ks; k < g.G; k += 64 / LPW) {
     float nx, ny, len;
     waypoint(c, g, k, nx, ny, len);
-    if (len < c.len_c) {
-      const float4 p = act4(tap_load(map, make_tap(nx, ny, g), zq), g.act);
-      pr.x *= 1.f - p.x; pr.y *= 1.f - p.y; pr.z *= 1.f - p.z; pr.w *= 1.f - p.w;
+    if (len < c.len_c && on) {
+      const Vec<V> x = tap_load<V>(map, make_tap(nx, ny, g), Z, z);
+#pragma unroll
+      for (int i = 0; i < V; ++i) pr.e[i] *= 1.f - act_f(x.e[i], g.act);
     }
   }
-  pr = kprod(pr);
-  if (ks == 0) {
-    const float4 pc = act4(tap_load(map, make_tap(c.ncx, c.ncy, g), zq), g.act);
-    *reinterpret_cast<float4*>(prob + ((size_t)b * Q + q) * kZ + zq * 4) =
-        make_float4(pr.x * pc.x, pr.y * pc.y, pr.z * pc.z, pr.w * pc.w);
+  pr = kprod<LPW>(pr);
+  if (ks == 0 && on) {
+    const Vec<V> xc = tap_load<V>(map, make_tap(c.ncx, c.ncy, g), Z, z);
+    Vec<V> out;
+#pragma unroll
+    for (int i = 0; i < V; ++i) out.e[i] = pr.e[i] * act_f(xc.e[i], g.act);
+    vec_store<V>(prob + ((size_t)b * Q + q) * Z + z, out);
   }
 }
 
-// stage 1 backward: grad_prob [bs,Q,16] -> grad_occ [bs,Q,16] (pre-zeroed, atomics)
-__global__ __launch_bounds__(kThreads) void lr_prob_bwd_kernel(const float* __restrict__ occ,
-                                                               const float* __restrict__ grad_prob,
-                                                               float* __restrict__ grad_occ, int Q,
-                                                               Geo g, int ncopies) {
+// stage 1 backward: grad_prob [bs,Q,Z] -> grad_occ [bs,Q,Z] (pre-zeroed, atomics); lane = (waypoint slot, bin): one
+// atomic instruction covers the contiguous bytes of a tap corner (atomics cost per instruction x line, see msda.hip)
+template <int LPW, int ZC>
+__device__ __forceinline__ void lr_prob_bwd(const float* __restrict__ occ, const float* __restrict__ grad_prob,
+                                            float* __restrict__ grad_occ, int Q, int Zr, const Geo& g, int ncopies) {
+  const int Z = ZC ? ZC : Zr;
   const int b = blockIdx.y;
   const int q = blockIdx.x * kCellsPerBlock + threadIdx.x / 64;
   if (q >= Q) return;
-  const int lane = threadIdx.x & 63, z = lane & 15, ks = lane >> 4;
-  const float* map = occ + (size_t)b * Q * kZ;
-  float* gmap = grad_occ + (copy_of_block(ncopies) + b) * Q * kZ;
+  const int lane = threadIdx.x & 63, z = lane & (LPW - 1), ks = lane / LPW;
+  const bool on = z < Z;
+  const float* map = occ + (size_t)b * Q * Z;
+  float* gmap = grad_occ + (copy_of_block(ncopies) + b) * Q * Z;
   const Cell c = make_cell(q, g);
   // pass 1: the transmittance product
-  float pr = 1.f;
-  for (int k = ks; k < g.G; k += 4) {
+  Vec<1> pr = vec_fill<1>(1.f);
+  for (int k = ks; k < g.G; k += 64 / LPW) {
     float nx, ny, len;
     waypoint(c, g, k, nx, ny, len);
-    if (len < c.len_c) pr *= 1.f - act_f(tap_load1(map, make_tap(nx, ny, g), z), g.act);
+    if (len < c.len_c && on) pr.e[0] *= 1.f - act_f(tap_load<1>(map, make_tap(nx, ny, g), Z, z).e[0], g.act);
   }
-  pr = kprod1(pr);
+  pr = kprod<LPW>(pr);
+  if (!on) return;
   const Tap tc = make_tap(c.ncx, c.ncy, g);
-  const float xc = tap_load1(map, tc, z);
+  const float xc = tap_load<1>(map, tc, Z, z).e[0];
   const float pc = act_f(xc, g.act);
-  const float go = grad_prob[((size_t)b * Q + q) * kZ + z];
+  const float go = grad_prob[((size_t)b * Q + q) * Z + z];
   // d/d(1-p_k) of prod * pc  = prod/(1-p_k) * pc ; guarded against (1-p_k) == 0
-  const float gp = go * pr * pc;
-  for (int k = ks; k < g.G; k += 4) {
+  const float gp = go * pr.e[0] * pc;
+  for (int k = ks; k < g.G; k += 64 / LPW) {
     float nx, ny, len;
     waypoint(c, g, k, nx, ny, len);
     if (len < c.len_c) {
       const Tap t = make_tap(nx, ny, g);
-      const float x = tap_load1(map, t, z);
+      const float x = tap_load<1>(map, t, Z, z).e[0];
       const float p = act_f(x, g.act);
       const float gs = (1.f - p) > 0.f ? -gp / (1.f - p) * act_d(x, p, g.act) : 0.f;
-      tap_scatter1(gmap, t, z, gs);
+      tap_scatter1(gmap, t, Z, z, gs);
     }
   }
-  if (ks == 0) tap_scatter1(gmap, tc, z, go * pr * act_d(xc, pc, g.act));
+  if (ks == 0) tap_scatter1(gmap, tc, Z, z, go * pr.e[0] * act_d(xc, pc, g.act));
 }
 
 // ---------------------------------------------------------------------------------------------
-// stage 2 forward: prob [bs,Q,16], a [bs,Q,16] -> feat [bs,Q,16], msum [bs,Q,16] (= sum_k m_k)
+// stage 2 forward: prob [bs,Q,Z], a [bs,Q,A] -> feat [bs,Q,A], msum [bs,Q,Z] (= sum_k m_k); A = Z * J and LoRA
+// channel ch is weighted by bin ch / J.  lane = (waypoint slot, V channels); A > LPW * V is walked in chunks.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void lr_gather_fwd_kernel(const float* __restrict__ prob,
-                                                                 const float* __restrict__ a,
-                                                                 float* __restrict__ feat,
-                                                                 float* __restrict__ msum, int Q,
-                                                                 Geo g) {
+template <int LPW, int V, int ZC>
+__device__ __forceinline__ void lr_gather_fwd(const float* __restrict__ prob, const float* __restrict__ a,
+                                              float* __restrict__ feat, float* __restrict__ msum, int Q, int Zr, int Ar,
+                                              const Geo& g) {
+  const int Z = ZC ? ZC : Zr, A = ZC ? ZC : Ar, J = ZC ? 1 : Ar / Zr;
   const int b = blockIdx.y;
   const int q = blockIdx.x * kCellsPerBlock + threadIdx.x / 64;
   if (q >= Q) return;
-  const int lane = threadIdx.x & 63, zq = lane & 3, ks = lane >> 2;
-  const float* pm = prob + (size_t)b * Q * kZ;
-  const float* am = a + (size_t)b * Q * kZ;
+  const int lane = threadIdx.x & 63, cl = (lane & (LPW - 1)) * V, ks = lane / LPW;
+  const float* pm = prob + (size_t)b * Q * Z;
+  const float* am = a + (size_t)b * Q * A;
   const Cell c = make_cell(q, g);
-  float4 M = make_float4(0.f, 0.f, 0.f, 0.f), Nn = M;
-  for (int k = ks; k < g.G; k += 16) {
-    float nx, ny, len;
-    waypoint(c, g, k, nx, ny, len);
-    if (len < c.bound) {
-      const Tap t = make_tap(nx, ny, g);
-      const float4 m = tap_load(pm, t, zq);
-      const float4 av = tap_load(am, t, zq);
-      M.x += m.x; M.y += m.y; M.z += m.z; M.w += m.w;
-      Nn.x += av.x * m.x; Nn.y += av.y * m.y; Nn.z += av.z * m.z; Nn.w += av.w * m.w;
+  for (int c0 = 0; c0 < A; c0 += LPW * V) {
+    const int ch = c0 + cl;
+    const bool on = ch < A;
+    Vec<V> M = vec_fill<V>(0.f), Nn = M;
+    for (int k = ks; k < g.G; k += 64 / LPW) {
+      float nx, ny, len;
+      waypoint(c, g, k, nx, ny, len);
+      if (len < c.bound && on) {
+        const Tap t = make_tap(nx, ny, g);
+        const Vec<V> m = tap_load_bins<V>(pm, t, Z, ch, J);
+        const Vec<V> av = tap_load<V>(am, t, A, ch);
+#pragma unroll
+        for (int i = 0; i < V; ++i) { M.e[i] += m.e[i]; Nn.e[i] += av.e[i] * m.e[i]; }
+      }
     }
-  }
-  M = ksum(M); Nn = ksum(Nn);
-  if (ks == 0) {
-    const size_t o = ((size_t)b * Q + q) * kZ + zq * 4;
-    *reinterpret_cast<float4*>(feat + o) = make_float4(Nn.x / (M.x + g.eps), Nn.y / (M.y + g.eps),
-                                                       Nn.z / (M.z + g.eps), Nn.w / (M.w + g.eps));
-    *reinterpret_cast<float4*>(msum + o) = M;
+    M = ksum<LPW>(M); Nn = ksum<LPW>(Nn);
+    if (ks == 0 && on) {
+      Vec<V> f;
+#pragma unroll
+      for (int i = 0; i < V; ++i) f.e[i] = Nn.e[i] / (M.e[i] + g.eps);
+      vec_store<V>(feat + ((size_t)b * Q + q) * A + ch, f);
+      float* mrow = msum + ((size_t)b * Q + q) * Z;
+      if (J == 1) {
+        vec_store<V>(mrow + ch, M);
+      } else {
+#pragma unroll
+        for (int i = 0; i < V; ++i)
+          if ((ch + i) % J == 0) mrow[(ch + i) / J] = M.e[i];
+      }
+    }
   }
 }
 
-// stage 2 backward: grad_feat -> grad_prob, grad_a (pre-zeroed, atomics)
+// stage 2 backward: grad_feat [bs,Q,A] -> grad_prob [bs,Q,Z], grad_a [bs,Q,A] (pre-zeroed, atomics); lane = (waypoint
+// slot, channel), A > LPW is walked in chunks.  grad_prob of a bin is summed over the bin's channels inside the wave
+// and added by the bin's first lane of the chunk.
+template <int LPW, int ZC>
+__device__ __forceinline__ void lr_gather_bwd(
+    const float* __restrict__ prob, const float* __restrict__ a, const float* __restrict__ feat,
+    const float* __restrict__ msum, const float* __restrict__ grad_feat,
+    float* __restrict__ grad_prob, float* __restrict__ grad_a, int Q, int Zr, int Ar, const Geo& g, int ncopies) {
+  const int Z = ZC ? ZC : Zr, A = ZC ? ZC : Ar, J = ZC ? 1 : Ar / Zr;
+  const int b = blockIdx.y;
+  const int q = blockIdx.x * kCellsPerBlock + threadIdx.x / 64;
+  if (q >= Q) return;
+  const int lane = threadIdx.x & 63, cl = lane & (LPW - 1), ks = lane / LPW;
+  const float* pm = prob + (size_t)b * Q * Z;
+  const float* am = a + (size_t)b * Q * A;
+  float* gpm = grad_prob + (copy_of_block(ncopies) + b) * Q * Z;
+  float* gam = grad_a + (copy_of_block(ncopies) + b) * Q * A;
+  const Cell c = make_cell(q, g);
+  for (int c0 = 0; c0 < A; c0 += LPW) {
+    const int ch = c0 + cl;
+    const bool on = ch < A;
+    const int bin = on ? ch / J : 0;
+    // lanes after this one in the same slot, chunk and bin; the lane that adds the bin's sum
+    const int ahead = on ? min(min(J - 1 - ch % J, LPW - 1 - cl), A - 1 - ch) : 0;
+    const bool first = on && (cl == 0 || ch % J == 0);
+    const float f = on ? feat[((size_t)b * Q + q) * A + ch] : 0.f;
+    const float s = on ? grad_feat[((size_t)b * Q + q) * A + ch] / (msum[((size_t)b * Q + q) * Z + bin] + g.eps) : 0.f;
+    for (int k = ks; k < g.G; k += 64 / LPW) {
+      float nx, ny, len;
+      waypoint(c, g, k, nx, ny, len);
+      if (len < c.bound) {
+        const Tap t = make_tap(nx, ny, g);
+        float gp = 0.f;
+        if (on) {
+          const float m = tap_load<1>(pm, t, Z, bin).e[0];
+          const float av = tap_load<1>(am, t, A, ch).e[0];
+          tap_scatter1(gam, t, A, ch, s * m);
+          gp = s * (av - f);
+        }
+        if (J > 1) gp = group_sum<LPW>(gp, ahead);
+        if (first) tap_scatter1(gpm, t, Z, bin, gp);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The kernels: the released shape under the names it has always had, every other shape as `_any`
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void lr_prob_fwd_kernel(const float* __restrict__ occ, float* __restrict__ prob,
+                                                               int Q, Geo g) {
+  lr_prob_fwd<4, 4, 16>(occ, prob, Q, 16, g);
+}
+__global__ __launch_bounds__(kThreads) void lr_prob_bwd_kernel(const float* __restrict__ occ,
+                                                               const float* __restrict__ grad_prob,
+                                                               float* __restrict__ grad_occ, int Q, Geo g, int ncopies) {
+  lr_prob_bwd<16, 16>(occ, grad_prob, grad_occ, Q, 16, g, ncopies);
+}
+__global__ __launch_bounds__(kThreads) void lr_gather_fwd_kernel(const float* __restrict__ prob,
+                                                                 const float* __restrict__ a, float* __restrict__ feat,
+                                                                 float* __restrict__ msum, int Q, Geo g) {
+  lr_gather_fwd<4, 4, 16>(prob, a, feat, msum, Q, 16, 16, g);
+}
 __global__ __launch_bounds__(kThreads) void lr_gather_bwd_kernel(
     const float* __restrict__ prob, const float* __restrict__ a, const float* __restrict__ feat,
     const float* __restrict__ msum, const float* __restrict__ grad_feat,
     float* __restrict__ grad_prob, float* __restrict__ grad_a, int Q, Geo g, int ncopies) {
-  const int b = blockIdx.y;
-  const int q = blockIdx.x * kCellsPerBlock + threadIdx.x / 64;
-  if (q >= Q) return;
-  const int lane = threadIdx.x & 63, z = lane & 15, ks = lane >> 4;
-  const float* pm = prob + (size_t)b * Q * kZ;
-  const float* am = a + (size_t)b * Q * kZ;
-  float* gpm = grad_prob + (copy_of_block(ncopies) + b) * Q * kZ;
-  float* gam = grad_a + (copy_of_block(ncopies) + b) * Q * kZ;
-  const Cell c = make_cell(q, g);
-  const size_t o = ((size_t)b * Q + q) * kZ + z;
-  const float f = feat[o];
-  const float s = grad_feat[o] / (msum[o] + g.eps);
-  for (int k = ks; k < g.G; k += 4) {
-    float nx, ny, len;
-    waypoint(c, g, k, nx, ny, len);
-    if (len < c.bound) {
-      const Tap t = make_tap(nx, ny, g);
-      const float m = tap_load1(pm, t, z);
-      const float av = tap_load1(am, t, z);
-      tap_scatter1(gam, t, z, s * m);
-      tap_scatter1(gpm, t, z, s * (av - f));
-    }
-  }
+  lr_gather_bwd<16, 16>(prob, a, feat, msum, grad_feat, grad_prob, grad_a, Q, 16, 16, g, ncopies);
+}
+template <int LPW, int V>
+__global__ __launch_bounds__(kThreads) void lr_prob_fwd_any_kernel(const float* __restrict__ occ,
+                                                                   float* __restrict__ prob, int Q, int Z, Geo g) {
+  lr_prob_fwd<LPW, V, 0>(occ, prob, Q, Z, g);
+}
+template <int LPW>
+__global__ __launch_bounds__(kThreads) void lr_prob_bwd_any_kernel(const float* __restrict__ occ,
+                                                                   const float* __restrict__ grad_prob,
+                                                                   float* __restrict__ grad_occ, int Q, int Z, Geo g,
+                                                                   int ncopies) {
+  lr_prob_bwd<LPW, 0>(occ, grad_prob, grad_occ, Q, Z, g, ncopies);
+}
+template <int LPW, int V>
+__global__ __launch_bounds__(kThreads) void lr_gather_fwd_any_kernel(const float* __restrict__ prob,
+                                                                     const float* __restrict__ a,
+                                                                     float* __restrict__ feat, float* __restrict__ msum,
+                                                                     int Q, int Z, int A, Geo g) {
+  lr_gather_fwd<LPW, V, 0>(prob, a, feat, msum, Q, Z, A, g);
+}
+template <int LPW>
+__global__ __launch_bounds__(kThreads) void lr_gather_bwd_any_kernel(
+    const float* __restrict__ prob, const float* __restrict__ a, const float* __restrict__ feat,
+    const float* __restrict__ msum, const float* __restrict__ grad_feat,
+    float* __restrict__ grad_prob, float* __restrict__ grad_a, int Q, int Z, int A, Geo g, int ncopies) {
+  lr_gather_bwd<LPW, 0>(prob, a, feat, msum, grad_feat, grad_prob, grad_a, Q, Z, A, g, ncopies);
 }
 
 inline bool lr_bad(int bs, int H, int W, int Z, int G, int act) {
-  return bs < 0 || H <= 0 || W <= 0 || Z != kZ || G <= 0 || (act != 0 && act != 1);
+  return bs < 0 || H <= 0 || W <= 0 || Z < 1 || Z > kMaxZ || G <= 0 || (act != 0 && act != 1);
 }
+inline bool lr_bad_group(int Z, int A) { return A < Z || A % Z != 0 || A > kMaxA; }
 inline dim3 lr_grid(int bs, int Q) { return dim3((Q + kCellsPerBlock - 1) / kCellsPerBlock, bs); }
+
+// the channel lanes per waypoint for n channels (or float4s of channels), as a compile-time constant for `f`: 1, 4, 16 or
+// 64 -- the smallest that covers n, so at most 3/4 of the channel lanes idle; n > 64 is walked in chunks of 64
+template <class F>
+void with_lanes(int n, F f) {
+  if (n <= 1) f(std::integral_constant<int, 1>{});
+  else if (n <= 4) f(std::integral_constant<int, 4>{});
+  else if (n <= 16) f(std::integral_constant<int, 16>{});
+  else f(std::integral_constant<int, 64>{});
+}
+template <class K, class... Args>
+void lr_launch(K kernel, int bs, int Q, hipStream_t s, Args... args) {
+  hipLaunchKernelGGL(kernel, lr_grid(bs, Q), dim3(kThreads), 0, s, args...);
+}
+
+// The released shape (Z = A = 16) runs the instantiation with its counts compiled in; every other shape picks the lane
+// map from its channel count: float4 lanes where the rows are a multiple of 4 floats, scalar lanes otherwise.
+void launch_prob_fwd(const float* occ, float* prob, int bs, int H, int W, int Z, Geo g, hipStream_t s) {
+  const int Q = H * W;
+  if (Z == 16) lr_launch(lr_prob_fwd_kernel, bs, Q, s, occ, prob, Q, g);
+  else if (Z % 4 == 0)
+    with_lanes(Z / 4, [&](auto l) { lr_launch(lr_prob_fwd_any_kernel<decltype(l)::value, 4>, bs, Q, s, occ, prob, Q, Z, g); });
+  else
+    with_lanes(Z, [&](auto l) { lr_launch(lr_prob_fwd_any_kernel<decltype(l)::value, 1>, bs, Q, s, occ, prob, Q, Z, g); });
+}
+void launch_prob_bwd(const float* occ, const float* go, float* acc, int bs, int H, int W, int Z, Geo g, int ncopies,
+                     hipStream_t s) {
+  const int Q = H * W;
+  if (Z == 16) lr_launch(lr_prob_bwd_kernel, bs, Q, s, occ, go, acc, Q, g, ncopies);
+  else
+    with_lanes(Z, [&](auto l) {
+      lr_launch(lr_prob_bwd_any_kernel<decltype(l)::value>, bs, Q, s, occ, go, acc, Q, Z, g, ncopies);
+    });
+}
+void launch_gather_fwd(const float* prob, const float* a, float* feat, float* msum, int bs, int H, int W, int Z, int A,
+                       Geo g, hipStream_t s) {
+  const int Q = H * W;
+  if (Z == 16 && A == 16) lr_launch(lr_gather_fwd_kernel, bs, Q, s, prob, a, feat, msum, Q, g);
+  else if (A % 4 == 0)
+    with_lanes(A / 4, [&](auto l) {
+      lr_launch(lr_gather_fwd_any_kernel<decltype(l)::value, 4>, bs, Q, s, prob, a, feat, msum, Q, Z, A, g);
+    });
+  else
+    with_lanes(A, [&](auto l) {
+      lr_launch(lr_gather_fwd_any_kernel<decltype(l)::value, 1>, bs, Q, s, prob, a, feat, msum, Q, Z, A, g);
+    });
+}
+
+// The two gradient maps of the stage 2 backward differ in size (Z and A channels); the copies are summed as float4
+// where both sizes allow it.
+int gather_bwd(const float* prob, const float* a, const float* feat, const float* msum, const float* grad_feat,
+               float* grad_prob, float* grad_a, int bs, int H, int W, int Z, int A, Geo g, void* workspace,
+               size_t workspace_bytes, hipStream_t s) {
+  const size_t nz = (size_t)bs * H * W * Z, na = (size_t)bs * H * W * A;
+  const int Q = H * W;
+  const auto launch = [&](float* sp, float* sa, int ncopies) {
+    if (Z == 16 && A == 16)
+      lr_launch(lr_gather_bwd_kernel, bs, Q, s, prob, a, feat, msum, grad_feat, sp, sa, Q, g, ncopies);
+    else
+      with_lanes(A, [&](auto l) {
+        lr_launch(lr_gather_bwd_any_kernel<decltype(l)::value>, bs, Q, s, prob, a, feat, msum, grad_feat, sp, sa, Q, Z, A,
+                  g, ncopies);
+      });
+  };
+  if ((nz | na) % 4 == 0)
+    return scatter_with_copies<float4>(grad_prob, grad_a, nz, na, false, workspace, workspace_bytes, s, launch);
+  return scatter_with_copies<float>(grad_prob, grad_a, nz, na, false, workspace, workspace_bytes, s, launch);
+}
 
 }  // namespace
 
@@ -315,9 +522,7 @@ int vidar_latent_render_prob_fwd_f32(const float* occ, float* path_prob, int bs,
   VIDAR_ENTER();
   if (lr_bad(bs, H, W, Z, grid_num, act)) return VIDAR_ERR_BAD_ARG;
   if (bs == 0) return 0;
-  Geo g{H, W, grid_num, step, act, 0.f};
-  hipLaunchKernelGGL(lr_prob_fwd_kernel, lr_grid(bs, H * W), dim3(kThreads), 0, (hipStream_t)stream,
-                     occ, path_prob, H * W, g);
+  launch_prob_fwd(occ, path_prob, bs, H, W, Z, Geo{H, W, grid_num, step, act, 0.f}, (hipStream_t)stream);
   return vidar_last_error();
 }
 
@@ -329,23 +534,42 @@ int vidar_latent_render_prob_bwd_f32(const float* occ, const float* grad_path_pr
   if (bs == 0) return 0;   // before anything is touched
   hipStream_t s = (hipStream_t)stream;
   Geo g{H, W, grid_num, step, act, 0.f};
-  return scatter_with_copies<float4>(grad_occ, nullptr, (size_t)bs * H * W * Z, false, workspace, workspace_bytes, s,
-                                     [&](float* acc, float*, int ncopies) {
-    hipLaunchKernelGGL(lr_prob_bwd_kernel, lr_grid(bs, H * W), dim3(kThreads), 0, s, occ, grad_path_prob, acc, H * W, g,
-                       ncopies);
-  });
+  const size_t n = (size_t)bs * H * W * Z;
+  const auto launch = [&](float* acc, float*, int ncopies) {
+    launch_prob_bwd(occ, grad_path_prob, acc, bs, H, W, Z, g, ncopies, s);
+  };
+  if (n % 4 == 0) return scatter_with_copies<float4>(grad_occ, nullptr, n, false, workspace, workspace_bytes, s, launch);
+  return scatter_with_copies<float>(grad_occ, nullptr, n, false, workspace, workspace_bytes, s, launch);
+}
+
+int vidar_latent_render_gather_grouped_fwd_f32(const float* path_prob, const float* lora_a, float* feat, float* msum,
+                                               int bs, int H, int W, int Z, int A, int grid_num, float step,
+                                               float eps, void* stream) {
+  VIDAR_ENTER();
+  if (lr_bad(bs, H, W, Z, grid_num, 0) || lr_bad_group(Z, A)) return VIDAR_ERR_BAD_ARG;
+  if (bs == 0) return 0;
+  launch_gather_fwd(path_prob, lora_a, feat, msum, bs, H, W, Z, A, Geo{H, W, grid_num, step, 0, eps},
+                    (hipStream_t)stream);
+  return vidar_last_error();
+}
+
+int vidar_latent_render_gather_grouped_bwd_f32(const float* path_prob, const float* lora_a, const float* feat,
+                                               const float* msum, const float* grad_feat, float* grad_path_prob,
+                                               float* grad_lora_a, int bs, int H, int W, int Z, int A, int grid_num,
+                                               float step, float eps, void* workspace, size_t workspace_bytes,
+                                               void* stream) {
+  VIDAR_ENTER();
+  if (lr_bad(bs, H, W, Z, grid_num, 0) || lr_bad_group(Z, A)) return VIDAR_ERR_BAD_ARG;
+  if (bs == 0) return 0;   // before anything is touched
+  return gather_bwd(path_prob, lora_a, feat, msum, grad_feat, grad_path_prob, grad_lora_a, bs, H, W, Z, A,
+                    Geo{H, W, grid_num, step, 0, eps}, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int vidar_latent_render_gather_fwd_f32(const float* path_prob, const float* lora_a, float* feat,
                                        float* msum, int bs, int H, int W, int Z, int grid_num,
                                        float step, float eps, void* stream) {
-  VIDAR_ENTER();
-  if (lr_bad(bs, H, W, Z, grid_num, 0)) return VIDAR_ERR_BAD_ARG;
-  if (bs == 0) return 0;
-  Geo g{H, W, grid_num, step, 0, eps};
-  hipLaunchKernelGGL(lr_gather_fwd_kernel, lr_grid(bs, H * W), dim3(kThreads), 0,
-                     (hipStream_t)stream, path_prob, lora_a, feat, msum, H * W, g);
-  return vidar_last_error();
+  return vidar_latent_render_gather_grouped_fwd_f32(path_prob, lora_a, feat, msum, bs, H, W, Z, Z, grid_num, step, eps,
+                                                    stream);
 }
 
 int vidar_latent_render_gather_bwd_f32(const float* path_prob, const float* lora_a, const float* feat,
@@ -353,16 +577,9 @@ int vidar_latent_render_gather_bwd_f32(const float* path_prob, const float* lora
                                        float* grad_path_prob, float* grad_lora_a, int bs, int H,
                                        int W, int Z, int grid_num, float step, float eps,
                                        void* workspace, size_t workspace_bytes, void* stream) {
-  VIDAR_ENTER();
-  if (lr_bad(bs, H, W, Z, grid_num, 0)) return VIDAR_ERR_BAD_ARG;
-  if (bs == 0) return 0;   // before anything is touched
-  hipStream_t s = (hipStream_t)stream;
-  Geo g{H, W, grid_num, step, 0, eps};
-  return scatter_with_copies<float4>(grad_path_prob, grad_lora_a, (size_t)bs * H * W * Z, false, workspace,
-                                     workspace_bytes, s, [&](float* sp, float* sa, int ncopies) {
-    hipLaunchKernelGGL(lr_gather_bwd_kernel, lr_grid(bs, H * W), dim3(kThreads), 0, s, path_prob, lora_a, feat, msum,
-                       grad_feat, sp, sa, H * W, g, ncopies);
-  });
+  return vidar_latent_render_gather_grouped_bwd_f32(path_prob, lora_a, feat, msum, grad_feat, grad_path_prob,
+                                                    grad_lora_a, bs, H, W, Z, Z, grid_num, step, eps, workspace,
+                                                    workspace_bytes, stream);
 }
 
 }  // extern "C"

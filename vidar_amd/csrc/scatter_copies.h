@@ -37,38 +37,48 @@ __global__ __launch_bounds__(256) void sum_copies_kernel(const T* __restrict__ c
   out[i] = a;
 }
 
-// The host side of a scatter backward with one gradient output (out1 == nullptr) or two, of n floats each; T is the
-// element type of the copy sum.
-//   * copies are used iff the workspace is non-NULL, holds scatter_workspace_bytes(n, volumes) and -- only where T is
-//     wider than float -- workspace and outputs are aligned to T;
+// The host side of a scatter backward with one gradient output (out1 == nullptr) of n0 floats or two, of n0 and n1
+// floats; T is the element type of the copy sum (n0 and n1 are multiples of its width).
+//   * copies are used iff the workspace is non-NULL, holds 8 copies of every output and -- only where T is wider than
+//     float -- workspace and outputs are aligned to T;
 //   * the accumulators (the copies, else the outputs) are zeroed;
-//   * `launch(acc0, acc1, ncopies)` enqueues the scatter kernel: volume v of copy c starts at acc_v + c * n;
+//   * `launch(acc0, acc1, ncopies)` enqueues the scatter kernel: copy c of volume v starts at acc_v + c * n_v;
 //   * the copies are summed into the outputs.  An `empty` launch (no rays) skips the kernel and leaves zeroed outputs.
 template <class T = float, class Launch>
-int scatter_with_copies(float* out0, float* out1, size_t n, bool empty, void* workspace, size_t workspace_bytes,
-                        hipStream_t s, Launch launch) {
-  const int volumes = out1 ? 2 : 1;
+int scatter_with_copies(float* out0, float* out1, size_t n0, size_t n1, bool empty, void* workspace,
+                        size_t workspace_bytes, hipStream_t s, Launch launch) {
+  if (!out1) n1 = 0;
+  const size_t need = scatter_workspace_bytes(n0 + n1, 1);
   const bool aligned =
       sizeof(T) == sizeof(float) || (((uintptr_t)workspace | (uintptr_t)out0 | (uintptr_t)out1) % sizeof(T)) == 0;
-  const bool copies = workspace != nullptr && workspace_bytes >= scatter_workspace_bytes(n, volumes) && aligned;
+  const bool copies = workspace != nullptr && workspace_bytes >= need && aligned;
   float* acc0 = copies ? (float*)workspace : out0;
-  float* acc1 = !out1 ? nullptr : copies ? (float*)workspace + n * kScatterCopies : out1;
+  float* acc1 = !out1 ? nullptr : copies ? (float*)workspace + n0 * kScatterCopies : out1;
   const auto zero_outputs = [&] {
-    hipError_t e = hipMemsetAsync(out0, 0, sizeof(float) * n, s);
-    if (e == hipSuccess && out1) e = hipMemsetAsync(out1, 0, sizeof(float) * n, s);
+    hipError_t e = hipMemsetAsync(out0, 0, sizeof(float) * n0, s);
+    if (e == hipSuccess && out1) e = hipMemsetAsync(out1, 0, sizeof(float) * n1, s);
     return e;
   };
-  const hipError_t e = copies ? hipMemsetAsync(workspace, 0, scatter_workspace_bytes(n, volumes), s) : zero_outputs();
+  const hipError_t e = copies ? hipMemsetAsync(workspace, 0, need, s) : zero_outputs();
   if (e != hipSuccess) return (int)e;
   if (empty) return copies ? (int)zero_outputs() : 0;
   launch(acc0, acc1, copies ? kScatterCopies : 1);
   if (copies) {
-    const size_t nt = n * sizeof(float) / sizeof(T);
-    const dim3 grid((unsigned)((nt + 255) / 256));
-    hipLaunchKernelGGL(sum_copies_kernel<T>, grid, dim3(256), 0, s, (const T*)acc0, (T*)out0, nt);
-    if (out1) hipLaunchKernelGGL(sum_copies_kernel<T>, grid, dim3(256), 0, s, (const T*)acc1, (T*)out1, nt);
+    const auto sum = [&](const float* acc, float* out, size_t n) {
+      const size_t nt = n * sizeof(float) / sizeof(T);
+      hipLaunchKernelGGL(sum_copies_kernel<T>, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, (const T*)acc, (T*)out,
+                         nt);
+    };
+    sum(acc0, out0, n0);
+    if (out1) sum(acc1, out1, n1);
   }
   return vidar_last_error();
+}
+// ... of n floats each
+template <class T = float, class Launch>
+int scatter_with_copies(float* out0, float* out1, size_t n, bool empty, void* workspace, size_t workspace_bytes,
+                        hipStream_t s, Launch launch) {
+  return scatter_with_copies<T>(out0, out1, n, n, empty, workspace, workspace_bytes, s, launch);
 }
 
 }  // namespace

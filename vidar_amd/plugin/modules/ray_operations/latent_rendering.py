@@ -56,16 +56,23 @@ class _PathProb(Function):
 
 
 class _RayGather(Function):
+    """prob [bs,H,W,Z], a [bs,H,W,A] with A = Z * J -> feat [bs,H,W,A]: LoRA channel ch takes the weights of bin ch // J"""
+
     @staticmethod
     def forward(ctx, prob, a, grid_num, grid_step, eps):
         bs, H, W, Z = prob.shape
+        A = a.shape[-1]
         prob = prob.float().contiguous(); a = a.float().contiguous()
-        feat = torch.empty_like(prob); msum = torch.empty_like(prob)
+        feat = torch.empty_like(a); msum = torch.empty_like(prob)
         step = _step(grid_step, H, W)
-        with TIMER.span("lr_gather_fwd", 4 * prob.numel() * 4):
-          check(lib().vidar_latent_render_gather_fwd_f32(ptr(prob), ptr(a), ptr(feat), ptr(msum), bs, H,
-                                                       W, Z, grid_num, step, eps, stream_of(prob)),
-              "latent_render_gather_fwd")
+        with TIMER.span("lr_gather_fwd", 4 * (2 * prob.numel() + 2 * a.numel())):
+          if A == Z:
+            rc = lib().vidar_latent_render_gather_fwd_f32(ptr(prob), ptr(a), ptr(feat), ptr(msum), bs, H,
+                                                          W, Z, grid_num, step, eps, stream_of(prob))
+          else:
+            rc = lib().vidar_latent_render_gather_grouped_fwd_f32(ptr(prob), ptr(a), ptr(feat), ptr(msum), bs, H, W, Z, A,
+                                                                  grid_num, step, eps, stream_of(prob))
+          check(rc, "latent_render_gather_fwd")
         ctx.save_for_backward(prob, a, feat, msum)
         ctx.cfg = (grid_num, step, eps)
         return feat
@@ -76,23 +83,32 @@ class _RayGather(Function):
         prob, a, feat, msum = ctx.saved_tensors
         grid_num, step, eps = ctx.cfg
         bs, H, W, Z = prob.shape
+        A = a.shape[-1]
         gp = torch.empty_like(prob); ga = torch.empty_like(a)
-        ws, wsp, wsn = workspace(lib().vidar_latent_render_bwd_workspace_bytes, bs, H, W, Z, 2, like=prob)
-        with TIMER.span("lr_gather_bwd", 4 * prob.numel() * 7):
-          check(lib().vidar_latent_render_gather_bwd_f32(ptr(prob), ptr(a), ptr(feat), ptr(msum),
-                                                       ptr(grad_feat.float().contiguous()), ptr(gp),
-                                                       ptr(ga), bs, H, W, Z, grid_num,
-                                                       step, eps, wsp, wsn, stream_of(prob)), "latent_render_gather_bwd")
+        ws, wsp, wsn = workspace(lib().vidar_latent_render_bwd_workspace_bytes, bs, H, W, max(Z, A), 2, like=prob)
+        grad_feat = grad_feat.float().contiguous()
+        with TIMER.span("lr_gather_bwd", 4 * (3 * prob.numel() + 4 * a.numel())):
+          if A == Z:
+            rc = lib().vidar_latent_render_gather_bwd_f32(ptr(prob), ptr(a), ptr(feat), ptr(msum),
+                                                          ptr(grad_feat), ptr(gp),
+                                                          ptr(ga), bs, H, W, Z, grid_num,
+                                                          step, eps, wsp, wsn, stream_of(prob))
+          else:
+            rc = lib().vidar_latent_render_gather_grouped_bwd_f32(ptr(prob), ptr(a), ptr(feat), ptr(msum), ptr(grad_feat),
+                                                                  ptr(gp), ptr(ga), bs, H, W, Z, A, grid_num, step, eps,
+                                                                  wsp, wsn, stream_of(prob))
+          check(rc, "latent_render_gather_bwd")
         return gp, ga, None, None, None
 
 
 def latent_render_path_prob(occ, grid_num, grid_step, act="sigmoid"):
-    """occ [bs,H,W,16] logits -> path probability [bs,H,W,16] (stage 1)."""
+    """occ [bs,H,W,Z] logits -> path probability [bs,H,W,Z] (stage 1), 1 <= Z <= 64."""
     return _PathProb.apply(occ, int(grid_num), float(grid_step), _ACT[act])
 
 
 def latent_render_gather(prob, a, grid_num, grid_step, eps=1e-3):
-    """prob, a [bs,H,W,16] -> ray-aggregated feature [bs,H,W,16] (stage 2)."""
+    """prob [bs,H,W,Z], a [bs,H,W,A] -> ray-aggregated feature [bs,H,W,A] (stage 2); A = Z * J <= 256 and channel ch
+    of `a` is weighted by bin ch // J of `prob` (the released configs: A == Z == 16)."""
     return _RayGather.apply(prob, a, int(grid_num), float(grid_step), float(eps))
 
 
@@ -103,6 +119,11 @@ class LatentRendering(nn.Module):
         super().__init__()
         if act not in _ACT:
             raise NotImplementedError("Only support exp or sigmoid activation_fn for now.")
+        lora = embed_dims // reduction
+        if pred_height < 1 or lora % pred_height or embed_dims % pred_height:
+            # the reference's view(bs, pred_height, -1, ...) (:148-150, :159-160) throws on these at the first forward
+            raise ValueError(f"LatentRendering: embed_dims // reduction ({lora}) and embed_dims ({embed_dims}) must both "
+                             f"be multiples of pred_height ({pred_height})")
         self.embed_dims = embed_dims
         self.num_pred_fcs = num_pred_fcs
         self.grid_num = grid_num
@@ -117,15 +138,10 @@ class LatentRendering(nn.Module):
         self.pred_height = pred_height
         self.lora_a = Linear(embed_dims, embed_dims // reduction)
         self.lora_b = Linear(embed_dims // reduction, embed_dims)
-        if pred_height != 16 or embed_dims // reduction != pred_height:
-            # the reference's view(bs, pred_height, -1, ...) (:151-154) allows more LoRA channels per
-            # height bin; every released config uses 16/16 and the kernels are specialised for it
-            raise NotImplementedError("LatentRendering HIP kernels need pred_height == "
-                                      "embed_dims // reduction == 16")
 
     def forward(self, embed, eps=1e-3, **kwargs):
         bs, bev_h, bev_w, _ = embed.shape
-        occ = self.unsup_raymarching_head(embed)                       # [bs,h,w,16]
+        occ = self.unsup_raymarching_head(embed)                       # [bs,h,w,Z]
         prob = latent_render_path_prob(occ, self.grid_num, self.grid_step, self.act)
         feat = latent_render_gather(prob, self.lora_a(embed), self.grid_num, self.grid_step, eps)
         out = self.lora_b(feat)                                        # [bs,h,w,C]
