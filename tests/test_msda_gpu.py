@@ -361,3 +361,114 @@ def test_merged_queue_mean_equals_the_unmerged_op_and_its_mean(bs, Nq, shapes, P
     torch.testing.assert_close(res[0][0], res[1][0], rtol=1e-5, atol=1e-6)
     for a, b, nm in zip(res[0][1], res[1][1], ["grad_value", "grad_off_raw", "grad_logit_raw"]):
         torch.testing.assert_close(a, b, rtol=2e-4, atol=2e-5 * max(1.0, float(b.abs().max())), msg=lambda m: nm + m)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the smallest shapes at which the bodies every MSDA kernel shares can still go wrong: 5 queries x 8 heads = 40 items
+# (partial workgroups of 8 and of 32 items), two levels of different size, L*P = 6 samples (not a multiple of 4)
+# ---------------------------------------------------------------------------------------------------------------------
+SMALL_SHAPES = [(3, 5), (2, 2)]
+FUSED_SMALL = {"mode0": (0, 2, 3, 2, False), "mode0_merged": (0, 2, 3, 2, True), "mode1_sca": (1, 1, 4, 2, False)}  # mode, Qn, P, R, merge
+
+
+@functools.lru_cache(maxsize=None)
+def _fused_small_case(name):
+    """operands and the fp64 expectation (the reference's tensor program, then the gather oracle), computed once"""
+    from vidar_amd.plugin.modules import multi_scale_deformable_attn_function as F
+    mode, Qn, P, R, merge = FUSED_SMALL[name]
+    bs, Nq, H, L = 1, 5, 8, len(SMALL_SHAPES)
+    g = torch.Generator().manual_seed(7)
+    Nv = sum(h * w for h, w in SMALL_SHAPES)
+    value = torch.randn(bs * Qn, Nv, H, 32, generator=g)
+    off_raw = torch.randn(bs, Nq, H * Qn * L * P * 2, generator=g) * 1.5            # pixels
+    logit_raw = torch.randn(bs, Nq, H * Qn * L * P, generator=g)
+    ref = torch.rand(bs * Qn, Nq, R, 2, generator=g) * 1.1 - 0.05
+    sh = torch.tensor(SMALL_SHAPES, dtype=torch.int64)
+    v64, o64, l64 = (t.double().requires_grad_(True) for t in (value, off_raw, logit_raw))
+    loc, w = F.compose_operands(o64, l64, ref.double(), sh, H, Qn, L, P, mode)
+    want = M.msda_gather(v64, sh, loc, w)
+    if merge:
+        want = want.view(bs, Qn, Nq, H * 32).mean(1)
+    gout = torch.randn(want.shape, generator=g)
+    gwant = torch.autograd.grad((want * gout.double()).sum(), [v64, o64, l64])
+    # no sample within fp32 rounding of a pixel boundary, where d/d offset is one-sided (a property of the inputs)
+    wh = torch.tensor([[w_, h_] for h_, w_ in SMALL_SHAPES], dtype=torch.float64).view(1, 1, 1, L, 1, 2)
+    pixel = loc.detach() * wh - 0.5
+    assert float((pixel - pixel.round()).abs().min()) > 1e-4
+    assert all(bool(torch.isfinite(t).all()) for t in (want, *gwant))
+    return (value, off_raw, logit_raw, ref, sh, gout), (want.detach(), loc.detach(), w.detach(), *gwant)
+
+
+@pytest.mark.parametrize("scatter", list(SCATTER))
+@pytest.mark.parametrize("name", list(FUSED_SMALL))
+def test_fused_small_shapes_through_both_backward_forms(name, scatter):
+    """vidar_msda_fused_{fwd,bwd}_f32 called directly, the backward with and without a workspace: the atomic kernel and
+    the binned path's gather run the same store phase (softmax backward, raw scatter) on the same numbers -- out, the
+    saved operands and the three gradients against the oracle, with the tolerances of the fused test above"""
+    from vidar_amd._lib import lib, check, ptr, stream_of
+    from vidar_amd.plugin.modules import multi_scale_deformable_attn_function as F
+    mode, Qn, P, R, merge = FUSED_SMALL[name]
+    bs, Nq, H, L = 1, 5, 8, len(SMALL_SHAPES)
+    (value, off_raw, logit_raw, ref, sh, gout), (want, wloc, ww, gv_w, go_w, gl_w) = _fused_small_case(name)
+    value, off_raw, logit_raw, ref, sh, gout = (t.cuda() for t in (value, off_raw, logit_raw, ref, sh, gout))
+    lsi = M.level_start_index(SMALL_SHAPES).cuda()
+    Bq, Nv = value.shape[:2]
+    loc = torch.empty((Bq, Nq, H, L, P, 2), device="cuda")
+    w = torch.empty((Bq, Nq, H, L, P), device="cuda")
+    out = torch.empty((bs if merge else Bq, Nq, H * 32), device="cuda")
+    check(lib().vidar_msda_fused_fwd_f32(ptr(value), ptr(sh), ptr(lsi), ptr(off_raw), ptr(logit_raw), ptr(ref), ptr(loc),
+                                         ptr(w), ptr(out), bs, Qn, Nv, H, 32, Nq, L, P, R, mode, int(merge), stream_of(value)),
+          "fused forward")
+    torch.testing.assert_close(out.cpu().double(), want, rtol=1e-4, atol=2e-5)
+    torch.testing.assert_close(loc.cpu().double(), wloc, rtol=1e-5, atol=1e-6)      # one fp32 division and one addition
+    torch.testing.assert_close(w.cpu().double(), ww, rtol=1e-5, atol=1e-6)
+    gv, g_off, g_logit = torch.empty_like(value), torch.empty_like(off_raw), torch.empty_like(logit_raw)
+    ws, ws_ptr, nbytes = F._bwd_workspace(value, Bq, Nv, H, Nq, L, P, SCATTER[scatter])
+    assert (ws is not None) == SCATTER[scatter]
+    check(lib().vidar_msda_fused_bwd_f32(ptr(value), ptr(sh), ptr(lsi), ptr(loc), ptr(w), ptr(gout), ptr(gv), ptr(g_off),
+                                         ptr(g_logit), bs, Qn, Nv, H, 32, Nq, L, P, int(merge), ws_ptr, nbytes,
+                                         stream_of(value)), "fused backward")
+    for a, b, nm in zip((gv, g_off, g_logit), (gv_w, go_w, gl_w), ["grad_value", "grad_off_raw", "grad_logit_raw"]):
+        scale = max(1.0, float(b.abs().max()))
+        torch.testing.assert_close(a.cpu().double(), b, rtol=3e-4, atol=3e-5 * scale, msg=lambda m: nm + m)
+
+
+@functools.lru_cache(maxsize=None)
+def _border_case():
+    """random locations with, per level and by hand, one sample 0.6 px outside each of the four borders (pixel -0.6 or
+    size - 0.4: one corner row / column still counts) and one NaN location.  The expectation is the oracle's on the same
+    operands with the NaN location moved far outside the level, which is what a NaN location means to every kernel; the
+    NaN sample's own grad_loc (undefined in the oracle) is not compared."""
+    value, sh, loc, w = M.make_case(4, 1, SMALL_SHAPES, 5, P=3)
+    for l, (Hl, Wl) in enumerate(SMALL_SHAPES):
+        loc[0, :4, 0, l, 0] = 0.4                            # the other coordinate: inside, away from pixel boundaries
+        loc[0, 0, 0, l, 0, 0] = -0.1 / Wl
+        loc[0, 1, 0, l, 0, 0] = (Wl + 0.1) / Wl
+        loc[0, 2, 0, l, 0, 1] = -0.1 / Hl
+        loc[0, 3, 0, l, 0, 1] = (Hl + 0.1) / Hl
+    nan_at = (0, 4, 1, 0, 1)
+    finite = loc.clone(); finite[nan_at] = 5.0
+    loc[nan_at] = float("nan")
+    v64, l64, w64 = (t.double().requires_grad_(True) for t in (value, finite, w))
+    ref = M.msda_gather(v64, sh, l64, w64)
+    gout = torch.randn(ref.shape, generator=torch.Generator().manual_seed(5))
+    gref = torch.autograd.grad((ref * gout.double()).sum(), [v64, l64, w64])
+    assert all(bool(torch.isfinite(t).all()) for t in (ref, *gref))
+    for l, (Hl, Wl) in enumerate(SMALL_SHAPES):              # the hand-placed samples do contribute
+        assert float(gref[2][0, :4, 0, l, 0].abs().min()) > 0
+    return (value, sh, loc, w, gout), (ref.detach(), *gref), nan_at
+
+
+@pytest.mark.parametrize("scatter", list(SCATTER))
+def test_samples_just_outside_each_border_and_a_nan_location(scatter):
+    from vidar_amd.plugin.modules import multi_scale_deformable_attn_function as F
+    (value, sh, loc, w, gout), (ref, rv, rl, rw), nan_at = _border_case()
+    lsi = M.level_start_index(SMALL_SHAPES).cuda()
+    args = (value.cuda(), sh.cuda(), lsi, loc.cuda(), w.cuda())
+    out = F._msda_forward(*args)
+    torch.testing.assert_close(out.cpu().double(), ref, rtol=1e-4, atol=1e-5)
+    got = [g.cpu().double() for g in F._msda_backward(*args, gout.cuda(), binned=SCATTER[scatter])]
+    got[1][nan_at] = rl[nan_at]
+    for g, r, nm in zip(got, (rv, rl, rw), ["grad_value", "grad_loc", "grad_w"]):
+        scale = max(1.0, float(r.abs().max()))
+        torch.testing.assert_close(g, r, rtol=2e-4, atol=2e-5 * scale, msg=lambda m: nm + m)

@@ -78,27 +78,34 @@ __device__ __forceinline__ bool item_map(ItemMap& m, int bid, int nblocks, int64
 // binned backward computes the tile of a sample in one kernel and its window offset in another
 __device__ __forceinline__ float pix(float v, int n) { return __fmaf_rn(v, (float)n, -0.5f); }
 
-struct Corner {
-  int64_t o00, o01, o10, o11;  // element offsets (in floats) or -1
-  float w00, w01, w10, w11;
-  float lh, lw;
+// Bilinear cell of a sample at normalised (x, y) on a level of Hl x Wl pixels: THE rule for "is this sample inside,
+// which corners count, what are the weights".  corner_records derives its record from it, msda_bwd_kernel its element
+// offsets, sample_tile the destination tile and msda_bwd_tile_kernel the window line: they agree bit for bit.
+struct Cell {
+  bool in;           // -1 < pixel < size on both axes (false for a NaN location): the sample counts
+  int h0, w0;        // top-left corner pixel, -1 .. size - 1 when `in`
+  float lh, lw;      // weight of the bottom row / right column
+  bool t, b, l, r;   // row h0 / row h0 + 1 / column w0 / column w0 + 1 lies inside the level
 };
 
-__device__ __forceinline__ Corner corners(float x, float y, int Hl, int Wl, int64_t base,
-                                          int row_stride) {
-  // x,y already in pixel units (loc*size - 0.5) and known to be inside (-1, size)
-  Corner c;
-  const int h0 = (int)floorf(y), w0 = (int)floorf(x);
-  const int h1 = h0 + 1, w1 = w0 + 1;
-  c.lh = y - h0; c.lw = x - w0;
-  const float hh = 1.f - c.lh, hw = 1.f - c.lw;
-  c.w00 = hh * hw; c.w01 = hh * c.lw; c.w10 = c.lh * hw; c.w11 = c.lh * c.lw;
-  const bool t = h0 >= 0, b = h1 <= Hl - 1, l = w0 >= 0, r = w1 <= Wl - 1;
-  c.o00 = (t && l) ? base + ((int64_t)h0 * Wl + w0) * row_stride : -1;
-  c.o01 = (t && r) ? base + ((int64_t)h0 * Wl + w1) * row_stride : -1;
-  c.o10 = (b && l) ? base + ((int64_t)h1 * Wl + w0) * row_stride : -1;
-  c.o11 = (b && r) ? base + ((int64_t)h1 * Wl + w1) * row_stride : -1;
+__device__ __forceinline__ Cell cell(float nx, float ny, int Hl, int Wl) {
+  Cell c;
+  const float x = pix(nx, Wl), y = pix(ny, Hl);
+  c.in = y > -1.f && x > -1.f && y < Hl && x < Wl;
+  c.h0 = (int)floorf(y); c.w0 = (int)floorf(x);
+  c.lh = y - c.h0; c.lw = x - c.w0;
+  c.t = c.h0 >= 0; c.b = c.h0 + 1 <= Hl - 1; c.l = c.w0 >= 0; c.r = c.w0 + 1 <= Wl - 1;
   return c;
+}
+
+// gradient of one sample w.r.t. its normalised (x, y) and its attention weight, from the four corner dot products
+// <value corner line, grad_out line> (the caller zeroes those of corners outside the level)
+__device__ __forceinline__ void sample_grads(float lh, float lw, float w, int Wl, int Hl, float d00, float d01, float d10,
+                                             float d11, float& gx, float& gy, float& gw) {
+  const float hh = 1.f - lh, hw = 1.f - lw;
+  gw = hh * hw * d00 + hh * lw * d01 + lh * hw * d10 + lh * lw * d11;
+  gx = w * Wl * (-hh * d00 + hh * d01 - lh * d10 + lh * d11);
+  gy = w * Hl * (-hw * d00 - lw * d01 + hw * d10 + lw * d11);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -131,26 +138,34 @@ struct Prep {
   int merge;
 };
 
+// Queue entries.  value / ref / the saved operands have one batch row per (batch element b, queue entry qn):
+// row b*Qn + qn, so an item there is ((b*Qn + qn)*Nq + q)*H + h; the raw Linear outputs are [bs, Nq, H, Qn, L*P]; a
+// merged item is (b, q, h) of the bs batch elements and carries its Qn entries as groups of samples.
+struct QueueMap {
+  int H, Nq, Qn;
+  // batch row of queue entry g of the merged item (b, q, h)
+  __device__ __forceinline__ int batch_row(int64_t item, int g) const { return (int)(item / H / Nq) * Qn + g; }
+  // the inverse: merged item (b, q, h) of item ((b*Qn + qn)*Nq + q)*H + h
+  __device__ __forceinline__ int64_t merged_item(int64_t item) const {
+    const int64_t bp = item / (Nq * H); return item - (bp - bp / Qn) * (Nq * H);
+  }
+  // index of (item, lp) inside the raw [bs, Nq, H, Qn, LP] layout
+  __device__ __forceinline__ int64_t raw_index(int64_t item, int lp, int LP) const {
+    const int h = (int)(item % H);
+    const int64_t bq = item / H, q = bq % Nq, bp = bq / Nq, b = bp / Qn, qn = bp % Qn;
+    return ((((b * Nq + q) * H + h) * Qn + qn) * LP) + lp;
+  }
+};
+
 // merged queue entries in the backward: grad_out is [bs, Nq, H*C], item' = ((b*Qn + qn)*Nq + q)*H + h reads the line of
 // (b, q, h), scaled by 1/Qn
 struct GoMap {
   int Qn, NqH;
   float scale;
   __device__ __forceinline__ int64_t at(int64_t item) const {
-    if (Qn <= 1) return item;
-    const int64_t bp = item / NqH;
-    return item - (bp - bp / Qn) * NqH;
+    return Qn <= 1 ? item : QueueMap{1, NqH, Qn}.merged_item(item);     // (q, h) as one axis of Nq*H lines
   }
 };
-
-// index of (item, lp) inside the raw [bs, Nq, H, Qn, LP] layout
-__device__ __forceinline__ int64_t raw_index(int64_t item, int lp, int H, int Nq, int LP, int Qn) {
-  const int h = (int)(item % H);
-  const int64_t bq = item / H;
-  const int64_t q = bq % Nq, bp = bq / Nq;
-  const int64_t b = bp / Qn, qn = bp % Qn;
-  return ((((b * Nq + q) * H + h) * Qn + qn) * LP) + lp;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Gather kernels (forward, and grad_loc / grad_w of the backward).  A workgroup owns 32 consecutive
@@ -168,26 +183,52 @@ __device__ __forceinline__ int64_t raw_index(int64_t item, int lp, int H, int Nq
 //   checks B*Nv*H*32*4 < 2^32); an invalid corner points at a valid line and carries weight / mask 0.
 // ---------------------------------------------------------------------------------------------
 constexpr int kRecF = 8;                    // floats per sample record
-constexpr int kGLv = 16;                    // levels supported by the gather kernels' level table
 
 __device__ __forceinline__ int rec_at(int it, int lp, int LP) { return (it * (LP + 1) + lp) * kRecF; }
 inline size_t rec_lds_bytes(int LP) { return sizeof(float) * (size_t)kItems * (LP + 1) * kRecF; }
 
-struct GLevels { int Hl[kGLv], Wl[kGLv], start[kGLv]; };
+// Level tables in LDS: the kernels read level sizes as int from here, not as int64 from `shapes` / `lsi` in their loops.
+// The binned path's table carries tile geometry instead of first pixels (two structs sharing kMaxL: no kernel's
+// static LDS grows).
+constexpr int kMaxL = 16;                   // levels supported
+#ifndef VIDAR_MSDA_TILE_SHIFT
+#define VIDAR_MSDA_TILE_SHIFT 3
+#endif
+constexpr int kTileShift = VIDAR_MSDA_TILE_SHIFT;
 
-__device__ __forceinline__ void load_levels(GLevels& t, const int64_t* __restrict__ shapes,
+struct Levels { int Hl[kMaxL], Wl[kMaxL], start[kMaxL]; };       // gather kernels, msda_bwd_kernel
+struct TileLevels {                                              // binned path (tiles of 2^kTileShift corner pixels)
+  int Hl[kMaxL], Wl[kMaxL], ntx[kMaxL], toff[kMaxL];             // tiles per tile row, first tile of the level
+  int T;                                                         // tiles per batch element
+};
+
+// load_levels fills the workgroup's table and ENDS WITH A BARRIER (one overload per table: the fills differ)
+__device__ __forceinline__ void load_levels(Levels& t, const int64_t* __restrict__ shapes,
                                             const int64_t* __restrict__ lsi, int L) {
   if ((int)threadIdx.x < L) {
     t.Hl[threadIdx.x] = (int)shapes[2 * threadIdx.x];
     t.Wl[threadIdx.x] = (int)shapes[2 * threadIdx.x + 1];
     t.start[threadIdx.x] = (int)lsi[threadIdx.x];
   }
+  __syncthreads();
+}
+__device__ __forceinline__ void load_levels(TileLevels& t, const int64_t* __restrict__ shapes, int L) {
+  if (threadIdx.x == 0) {                                        // toff is a running sum: one thread
+    int off = 0;
+    for (int l = 0; l < L; ++l) {
+      const int Hl = (int)shapes[2 * l], Wl = (int)shapes[2 * l + 1];
+      t.Hl[l] = Hl; t.Wl[l] = Wl; t.ntx[l] = (Wl >> kTileShift) + 1; t.toff[l] = off;
+      off += t.ntx[l] * ((Hl >> kTileShift) + 1);       // px = floor(x)+1 in [0, Wl], py likewise
+    }
+    t.T = off;
+  }
+  __syncthreads();
 }
 
 // stage (x, y, w) of the workgroup's items into fields 0..2 of their records
 template <int kThr>
 __device__ __forceinline__ void stage_records(const Prep& pr, const float* __restrict__ loc,
-                                              const float* __restrict__ attw, const GLevels& lv, float* rec,
+                                              const float* __restrict__ attw, const Levels& lv, float* rec,
                                               const ItemMap& im, int H, int Nq, int L, int P) {
   const int LP = L * P;
   const int nvalid = im.nvalid;
@@ -206,16 +247,17 @@ __device__ __forceinline__ void stage_records(const Prep& pr, const float* __res
   // (b, q, h) is queue entry g: batch row b*Qn + g of ref / value / the saved operands, and the raw layout
   // [bs, Nq, H, Qn, L*P] makes the item's Qn * L*P raw values contiguous
   const int Qm = pr.merge ? pr.Qn : 1, LPg = LP / Qm;
+  const QueueMap qm{H, Nq, pr.Qn};
   for (int i = threadIdx.x; i < nvalid * LP; i += kThr) {
     const int it = i / LP, lp = i - it * LP;
     const int64_t item = im.at(it);
     const int g = lp / LPg, lpg = lp - g * LPg;
-    const int64_t raw = pr.merge ? item * LP + lp : raw_index(item, lp, H, Nq, LP, pr.Qn);
+    const int64_t raw = pr.merge ? item * LP + lp : qm.raw_index(item, lp, LP);
     const int l = lpg / P, p = lpg - l * P;
     const int rr = pr.mode == 0 ? l : p % pr.R;
     const float2 o = reinterpret_cast<const float2*>(pr.off_raw)[raw];
     const int64_t bq = item / H;                     // merge: (b, q) of the bs rows -> row b*Qn + g of ref
-    const int64_t refrow = pr.merge ? ((bq / Nq) * Qm + g) * Nq + bq % Nq : bq;
+    const int64_t refrow = pr.merge ? (int64_t)qm.batch_row(item, g) * Nq + bq % Nq : bq;
     const float2 rf = reinterpret_cast<const float2*>(pr.ref)[refrow * pr.R + rr];
     float* r = rec + rec_at(it, lp, LP);
     r[0] = rf.x + o.x / (float)lv.Wl[l];
@@ -260,9 +302,9 @@ __device__ __forceinline__ void stage_records(const Prep& pr, const float* __res
       const float* r = rec + rec_at(it, lp, LP);
       int64_t e = im.at(it) * LP + lp;
       if (pr.merge) {                                  // saved operands stay [bs*Qn, Nq, H, L*P]
-        const int64_t item = im.at(it), bq = item / H;
+        const int64_t item = im.at(it);
         const int g = lp / LPg;
-        e = ((((bq / Nq) * Qm + g) * Nq + bq % Nq) * H + item % H) * LPg + (lp - g * LPg);
+        e = (((int64_t)qm.batch_row(item, g) * Nq + item / H % Nq) * H + item % H) * LPg + (lp - g * LPg);
       }
       reinterpret_cast<float2*>(pr.loc_out)[e] = make_float2(r[0], r[1]);
       pr.w_out[e] = r[2];
@@ -272,37 +314,35 @@ __device__ __forceinline__ void stage_records(const Prep& pr, const float* __res
 
 // corner arithmetic of one sample, once: (x, y, w) in the record -> the forward or backward record
 template <int kThr, bool BWD>
-__device__ __forceinline__ void corner_records(const GLevels& lv, float* rec, const ItemMap& im, int Nv,
+__device__ __forceinline__ void corner_records(const Levels& lv, float* rec, const ItemMap& im, int Nv,
                                                int H, int Nq, int L, int P, int Qm = 1) {
   // Qm > 1 (merged queue entries, forward): LP = Qm * L * P samples per item, group g reads value plane b*Qm + g
   const int LP = Qm * L * P, LPg = L * P;
   const int nvalid = im.nvalid;
+  const QueueMap qm{H, Nq, Qm};
   for (int i = threadIdx.x; i < nvalid * LP; i += kThr) {
     const int it = i / LP, lp = i - it * LP;
     const int g = lp / LPg;
     const int l = (lp - g * LPg) / P;
     const int64_t item = im.at(it);
     const int h = (int)(item % H);
-    const int b = (int)(item / H / Nq) * Qm + g;
+    const int b = qm.batch_row(item, g);
     const int Hl = lv.Hl[l], Wl = lv.Wl[l];
     float* r = rec + rec_at(it, lp, LP);
-    const float x = pix(r[0], Wl), y = pix(r[1], Hl), w = r[2];
-    const bool in = y > -1.f && x > -1.f && y < Hl && x < Wl;
-    const int h0 = (int)floorf(y), w0 = (int)floorf(x);
-    const float lh = y - h0, lw = x - w0;
-    const bool t = h0 >= 0, bo = h0 + 1 <= Hl - 1, le = w0 >= 0, ri = w0 + 1 <= Wl - 1;
-    const int r0 = min(max(h0, 0), Hl - 1) * Wl, r1 = min(max(h0 + 1, 0), Hl - 1) * Wl;
-    const int c0 = min(max(w0, 0), Wl - 1), c1 = min(max(w0 + 1, 0), Wl - 1);
+    const Cell c = cell(r[0], r[1], Hl, Wl);
+    const float lh = c.lh, lw = c.lw, w = r[2];
+    const int r0 = min(max(c.h0, 0), Hl - 1) * Wl, r1 = min(max(c.h0 + 1, 0), Hl - 1) * Wl;
+    const int c0 = min(max(c.w0, 0), Wl - 1), c1 = min(max(c.w0 + 1, 0), Wl - 1);
     const unsigned line0 = ((unsigned)b * Nv + lv.start[l]) * H + h;          // line index of pixel 0 (128 B per line)
     const unsigned o00 = (line0 + (unsigned)(r0 + c0) * H) * (kCh * 4), o01 = (line0 + (unsigned)(r0 + c1) * H) * (kCh * 4);
     const unsigned o10 = (line0 + (unsigned)(r1 + c0) * H) * (kCh * 4), o11 = (line0 + (unsigned)(r1 + c1) * H) * (kCh * 4);
     if (!BWD) {
       // a sample outside the level (or with a NaN location) contributes nothing: selects, not products with 0
       const float hh = 1.f - lh, hw = 1.f - lw;
-      reinterpret_cast<float4*>(r)[0] = make_float4((in && t && le) ? hh * hw * w : 0.f, (in && t && ri) ? hh * lw * w : 0.f,
-                                                    (in && bo && le) ? lh * hw * w : 0.f, (in && bo && ri) ? lh * lw * w : 0.f);
+      reinterpret_cast<float4*>(r)[0] = make_float4((c.in && c.t && c.l) ? hh * hw * w : 0.f, (c.in && c.t && c.r) ? hh * lw * w : 0.f,
+                                                    (c.in && c.b && c.l) ? lh * hw * w : 0.f, (c.in && c.b && c.r) ? lh * lw * w : 0.f);
     } else {
-      const int meta = in ? ((int)(t && le) | ((int)(t && ri) << 1) | ((int)(bo && le) << 2) | ((int)(bo && ri) << 3) | (l << 4)) : -1;
+      const int meta = c.in ? ((int)(c.t && c.l) | ((int)(c.t && c.r) << 1) | ((int)(c.b && c.l) << 2) | ((int)(c.b && c.r) << 3) | (l << 4)) : -1;
       reinterpret_cast<float4*>(r)[0] = make_float4(lh, lw, w, __int_as_float(meta));
     }
     reinterpret_cast<uint4*>(r)[1] = make_uint4(o00, o01, o10, o11);
@@ -320,13 +360,12 @@ __global__ __launch_bounds__(kThreads) void msda_fwd_kernel(
     float* __restrict__ out, int Nv, int H, int Nq, int L, int P, int64_t n_items, int nblocks, int head_major,
     Prep pr) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ GLevels lv;
+  __shared__ Levels lv;
   const int Qm = pr.merge ? pr.Qn : 1;
   const int LP = Qm * L * P;                  // samples per item (merged queue entries: Qn groups of L * P)
   ItemMap im;
   if (!item_map(im, blockIdx.x, nblocks, n_items, H, head_major)) return;
   load_levels(lv, shapes, lsi, L);
-  __syncthreads();
   const int nvalid = im.nvalid;
   stage_records<kThreads>(pr, loc, attw, lv, smem, im, H, Nq, Qm * L, P);
   corner_records<kThreads, false>(lv, smem, im, Nv, H, Nq, L, P, Qm);
@@ -350,32 +389,31 @@ __global__ __launch_bounds__(kThreads) void msda_fwd_kernel(
   *reinterpret_cast<float4*>(out + im.at(it) * kCh + sub * 4) = acc;
 }
 
-// store phase of the backward kernels: s_loc / s_w hold grad_loc / grad_w of `nvalid` items
-template <int kThr>
-__device__ __forceinline__ void store_grads(const Prep& pr, const float* __restrict__ attw,
-                                            const int64_t* __restrict__ shapes, float* __restrict__ grad_loc,
-                                            float* __restrict__ grad_w, float* s_loc, float* s_w, float* s_dot,
-                                            int64_t item0, int nvalid, int H, int Nq, int L, int P) {
+// Store phase of the fused backward, shared by both backward forms: grad_loc / grad_w of the workgroup's `nvalid` items
+// become grad_off_raw / grad_logit_raw.  The kernel says how it keeps them: at(it, lp) -> {g_x, g_y, g_w, w} of a
+// sample, item_of(it) -> the item.
+template <int kThr, class ItemOf, class At>
+__device__ __forceinline__ void store_raw_grads(const Prep& pr, const Levels& lv, float* s_dot, int nvalid, int H, int Nq,
+                                                int L, int P, ItemOf item_of, At at) {
   const int LP = L * P;
-  if (pr.g_off_raw == nullptr) {
-    for (int i = threadIdx.x; i < nvalid * LP * 2; i += kThr) grad_loc[item0 * LP * 2 + i] = s_loc[i];
-    for (int i = threadIdx.x; i < nvalid * LP; i += kThr) grad_w[item0 * LP + i] = s_w[i];
-    return;
-  }
+  const QueueMap qm{H, Nq, pr.Qn};
   // softmax backward: g_logit = w * (g_w - sum_j w_j g_w_j);  d loc / d off = 1 / (W_l, H_l)
   for (int it = threadIdx.x; it < nvalid; it += kThr) {
     float dot = 0.f;
-    for (int lp = 0; lp < LP; ++lp) dot += attw[(item0 + it) * LP + lp] * s_w[it * LP + lp];
+    for (int lp = 0; lp < LP; ++lp) {
+      const float4 a = at(it, lp);
+      dot += a.w * a.z;
+    }
     s_dot[it] = dot;
   }
   __syncthreads();
   for (int i = threadIdx.x; i < nvalid * LP; i += kThr) {
     const int it = i / LP, lp = i - it * LP;
-    const int64_t raw = raw_index(item0 + it, lp, H, Nq, LP, pr.Qn);
+    const float4 a = at(it, lp);
+    const int64_t raw = qm.raw_index(item_of(it), lp, LP);
     const int l = lp / P;
-    pr.g_logit_raw[raw] = attw[item0 * LP + i] * (s_w[i] - s_dot[it]);
-    reinterpret_cast<float2*>(pr.g_off_raw)[raw] =
-        make_float2(s_loc[2 * i] / (float)shapes[2 * l + 1], s_loc[2 * i + 1] / (float)shapes[2 * l]);
+    pr.g_logit_raw[raw] = a.w * (a.z - s_dot[it]);
+    reinterpret_cast<float2*>(pr.g_off_raw)[raw] = make_float2(a.x / (float)lv.Wl[l], a.y / (float)lv.Hl[l]);
   }
 }
 
@@ -405,6 +443,7 @@ __global__ __launch_bounds__(kThreads) void msda_bwd_kernel(
     float* __restrict__ grad_loc, float* __restrict__ grad_w, int Nv, int H, int Nq, int L, int P,
     int64_t n_items, int nblocks, Prep pr, GoMap gm) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  __shared__ Levels lv;
   const int LP = L * P;
   float* s_loc = smem;                         // [kBItems][LP*2]  in: loc, out: grad_loc
   float* s_w = smem + kBItems * LP * 2;        // [kBItems][LP]    in: w,   out: grad_w
@@ -415,7 +454,7 @@ __global__ __launch_bounds__(kThreads) void msda_bwd_kernel(
   const int nvalid = (int)min((int64_t)kBItems, n_items - item0);
   for (int i = threadIdx.x; i < nvalid * LP * 2; i += kThreads) s_loc[i] = loc[item0 * LP * 2 + i];
   for (int i = threadIdx.x; i < nvalid * LP; i += kThreads) s_w[i] = attw[item0 * LP + i];
-  __syncthreads();
+  load_levels(lv, shapes, lsi, L);             // its barrier is also the one between the staging loops above and their readers
   const int it = threadIdx.x / kBLanes, ch = threadIdx.x % kBLanes;
   if (it < nvalid) {
     const int64_t item = item0 + it;
@@ -430,26 +469,24 @@ __global__ __launch_bounds__(kThreads) void msda_bwd_kernel(
     float* ml = s_loc + it * LP * 2;
     float* mw = s_w + it * LP;
     for (int l = 0; l < L; ++l) {
-      const int Hl = (int)shapes[2 * l], Wl = (int)shapes[2 * l + 1];
-      const int64_t base = lsi[l] * row_stride;
+      const int Hl = lv.Hl[l], Wl = lv.Wl[l];
+      const int64_t base = (int64_t)lv.start[l] * row_stride;
       for (int p = 0; p < P; ++p) {
-        const float x = pix(ml[(l * P + p) * 2], Wl);
-        const float y = pix(ml[(l * P + p) * 2 + 1], Hl);
+        const Cell c = cell(ml[(l * P + p) * 2], ml[(l * P + p) * 2 + 1], Hl, Wl);
         const float w = mw[l * P + p];
         float gx = 0.f, gy = 0.f, gw = 0.f;
-        if (y > -1.f && x > -1.f && y < Hl && x < Wl) {     // uniform over the item's 32 lanes
-          const Corner c = corners(x, y, Hl, Wl, base, row_stride);
-          const float d00 = ld1(vb, c.o00) * go, d01 = ld1(vb, c.o01) * go,
-                      d10 = ld1(vb, c.o10) * go, d11 = ld1(vb, c.o11) * go;
+        if (c.in) {                                         // uniform over the item's 32 lanes
+          const int64_t top = base + ((int64_t)c.h0 * Wl + c.w0) * row_stride, bot = top + (int64_t)Wl * row_stride;
+          const int64_t o00 = (c.t && c.l) ? top : -1, o01 = (c.t && c.r) ? top + row_stride : -1;   // element offsets or -1
+          const int64_t o10 = (c.b && c.l) ? bot : -1, o11 = (c.b && c.r) ? bot + row_stride : -1;
+          const float d00 = ld1(vb, o00) * go, d01 = ld1(vb, o01) * go, d10 = ld1(vb, o10) * go, d11 = ld1(vb, o11) * go;
+          sample_grads(c.lh, c.lw, w, Wl, Hl, d00, d01, d10, d11, gx, gy, gw);
           const float hh = 1.f - c.lh, hw = 1.f - c.lw;
-          gw = c.w00 * d00 + c.w01 * d01 + c.w10 * d10 + c.w11 * d11;
-          gx = w * Wl * (-hh * d00 + hh * d01 - c.lh * d10 + c.lh * d11);
-          gy = w * Hl * (-hw * d00 - c.lw * d01 + hw * d10 + c.lw * d11);
           const float wg = w * go;
-          if (c.o00 >= 0) unsafeAtomicAdd(gvb + c.o00, c.w00 * wg);
-          if (c.o01 >= 0) unsafeAtomicAdd(gvb + c.o01, c.w01 * wg);
-          if (c.o10 >= 0) unsafeAtomicAdd(gvb + c.o10, c.w10 * wg);
-          if (c.o11 >= 0) unsafeAtomicAdd(gvb + c.o11, c.w11 * wg);
+          if (o00 >= 0) unsafeAtomicAdd(gvb + o00, hh * hw * wg);
+          if (o01 >= 0) unsafeAtomicAdd(gvb + o01, hh * c.lw * wg);
+          if (o10 >= 0) unsafeAtomicAdd(gvb + o10, c.lh * hw * wg);
+          if (o11 >= 0) unsafeAtomicAdd(gvb + o11, c.lh * c.lw * wg);
         }
         gx = half_wave_sum(gx); gy = half_wave_sum(gy); gw = half_wave_sum(gw);
         // all 32 lanes consumed (x, y, w) of this point before the shuffles finished
@@ -462,7 +499,16 @@ __global__ __launch_bounds__(kThreads) void msda_bwd_kernel(
     }
   }
   __syncthreads();
-  store_grads<kThreads>(pr, attw, shapes, grad_loc, grad_w, s_loc, s_w, s_dot, item0, nvalid, H, Nq, L, P);
+  // store phase: s_loc / s_w hold grad_loc / grad_w of `nvalid` items
+  if (pr.g_off_raw == nullptr) {
+    for (int i = threadIdx.x; i < nvalid * LP * 2; i += kThreads) grad_loc[item0 * LP * 2 + i] = s_loc[i];
+    for (int i = threadIdx.x; i < nvalid * LP; i += kThreads) grad_w[item0 * LP + i] = s_w[i];
+    return;
+  }
+  store_raw_grads<kThreads>(pr, lv, s_dot, nvalid, H, Nq, L, P, [&](int it) { return item0 + it; }, [&](int it, int lp) {
+    const int i = it * LP + lp;
+    return make_float4(s_loc[2 * i], s_loc[2 * i + 1], s_w[i], attw[item0 * LP + i]);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -481,10 +527,6 @@ __global__ __launch_bounds__(kThreads) void msda_bwd_kernel(
 // flushes the non-zero window lines with one atomic per line: ~2-3 M requests instead of 61 M.
 // grad_loc / grad_w come from a gather kernel shaped like the forward (no atomics at all).
 // ---------------------------------------------------------------------------------------------
-#ifndef VIDAR_MSDA_TILE_SHIFT
-#define VIDAR_MSDA_TILE_SHIFT 3
-#endif
-constexpr int kTileShift = VIDAR_MSDA_TILE_SHIFT;
 constexpr int kTile = 1 << kTileShift;         // tile edge (top-left corner pixels)
 constexpr int kWin = kTile + 1;                // window edge (corner pixels)
 constexpr int kWinLines = kWin * kWin;         // 81 lines of 32 floats
@@ -493,7 +535,6 @@ static_assert(kWinLines < 128, "the window line index shares a word with a 128-b
 #define VIDAR_MSDA_CHUNK 1024
 #endif
 constexpr int kChunk = VIDAR_MSDA_CHUNK;       // samples per chunk descriptor (tuning sweep: tools/tune_msda_tile.sh)
-constexpr int kMaxL = 16;                      // levels supported by the binned path
 constexpr int kTWaves = 4;                     // waves (= chunks, private 10 KB windows) per workgroup of the accumulate kernel
 #ifndef VIDAR_MSDA_TILE_GROUP
 #define VIDAR_MSDA_TILE_GROUP 8
@@ -503,33 +544,13 @@ static_assert(64 % kGrp == 0, "groups tile a 64-sample batch");
 // (16-byte sort records {x, y, attention weight, sample} that the accumulate kernel would read coalesced instead of
 //  gathering loc[s] / attw[s]: 1.24 vs 1.19 ms for the SCA backward -- the fill pass's scattered stores grow 4x; removed)
 
-struct LevelTab {
-  int Hl[kMaxL], Wl[kMaxL], ntx[kMaxL], toff[kMaxL];
-  int T;                                       // tiles per batch element
-};
-
-__device__ __forceinline__ void build_tab(LevelTab& t, const int64_t* __restrict__ shapes, int L) {
-  if (threadIdx.x == 0) {
-    int off = 0;
-    for (int l = 0; l < L; ++l) {
-      const int Hl = (int)shapes[2 * l], Wl = (int)shapes[2 * l + 1];
-      t.Hl[l] = Hl; t.Wl[l] = Wl; t.ntx[l] = (Wl >> kTileShift) + 1; t.toff[l] = off;
-      off += t.ntx[l] * ((Hl >> kTileShift) + 1);       // px = floor(x)+1 in [0, Wl], py likewise
-    }
-    t.T = off;
-  }
-  __syncthreads();
-}
-
 // tile (within its level) of a sample, or -1 when the sample falls outside the level -- exactly the
 // test of the forward
-__device__ __forceinline__ int sample_tile(const LevelTab& t, const float* __restrict__ loc, int64_t s, int l) {
+__device__ __forceinline__ int sample_tile(const TileLevels& t, const float* __restrict__ loc, int64_t s, int l) {
   const float2 xy = reinterpret_cast<const float2*>(loc)[s];
-  const int Hl = t.Hl[l], Wl = t.Wl[l];
-  const float x = pix(xy.x, Wl), y = pix(xy.y, Hl);
-  if (!(y > -1.f && x > -1.f && y < Hl && x < Wl)) return -1;
-  const int px = (int)floorf(x) + 1, py = (int)floorf(y) + 1;
-  return (py >> kTileShift) * t.ntx[l] + (px >> kTileShift);
+  const Cell c = cell(xy.x, xy.y, t.Hl[l], t.Wl[l]);
+  if (!c.in) return -1;
+  return ((c.h0 + 1) >> kTileShift) * t.ntx[l] + ((c.w0 + 1) >> kTileShift);
 }
 
 // Counting sort, passes 1 and 3.  Global int atomics on the tile counters would put the sort on the
@@ -552,8 +573,8 @@ __global__ __launch_bounds__(kThreads) void msda_bin_kernel(
     const int64_t* __restrict__ shapes, const float* __restrict__ loc, int* __restrict__ counts,
     int* __restrict__ rec, int H, int Nq, int L, int P, int kBinQ) {
   extern __shared__ int s_hist[];              // [ntl] counts; (FILL) then the per-tile record cursors
-  __shared__ LevelTab t;
-  build_tab(t, shapes, L);
+  __shared__ TileLevels t;
+  load_levels(t, shapes, L);
   // a workgroup owns kBinQ queries of one (batch element, head) with ALL their levels: the L * P locations of a
   // (query, head) are 256 contiguous bytes, read once as whole lines (one workgroup per level fetched every line twice:
   // FETCH_SIZE 189 MB per pass for the 94 MB of locations)
@@ -620,9 +641,9 @@ constexpr int kScanSlab = kScanThreads * kScanPer;
 __global__ __launch_bounds__(kScanThreads) void msda_bin_scan_kernel(
     const int64_t* __restrict__ shapes, const int* __restrict__ counts, int* __restrict__ cursor,
     int4* __restrict__ desc, int* __restrict__ n_chunks, int* __restrict__ group_start, int B, int H, int L) {
-  __shared__ LevelTab t;
+  __shared__ TileLevels t;
   __shared__ int s_wsum[kScanThreads / 64], s_wchk[kScanThreads / 64];
-  build_tab(t, shapes, L);
+  load_levels(t, shapes, L);
   const int nbins = B * t.T * H;
   const int base = (int)blockIdx.x * kScanSlab;
   if (base >= nbins) return;
@@ -779,13 +800,11 @@ __global__ __launch_bounds__(64 * kTWaves) void msda_bwd_tile_kernel(
       aw_cur = attw[s_cur];
     }
     s_nxt = rec_at_batch(base + 128);
-    const float x = pix(xy.x, Wl), y = pix(xy.y, Hl);
-    const int h0 = (int)floorf(y), w0 = (int)floorf(x);
-    const float lh = y - h0, lw = x - w0;
-    const float hh = (1.f - lh) * aw, lha = lh * aw;
+    const Cell c = cell(xy.x, xy.y, Hl, Wl);           // (binned samples are inside; the window is clipped at the flush)
+    const float hh = (1.f - c.lh) * aw, lha = c.lh * aw, lw = c.lw;
     __builtin_amdgcn_wave_barrier();                   // the previous batch's reads of s_par are done (in-order LDS)
     s_par[wave][lane] = make_float4(hh * (1.f - lw), lha * (1.f - lw), hh * lw, lha * lw);
-    const int line = min(max(h0 + 1 - ty * kTile, 0), kTile - 1) * kWin + min(max(w0 + 1 - tx * kTile, 0), kTile - 1);
+    const int line = min(max(c.h0 + 1 - ty * kTile, 0), kTile - 1) * kWin + min(max(c.w0 + 1 - tx * kTile, 0), kTile - 1);
     // one word per sample for the v_readlane hand-off: byte offset of its grad_out line (a multiple of 128) | window line
     const int pack = ((int)gm.at(s / LP) * (kCh * 4)) | line;
     __builtin_amdgcn_wave_barrier();
@@ -872,13 +891,12 @@ __global__ __launch_bounds__(kThreads) void msda_bwd_locw_kernel(
     const float* __restrict__ grad_out, float* __restrict__ grad_loc, float* __restrict__ grad_w, int Nv,
     int H, int Nq, int L, int P, int64_t n_items, int nblocks, int head_major, Prep pr, GoMap gm) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ GLevels lv;
+  __shared__ Levels lv;
   __shared__ float s_dot[kItems];
   const int LP = L * P;
   ItemMap im;
   if (!item_map(im, blockIdx.x, nblocks, n_items, H, head_major)) return;
   load_levels(lv, shapes, lsi, L);
-  __syncthreads();
   const int nvalid = im.nvalid;
   stage_records<kThreads>(Prep{}, loc, attw, lv, smem, im, H, Nq, L, P);     // saved (prepared) operands
   corner_records<kThreads, true>(lv, smem, im, Nv, H, Nq, L, P);
@@ -906,12 +924,9 @@ __global__ __launch_bounds__(kThreads) void msda_bwd_locw_kernel(
     float gx = 0.f, gy = 0.f, gw = 0.f;
     if (meta >= 0) {
       const int l = meta >> 4;
-      const float lh = a.x, lw = a.y, w = a.z, hh = 1.f - lh, hw = 1.f - lw;
       const float d00 = (meta & 1) ? d.x : 0.f, d01 = (meta & 2) ? d.y : 0.f, d10 = (meta & 4) ? d.z : 0.f,
                   d11 = (meta & 8) ? d.w : 0.f;
-      gw = hh * hw * d00 + hh * lw * d01 + lh * hw * d10 + lh * lw * d11;
-      gx = w * lv.Wl[l] * (-hh * d00 + hh * d01 - lh * d10 + lh * d11);
-      gy = w * lv.Hl[l] * (-hw * d00 - lw * d01 + hw * d10 + lw * d11);
+      sample_grads(a.x, a.y, a.z, lv.Wl[l], lv.Hl[l], d00, d01, d10, d11, gx, gy, gw);
     }
     if (!fused) {
       const int64_t e = im.at(itx) * LP + lp;
@@ -923,24 +938,8 @@ __global__ __launch_bounds__(kThreads) void msda_bwd_locw_kernel(
   }
   if (!fused) return;
   __syncthreads();
-  // softmax backward: g_logit = w * (g_w - sum_j w_j g_w_j);  d loc / d off = 1 / (W_l, H_l)
-  for (int itx = threadIdx.x; itx < nvalid; itx += kThreads) {
-    float dot = 0.f;
-    for (int lp = 0; lp < LP; ++lp) {
-      const float* r = smem + rec_at(itx, lp, LP);
-      dot += r[3] * r[2];
-    }
-    s_dot[itx] = dot;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < nvalid * LP; i += kThreads) {
-    const int itx = i / LP, lp = i - itx * LP;
-    const float4 a = reinterpret_cast<const float4*>(smem + rec_at(itx, lp, LP))[0];
-    const int64_t raw = raw_index(im.at(itx), lp, H, Nq, LP, pr.Qn);
-    const int l = lp / P;
-    pr.g_logit_raw[raw] = a.w * (a.z - s_dot[itx]);
-    reinterpret_cast<float2*>(pr.g_off_raw)[raw] = make_float2(a.x / (float)lv.Wl[l], a.y / (float)lv.Hl[l]);
-  }
+  store_raw_grads<kThreads>(pr, lv, s_dot, nvalid, H, Nq, L, P, [&](int it) { return im.at(it); },
+                            [&](int it, int lp) { return reinterpret_cast<const float4*>(smem + rec_at(it, lp, LP))[0]; });
 }
 
 // workspace layout of the binned backward (all int32): [counts: nbins_bound][cursor: nbins_bound][n_chunks: 4][group starts: B*H+1]
@@ -977,7 +976,7 @@ inline BinPlan bin_plan(int B, int Nv, int H, int Nq, int L, int P) {
 
 inline bool msda_bad(int B, int Nv, int H, int C, int Nq, int L, int P) {
   if ((int64_t)B * Nv * H * kCh * 4 >= (1ll << 32)) return true;   // 32-bit corner byte offsets into `value`
-  if (L > kGLv) return true;
+  if (L > kMaxL) return true;
   return B < 0 || Nv < 0 || H <= 0 || C != kCh || Nq < 0 || L <= 0 || P <= 0 || L * P > kMaxLP;
 }
 
@@ -1000,6 +999,46 @@ inline void gather_grid(int64_t n_items, int H, int& nblocks, int& grid) {
     nblocks = (int)((n_items + kItems - 1) / kItems);
     grid = ((nblocks + 7) / 8) * 8;
   }
+}
+
+// The kernels address `value` with 32-bit byte offsets, so ONE launch covers at most 4 GiB of it.  A call with a larger
+// `value` tensor (many frames x batch x cameras at once) is split over batch elements: each launch gets its own base
+// pointers, the results are the same.  -> batch elements per launch, 0 when a single element does not fit.
+inline int batch_per_launch(int B, int Nv, int H) {
+  const int64_t per = (int64_t)Nv * H * kCh * 4;
+  if (per <= 0) return B > 0 ? B : 1;
+  const int64_t fit = ((1ll << 32) - 1) / per;
+  return (int)(fit < B ? fit : (B > 0 ? B : 1));
+}
+
+// One launch's share of a split call: batch rows [r0, r0 + n) of `value` and the operands, batch elements from b0.  A
+// batch element has 1 row, or Qn (the queue entries of the fused entry points, never split apart).  Base pointers move
+// only through row() / elem().
+struct BatchChunk {
+  int64_t b0, r0;            // first batch element, first batch row
+  int n;                     // batch rows of this launch
+  int64_t value, loc, w, out;   // floats per batch row: value [Nv, H, 32], loc [Nq, H, L, P, 2], w [Nq, H, L, P], out [Nq, H*32]
+  template <class T> T* row(T* p, int64_t stride) const { return p + r0 * stride; }
+  template <class T> T* elem(T* p, int64_t stride) const { return p + b0 * stride; }   // merged queue: one out row per ELEMENT
+};
+
+// launch(chunk) for every chunk of `B` batch elements of `rows` batch rows each (a workspace is reused: the launches of
+// one stream run in order); stops at the first error
+template <class Launch>
+inline int for_batch_chunks(int B, int rows, int Nv, int H, int Nq, int L, int P, Launch launch) {
+  const int cb = batch_per_launch(B * rows, Nv, H) / rows;         // whole batch elements per launch
+  if (cb <= 0) return VIDAR_ERR_BAD_ARG;
+  const int64_t is = (int64_t)Nq * H, LP = (int64_t)L * P;         // items per batch row, samples per item
+  BatchChunk c{0, 0, 0, (int64_t)Nv * H * kCh, is * LP * 2, is * LP, is * kCh};
+  int b0 = 0;
+  do {
+    const int nb = B - b0 < cb ? B - b0 : cb;
+    c.b0 = b0; c.r0 = (int64_t)b0 * rows; c.n = nb * rows;
+    const int rc = launch(c);
+    if (rc != 0) return rc;
+    b0 += nb;
+  } while (b0 < B);
+  return 0;
 }
 
 }  // namespace
@@ -1100,33 +1139,15 @@ static bool prep_bad(int bs, int Qn, int R, int mode, int L, int P) {
          (mode == 1 && P % R != 0);
 }
 
-// The kernels address `value` with 32-bit byte offsets, so ONE launch covers at most 4 GiB of it.  A call with a larger
-// `value` tensor (many frames x batch x cameras at once) is split over batch elements: each launch gets its own base
-// pointers, the results are the same.  -> batch elements per launch, 0 when a single element does not fit.
-static int batch_per_launch(int B, int Nv, int H) {
-  const int64_t per = (int64_t)Nv * H * kCh * 4;
-  if (per <= 0) return B > 0 ? B : 1;
-  const int64_t fit = ((1ll << 32) - 1) / per;
-  return (int)(fit < B ? fit : (B > 0 ? B : 1));
-}
-
 int vidar_msda_fwd_f32(const float* value, const int64_t* spatial_shapes,
                        const int64_t* level_start_index, const float* sampling_loc,
                        const float* attn_weight, float* out, int B, int Nv, int H, int C, int Nq,
                        int L, int P, void* stream) {
   VIDAR_ENTER();
-  const int cb = batch_per_launch(B, Nv, H);
-  if (cb <= 0) return VIDAR_ERR_BAD_ARG;
-  const int64_t vs = (int64_t)Nv * H * kCh, is = (int64_t)Nq * H, LP = (int64_t)L * P;
-  int b0 = 0;
-  do {
-    const int nb = B - b0 < cb ? B - b0 : cb;
-    const int rc = msda_fwd_launch(value + b0 * vs, spatial_shapes, level_start_index, sampling_loc + b0 * is * LP * 2,
-                                   attn_weight + b0 * is * LP, out + b0 * is * kCh, nb, Nv, H, C, Nq, L, P, Prep{}, stream);
-    if (rc != 0) return rc;
-    b0 += nb;
-  } while (b0 < B);
-  return 0;
+  return for_batch_chunks(B, 1, Nv, H, Nq, L, P, [&](const BatchChunk& c) {
+    return msda_fwd_launch(c.row(value, c.value), spatial_shapes, level_start_index, c.row(sampling_loc, c.loc),
+                           c.row(attn_weight, c.w), c.row(out, c.out), c.n, Nv, H, C, Nq, L, P, Prep{}, stream);
+  });
 }
 
 size_t vidar_msda_bwd_workspace_bytes(int B, int Nv, int H, int Nq, int L, int P) {
@@ -1141,20 +1162,12 @@ int vidar_msda_bwd_f32(const float* value, const int64_t* spatial_shapes,
                        float* grad_sampling_loc, float* grad_attn_weight, int B, int Nv, int H, int C,
                        int Nq, int L, int P, void* workspace, size_t workspace_bytes, void* stream) {
   VIDAR_ENTER();
-  const int cb = batch_per_launch(B, Nv, H);
-  if (cb <= 0) return VIDAR_ERR_BAD_ARG;
-  const int64_t vs = (int64_t)Nv * H * kCh, is = (int64_t)Nq * H, LP = (int64_t)L * P;
-  int b0 = 0;
-  do {                                         // (the workspace is reused: the launches of one stream run in order)
-    const int nb = B - b0 < cb ? B - b0 : cb;
-    const int rc = msda_bwd_launch(value + b0 * vs, spatial_shapes, level_start_index, sampling_loc + b0 * is * LP * 2,
-                                   attn_weight + b0 * is * LP, grad_out + b0 * is * kCh, grad_value + b0 * vs,
-                                   grad_sampling_loc + b0 * is * LP * 2, grad_attn_weight + b0 * is * LP, nb, Nv, H, C, Nq,
-                                   L, P, workspace, workspace_bytes, Prep{}, stream);
-    if (rc != 0) return rc;
-    b0 += nb;
-  } while (b0 < B);
-  return 0;
+  return for_batch_chunks(B, 1, Nv, H, Nq, L, P, [&](const BatchChunk& c) {
+    return msda_bwd_launch(c.row(value, c.value), spatial_shapes, level_start_index, c.row(sampling_loc, c.loc),
+                           c.row(attn_weight, c.w), c.row(grad_out, c.out), c.row(grad_value, c.value),
+                           c.row(grad_sampling_loc, c.loc), c.row(grad_attn_weight, c.w), c.n, Nv, H, C, Nq, L, P,
+                           workspace, workspace_bytes, Prep{}, stream);
+  });
 }
 
 int vidar_msda_fused_fwd_f32(const float* value, const int64_t* spatial_shapes,
@@ -1165,24 +1178,14 @@ int vidar_msda_fused_fwd_f32(const float* value, const int64_t* spatial_shapes,
   if (prep_bad(bs, Qn, R, mode, L, P) || (merge_queue != 0 && merge_queue != 1)) return VIDAR_ERR_BAD_ARG;
   if ((int64_t)bs * Qn * Nq * H == 0) return msda_bad(bs * Qn, Nv, H, C, Nq, L, P) ? VIDAR_ERR_BAD_ARG : 0;
   if (!off_raw || !logit_raw || !ref || !loc_out || !w_out) return VIDAR_ERR_BAD_ARG;   // (empty tensors are NULL)
-  const int cb = batch_per_launch(bs * Qn, Nv, H) / Qn;            // whole batch items (Qn queue entries each) per launch
-  if (cb <= 0) return VIDAR_ERR_BAD_ARG;
-  const int64_t vs = (int64_t)Nv * H * kCh, is = (int64_t)Nq * H, LP = (int64_t)L * P;
-  int b0 = 0;
-  do {
-    const int nb = bs - b0 < cb ? bs - b0 : cb;
-    const int64_t q0 = (int64_t)b0 * Qn;                             // first (batch, queue) row of this launch
+  return for_batch_chunks(bs, Qn, Nv, H, Nq, L, P, [&](const BatchChunk& c) {
     Prep pr{};
-    pr.off_raw = off_raw + q0 * is * LP * 2; pr.logit_raw = logit_raw + q0 * is * LP; pr.ref = ref + q0 * Nq * R * 2;
-    pr.loc_out = loc_out + q0 * is * LP * 2; pr.w_out = w_out + q0 * is * LP;
+    pr.off_raw = c.row(off_raw, c.loc); pr.logit_raw = c.row(logit_raw, c.w); pr.ref = c.row(ref, (int64_t)Nq * R * 2);
+    pr.loc_out = c.row(loc_out, c.loc); pr.w_out = c.row(w_out, c.w);
     pr.Qn = Qn; pr.R = R; pr.mode = mode; pr.merge = merge_queue;
-    float* out_b = out + (merge_queue ? (int64_t)b0 : q0) * is * kCh;          // merged: one output row block per batch row
-    const int rc = msda_fwd_launch(value + q0 * vs, spatial_shapes, level_start_index, nullptr, nullptr, out_b,
-                                   nb * Qn, Nv, H, C, Nq, L, P, pr, stream);
-    if (rc != 0) return rc;
-    b0 += nb;
-  } while (b0 < bs);
-  return 0;
+    return msda_fwd_launch(c.row(value, c.value), spatial_shapes, level_start_index, nullptr, nullptr,
+                           merge_queue ? c.elem(out, c.out) : c.row(out, c.out), c.n, Nv, H, C, Nq, L, P, pr, stream);
+  });
 }
 
 int vidar_msda_fused_bwd_f32(const float* value, const int64_t* spatial_shapes,
@@ -1196,24 +1199,15 @@ int vidar_msda_fused_bwd_f32(const float* value, const int64_t* spatial_shapes,
   if (bs == 0) return msda_bwd_launch(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out,
                                       grad_value, nullptr, nullptr, 0, Nv, H, C, Nq, L, P, workspace, workspace_bytes,
                                       Prep{}, stream);
-  const int cb = batch_per_launch(bs * Qn, Nv, H) / Qn;
-  if (cb <= 0) return VIDAR_ERR_BAD_ARG;
-  const int64_t vs = (int64_t)Nv * H * kCh, is = (int64_t)Nq * H, LP = (int64_t)L * P;
-  int b0 = 0;
-  do {
-    const int nb = bs - b0 < cb ? bs - b0 : cb;
-    const int64_t q0 = (int64_t)b0 * Qn;
+  return for_batch_chunks(bs, Qn, Nv, H, Nq, L, P, [&](const BatchChunk& c) {
     Prep pr{};
-    pr.g_off_raw = grad_off_raw + q0 * is * LP * 2; pr.g_logit_raw = grad_logit_raw + q0 * is * LP; pr.Qn = Qn;
+    pr.g_off_raw = c.row(grad_off_raw, c.loc); pr.g_logit_raw = c.row(grad_logit_raw, c.w); pr.Qn = Qn;
     pr.merge = merge_queue;
-    const int rc = msda_bwd_launch(value + q0 * vs, spatial_shapes, level_start_index, sampling_loc + q0 * is * LP * 2,
-                                   attn_weight + q0 * is * LP, grad_out + (merge_queue ? (int64_t)b0 : q0) * is * kCh,
-                                   grad_value + q0 * vs, nullptr,
-                                   nullptr, nb * Qn, Nv, H, C, Nq, L, P, workspace, workspace_bytes, pr, stream);
-    if (rc != 0) return rc;
-    b0 += nb;
-  } while (b0 < bs);
-  return 0;
+    return msda_bwd_launch(c.row(value, c.value), spatial_shapes, level_start_index, c.row(sampling_loc, c.loc),
+                           c.row(attn_weight, c.w), merge_queue ? c.elem(grad_out, c.out) : c.row(grad_out, c.out),
+                           c.row(grad_value, c.value), nullptr, nullptr, c.n, Nv, H, C, Nq, L, P, workspace,
+                           workspace_bytes, pr, stream);
+  });
 }
 
 }  // extern "C"

@@ -62,12 +62,13 @@ def _msda_backward(value, shapes, lsi, loc, w, grad_out, binned=None):
     return gv, gl, gw
 
 
-def _prep(value, shapes, lsi, loc, w):
+def _prep(value, shapes, lsi, *operands):
+    """-> value, shapes, lsi and the float operands as the C entry points read them: fp32 / int64, contiguous, on value's device"""
     if not value.is_cuda:
         raise RuntimeError("MultiScaleDeformableAttnFunction needs CUDA tensors (no CPU fallback)")
     f = lambda t: t.float().contiguous()
     i = lambda t: t.to(device=value.device, dtype=torch.int64).contiguous()
-    return f(value), i(shapes), i(lsi), f(loc), f(w)
+    return (f(value), i(shapes), i(lsi), *map(f, operands))
 
 
 class MultiScaleDeformableAttnFunction_fp32(Function):
@@ -143,9 +144,7 @@ class FusedDeformAttnFunction(Function):
     @staticmethod
     def forward(ctx, value, shapes, lsi, off_raw, logit_raw, ref, Qn, L, P, mode, merge_queue=False):
         ctx.in_dtypes = (value.dtype, off_raw.dtype, logit_raw.dtype)
-        f = lambda t: t.float().contiguous()
-        i = lambda t: t.to(device=value.device, dtype=torch.int64).contiguous()
-        value, off_raw, logit_raw, ref, shapes, lsi = f(value), f(off_raw), f(logit_raw), f(ref), i(shapes), i(lsi)
+        value, shapes, lsi, off_raw, logit_raw, ref = _prep(value, shapes, lsi, off_raw, logit_raw, ref)
         Bq, Nv, H, C = value.shape
         bs, Nq = off_raw.shape[:2]
         R = ref.shape[2]
