@@ -375,6 +375,8 @@ int vidar_ray_force_streamed(int on);
  * itself is a GEMM of weight [Cout, C*kh*kw] with the column matrix built here.
  *   x [N,C,H,W], offset [N,2*kh*kw,Ho,Wo] ((dy,dx) per tap), mask [N,kh*kw,Ho,Wo],
  *   cols / grad_cols [N, C*kh*kw, Ho*Wo].  deform_groups == 1.
+ *   kh*kw <= 9 (VIDAR_ERR_BAD_ARG beyond).  Any W >= 1: the kernels read a cell's two corner columns with one 8-byte
+ *   load per row; a one-column image runs the same kernel bodies with single 4-byte loads.
  * col2im: grad_offset / grad_mask written; grad_x by one of two strategies chosen through `workspace`:
  *   NULL  : zeroed by the call, then one fp32 atomic per (channel, tap, pixel, corner);
  *   else  : the sampling positions are shared by all channels (deform_groups == 1), so the call sorts the

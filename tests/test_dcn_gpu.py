@@ -10,24 +10,22 @@ from oracle import dcn as D
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("N,C,Cout,H,W,stride", [(2, 8, 6, 9, 11, 1), (1, 16, 16, 12, 10, 2), (1, 3, 4, 5, 5, 1),
-                                                 (2, 40, 8, 58, 100, 1),       # stage-3 feature map size
-                                                 (1, 20, 4, 6, 2, 1)])         # narrowest image of the pair-load kernels
-def test_dcn_fwd_bwd(N, C, Cout, H, W, stride):
+def _fwd_bwd(N, C, Cout, H, W, stride, kh=3, kw=3, pad=1, dil=1):
     from vidar_amd.plugin.backbones import modulated_deform_conv2d
     g = torch.Generator().manual_seed(N * 100 + C)
-    Ho = (H + 2 - 3) // stride + 1; Wo = (W + 2 - 3) // stride + 1
+    K = kh * kw
+    Ho = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1; Wo = (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
     x = torch.randn(N, C, H, W, generator=g, dtype=torch.float64)
-    off = torch.randn(N, 18, Ho, Wo, generator=g, dtype=torch.float64) * 1.5     # leaves the image at borders
-    mask = torch.rand(N, 9, Ho, Wo, generator=g, dtype=torch.float64)
-    wgt = torch.randn(Cout, C, 3, 3, generator=g, dtype=torch.float64) * 0.2
+    off = torch.randn(N, 2 * K, Ho, Wo, generator=g, dtype=torch.float64) * 1.5     # leaves the image at borders
+    mask = torch.rand(N, K, Ho, Wo, generator=g, dtype=torch.float64)
+    wgt = torch.randn(Cout, C, kh, kw, generator=g, dtype=torch.float64) * 0.2
     bias = torch.randn(Cout, generator=g, dtype=torch.float64)
     leaves = [t.clone().requires_grad_(True) for t in (x, off, mask, wgt, bias)]
-    ref = D.modulated_deform_conv2d(*leaves, stride=stride, padding=1)
+    ref = D.modulated_deform_conv2d(*leaves, stride=stride, padding=pad, dilation=dil)
     gout = torch.randn(ref.shape, generator=g, dtype=torch.float64)
     gref = torch.autograd.grad((ref * gout).sum(), leaves)
     dl = [t.float().cuda().requires_grad_(True) for t in (x, off, mask, wgt, bias)]
-    out = modulated_deform_conv2d(*dl, stride=stride, padding=1)
+    out = modulated_deform_conv2d(*dl, stride=stride, padding=pad, dilation=dil)
     torch.testing.assert_close(out.cpu().double(), ref.detach(), rtol=1e-4, atol=1e-4)
     got = torch.autograd.grad((out * gout.float().cuda()).sum(), dl)
     for a, b, nm in zip(got, gref, ["x", "offset", "mask", "weight", "bias"]):
@@ -35,18 +33,55 @@ def test_dcn_fwd_bwd(N, C, Cout, H, W, stride):
                                    msg=lambda m: nm + ": " + m)
 
 
-def test_one_column_image_equals_the_same_image_padded_with_a_zero_column():
-    """W == 1 takes the scalar-load kernels (the pair-load ones need two columns; the grid_sample oracle cannot
-    express a one-column image): zero padding makes it equal to the W == 2 image with an empty second column."""
+@pytest.mark.parametrize("N,C,Cout,H,W,stride", [(2, 8, 6, 9, 11, 1), (1, 16, 16, 12, 10, 2), (1, 3, 4, 5, 5, 1),
+                                                 (2, 40, 8, 58, 100, 1),       # stage-3 feature map size
+                                                 (1, 20, 4, 6, 2, 1)])         # narrowest image of the pair-load kernels
+def test_dcn_fwd_bwd(N, C, Cout, H, W, stride):
+    _fwd_bwd(N, C, Cout, H, W, stride)
+
+
+@pytest.mark.parametrize("kh,kw,pad,dil", [(2, 3, 1, 1), (3, 3, 2, 2)])
+def test_dcn_fwd_bwd_tap_row_column_split(kh, kw, pad, dil):
+    """tap t sits at row t / kw, column t - (t / kw) * kw of the kernel, dil pixels apart: kh != kw and dilation 2
+    (these take the global gather; the LDS window kernel is 3x3 / dilation 1 only)"""
+    _fwd_bwd(1, 5, 4, 7, 6, 1, kh, kw, pad, dil)
+
+
+def test_more_than_nine_taps_is_a_bad_argument():
+    """kh * kw <= 9 is the limit of both entry points: VIDAR_ERR_BAD_ARG, which `check` raises as ValueError"""
+    from vidar_amd.plugin.backbones import dcn_col2im, modulated_deform_conv2d
+    kh, kw, Ho, Wo = 4, 3, 6, 6                         # 7 x 6 image, padding 1
+    x = torch.randn(1, 5, 7, 6).cuda()
+    off = torch.zeros(1, 2 * kh * kw, Ho, Wo).cuda()
+    mask = torch.ones(1, kh * kw, Ho, Wo).cuda()
+    with pytest.raises(ValueError, match="dcn_im2col"):
+        modulated_deform_conv2d(x, off, mask, torch.randn(4, 5, kh, kw).cuda(), None, stride=1, padding=1)
+    gcols = torch.randn(1, 5 * kh * kw, Ho * Wo).cuda()
+    for gather in (True, False):
+        with pytest.raises(ValueError, match="dcn_col2im"):
+            dcn_col2im(gcols, x, off, mask, kh, kw, 1, 1, 1, Ho, Wo, gather=gather)
+
+
+@pytest.mark.parametrize("wild", [False, True])
+@pytest.mark.parametrize("C", [6, 19])
+def test_one_column_image_equals_the_same_image_padded_with_a_zero_column(C, wild):
+    """W == 1 runs the same kernel bodies as every other width with single 4-byte loads in place of the 8-byte pair
+    loads, which need two columns (the grid_sample oracle cannot express a one-column image): zero padding makes it
+    equal to the W == 2 image with an empty second column.  19 channels: two im2col channel groups (16 + 3), two blocks
+    of 8 channels and a tail of 3 in the offset / mask gradient.  wild: offsets of 2 pixels, one NaN, one far outside."""
     from vidar_amd.plugin.backbones import modulated_deform_conv2d
     g = torch.Generator().manual_seed(11)
-    x1 = torch.randn(2, 6, 5, 1, generator=g).cuda().requires_grad_(True)
-    off = (torch.randn(2, 18, 5, 1, generator=g) * 0.8).cuda().requires_grad_(True)
+    x1 = torch.randn(2, C, 5, 1, generator=g).cuda().requires_grad_(True)
+    off = torch.randn(2, 18, 5, 1, generator=g) * (2.0 if wild else 0.8)
+    if wild:
+        off[0, 4, 1, 0] = float("nan"); off[1, 7, 3, 0] = 1e4
+    off = off.cuda().requires_grad_(True)
     mask = torch.rand(2, 9, 5, 1, generator=g).cuda().requires_grad_(True)
-    wgt = torch.randn(4, 6, 3, 3, generator=g).cuda()
+    wgt = torch.randn(4, C, 3, 3, generator=g).cuda()
     gout = torch.randn(2, 4, 5, 1, generator=g).cuda()
     out1 = modulated_deform_conv2d(x1, off, mask, wgt, None, stride=1, padding=1)
     g1 = torch.autograd.grad((out1 * gout).sum(), [x1, off, mask])
+    assert torch.isfinite(out1).all() and all(torch.isfinite(t).all() for t in g1)
     x2 = torch.cat([x1.detach(), torch.zeros_like(x1)], -1).requires_grad_(True)               # [.., 5, 2]
     pad = lambda t, v: torch.cat([t.detach(), torch.full_like(t, v)], -1).requires_grad_(True)  # second output column unused
     off2, mask2 = pad(off, 0.0), pad(mask, 0.0)
@@ -73,7 +108,8 @@ def test_im2col_far_and_nan_offsets_contribute_nothing():
     torch.testing.assert_close(out[..., ok.cuda()], ref[..., ok.cuda()], rtol=1e-4, atol=1e-4)
 
 
-@pytest.mark.parametrize("N,C,H,W,stride", [(2, 19, 9, 11, 1), (1, 32, 29, 50, 1), (2, 5, 12, 10, 2)])
+@pytest.mark.parametrize("N,C,H,W,stride", [(2, 19, 9, 11, 1), (1, 32, 29, 50, 1), (2, 5, 12, 10, 2),
+                                            (2, 19, 5, 1, 1)])              # one column
 def test_col2im_gather_equals_atomic_scatter(N, C, H, W, stride):
     """both grad_x strategies of vidar_dcn_col2im_f32 (workspace / reverse-map gather vs atomics)"""
     from vidar_amd.plugin.backbones import dcn_col2im

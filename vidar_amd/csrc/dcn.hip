@@ -8,7 +8,7 @@
 // these kernels build / differentiate the deformable column matrix:
 //   cols[n, (c*K + t), p] = mask[n,t,p] * bilinear(x[n,c], p_y*s - pad + i*dil + off[n,2t,p],
 //                                                          p_x*s - pad + j*dil + off[n,2t+1,p])
-// with zero padding (a sample counts iff -1 < h < H and -1 < w < W; each corner zero outside).
+// with zero padding (a tap counts iff -1 < h < H and -1 < w < W; each corner zero outside).
 // Layouts: x [N,C,H,W], offset [N,2K,Ho,Wo] ((dy,dx) interleaved per tap), mask [N,K,Ho,Wo],
 // cols [N, C*K, Ho*Wo] -- lanes run over output pixels so column writes, offset/mask reads and
 // (for small offsets) input reads are coalesced; the backward scatter therefore puts neighbouring
@@ -34,11 +34,9 @@ __device__ __forceinline__ PlaneTile xcd_plane_tile(int L, int T, int planes) {
 }
 inline unsigned xcd_plane_grid(int T, int planes) { return 8u * (unsigned)T * (unsigned)((planes + 7) / 8); }
 
-struct Conv {
-  int C, H, W, Ho, Wo, kh, kw, stride, pad, dil;
-};
+struct Conv { int C, H, W, Ho, Wo, kh, kw, stride, pad, dil; };
 
-struct Bil {
+struct Bil {                    // the cell of a sampling position: top-left corner, fractions, which corners exist
   int h0, w0;
   float lh, lw;
   bool in, t, b, l, r;
@@ -53,133 +51,83 @@ __device__ __forceinline__ Bil bil(float h, float w, int H, int W) {
   return q;
 }
 
-__device__ __forceinline__ float sample(const float* __restrict__ im, const Bil& q, int W) {
-  if (!q.in) return 0.f;
-  const float v1 = (q.t && q.l) ? im[q.h0 * W + q.w0] : 0.f;
-  const float v2 = (q.t && q.r) ? im[q.h0 * W + q.w0 + 1] : 0.f;
-  const float v3 = (q.b && q.l) ? im[(q.h0 + 1) * W + q.w0] : 0.f;
-  const float v4 = (q.b && q.r) ? im[(q.h0 + 1) * W + q.w0 + 1] : 0.f;
+// Sampling position of tap t = i * kw + j of output pixel (py, px), (oh, ow) its learned offset.
+struct Pos { float h, w; };
+__device__ __forceinline__ Pos tap_pos(const Conv& g, int py, int px, int t, float oh, float ow) {
+  const int i = t / g.kw, j = t - i * g.kw;
+  return Pos{py * g.stride - g.pad + i * g.dil + oh, px * g.stride - g.pad + j * g.dil + ow};
+}
+
+// f(pixel index, bilinear weight) for each of the cell's four corners that lies inside the image
+template <class F>
+__device__ __forceinline__ void for_corners(const Bil& q, int W, F f) {
   const float hh = 1.f - q.lh, hw = 1.f - q.lw;
-  return hh * hw * v1 + hh * q.lw * v2 + q.lh * hw * v3 + q.lh * q.lw * v4;
+  const int tl = q.h0 * W + q.w0;
+  if (q.t && q.l) f(tl, hh * hw);
+  if (q.t && q.r) f(tl + 1, hh * q.lw);
+  if (q.b && q.l) f(tl + W, q.lh * hw);
+  if (q.b && q.r) f(tl + W + 1, q.lh * q.lw);
 }
 
-// A thread owns one output pixel and kCG consecutive channels: the 9 sampling footprints (index
-// arithmetic + offset / mask loads) are computed once and reused for every channel of the group.
-constexpr int kCG = 8;
-constexpr int kMaxTaps = 9;
+constexpr int kMaxTaps = 9;    // largest kh * kw the entry points accept
 
-struct Foot {
-  Bil q[kMaxTaps];
-  float m[kMaxTaps];
-};
-
-__device__ __forceinline__ Foot footprints(const float* __restrict__ offset,
-                                           const float* __restrict__ mask, int n, int p, const Conv& g) {
-  const int P = g.Ho * g.Wo, K = g.kh * g.kw;
-  const int py = p / g.Wo, px = p % g.Wo;
-  Foot f;
-#pragma unroll
-  for (int t = 0; t < kMaxTaps; ++t) {
-    if (t < K) {
-      const int i = t / g.kw, j = t % g.kw;
-      const float h = py * g.stride - g.pad + i * g.dil + offset[((size_t)n * 2 * K + 2 * t) * P + p];
-      const float w = px * g.stride - g.pad + j * g.dil + offset[((size_t)n * 2 * K + 2 * t + 1) * P + p];
-      f.q[t] = bil(h, w, g.H, g.W);
-      f.m[t] = mask[((size_t)n * K + t) * P + p];
-    } else {
-      f.q[t] = bil(-2.f, -2.f, g.H, g.W);
-      f.m[t] = 0.f;
-    }
-  }
-  return f;
-}
-
-// grid: (ceil(P/256), ceil(C/kCG), N)
-__global__ __launch_bounds__(256) void dcn_im2col_kernel(const float* __restrict__ x,
-                                                         const float* __restrict__ offset,
-                                                         const float* __restrict__ mask,
-                                                         float* __restrict__ cols, Conv g) {
-  const int P = g.Ho * g.Wo, K = g.kh * g.kw;
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= P) return;
-  const int n = blockIdx.z, c0 = blockIdx.y * kCG;
-  const Foot f = footprints(offset, mask, n, p, g);
-  for (int c = c0; c < min(c0 + kCG, g.C); ++c) {
-    const float* im = x + ((size_t)n * g.C + c) * g.H * g.W;
-    float* out = cols + ((size_t)n * g.C + c) * K * P + p;
-#pragma unroll
-    for (int t = 0; t < kMaxTaps; ++t)
-      if (t < K) out[(size_t)t * P] = sample(im, f.q[t], g.W) * f.m[t];
-  }
-}
-
-// im2col, pair-load form (W >= 2).  The four corners of a tap are two horizontally adjacent PAIRS: one 8-byte load
-// per row instead of two 4-byte loads (the kernel sits on the vector memory pipe: 4 gathers + 1 store per column
-// element before, 2 + 1 now), and everything that does not depend on the channel -- clamped pair index, the four
-// weights times the mask, with the zero padding folded into the weights -- is computed once per (pixel, tap) and
-// reused for the kCP channels of the thread's group.  The pair starts at column c0 = clamp(w0, 0, W-2): for
-// w0 == -1 the right corner is element 0 of the pair, for w0 == W-1 the left corner is element 1.
-constexpr int kCP = 16;
+// Pair loads.  The four corners of a tap are two horizontally adjacent PAIRS: one 8-byte load per row instead of two
+// 4-byte loads (im2col sits on the vector memory pipe: 4 gathers + 1 store per column element before, 2 + 1 now), and
+// everything that does not depend on the channel -- clamped pair index, the corner weights with the zero padding
+// folded in -- is computed once per (pixel, tap) and reused for every channel.  The pair starts at column
+// c0 = clamp(w0, 0, W-2): for w0 == -1 the right corner is element 0 of the pair, for w0 == W-1 the left corner is
+// element 1.  A one-column image (PAIR == false) runs the same bodies with c0 = 0, a single 4-byte load per row and
+// element 1 read as zero.
 typedef float pair_t __attribute__((ext_vector_type(2), aligned(4)));
 
-struct PairFoot {
-  int top[kMaxTaps], bot[kMaxTaps];          // element index of the pair in the top / bottom row
-  float wt0[kMaxTaps], wt1[kMaxTaps], wb0[kMaxTaps], wb1[kMaxTaps];
-};
-
-__device__ __forceinline__ PairFoot pair_footprints(const float* __restrict__ offset, const float* __restrict__ mask,
-                                                    int n, int p, const Conv& g) {
-  const Foot f = footprints(offset, mask, n, p, g);
-  PairFoot o;
-#pragma unroll
-  for (int t = 0; t < kMaxTaps; ++t) {
-    const Bil& q = f.q[t];
-    const float m = q.in ? f.m[t] : 0.f;
-    const int c0 = min(max(q.w0, 0), g.W - 2);
-    const int r0 = min(max(q.h0, 0), g.H - 1), r1 = min(max(q.h0 + 1, 0), g.H - 1);
-    // weights of the left / right corner, then their place in the loaded pair
-    const float wl = (q.l ? 1.f - q.lw : 0.f), wr = (q.r ? q.lw : 0.f);
-    const float a0 = q.w0 == c0 ? wl : (q.w0 < c0 ? wr : 0.f);          // w0 == -1: the right corner is element 0
-    const float a1 = q.w0 == c0 ? wr : (q.w0 > c0 ? wl : 0.f);          // w0 == W-1: the left corner is element 1
-    const float ht = (q.t ? 1.f - q.lh : 0.f) * m, hb = (q.b ? q.lh : 0.f) * m;
-    o.top[t] = r0 * g.W + c0; o.bot[t] = r1 * g.W + c0;
-    // a sample outside the image (or NaN) contributes nothing: select, not a product with 0
-    o.wt0[t] = q.in ? ht * a0 : 0.f; o.wt1[t] = q.in ? ht * a1 : 0.f;
-    o.wb0[t] = q.in ? hb * a0 : 0.f; o.wb1[t] = q.in ? hb * a1 : 0.f;
-  }
-  return o;
+template <bool PAIR>
+__device__ __forceinline__ pair_t load_pair(const void* p) {
+  if constexpr (PAIR) return *reinterpret_cast<const pair_t*>(p);
+  else return pair_t{*reinterpret_cast<const float*>(p), 0.f};
 }
 
-// grid: (ceil(P/256), ceil(C/kCP), N)
+struct PairMap {
+  int top, bot;            // element index of the pair in the cell's top / bottom row (rows clamped into the image)
+  bool same, left;         // w0 == c0; w0 < c0 (w0 == -1); neither: w0 == W-1 > c0
+  // place of a (left corner, right corner) coefficient in the loaded pair
+  __device__ __forceinline__ float e0(float cl, float cr) const { return same ? cl : (left ? cr : 0.f); }
+  __device__ __forceinline__ float e1(float cl, float cr) const { return same ? cr : (left ? 0.f : cl); }
+};
+
+__device__ __forceinline__ PairMap pair_map(const Bil& q, int H, int W) {
+  const int c0 = min(max(q.w0, 0), max(W - 2, 0));
+  const int r0 = min(max(q.h0, 0), H - 1), r1 = min(max(q.h0 + 1, 0), H - 1);
+  return PairMap{r0 * W + c0, r1 * W + c0, q.w0 == c0, q.w0 < c0};
+}
+
+// im2col.  grid: xcd_plane_grid(ceil(P/256), ceil(C/kCP) * N)
 // Counters (profiles/r03_pmc_dcn): with the channel loop outside (18 gathers, then 9 column stores per channel) the
 // waves spent 91 % of their cycles in s_waitcnt at 7 % VALU -- loads and stores share gfx9's vmcnt counter and
 // complete out of order with respect to each other, so the compiler has to drain the previous stores before it may
 // consume the next gathers: the store acknowledgement latency is exposed once per (load batch, store batch) round.
 // Hence the TAP loop is outside: per tap the 2 x kCP pair loads of all channels of the group are in flight together
 // (plus the next tap's offsets and mask), then kCP stores -- 9 rounds per thread instead of 16, each twice as big.
+constexpr int kCP = 16;
 struct TapFoot { unsigned top, bot; float wt0, wt1, wb0, wb1; };
 
-__device__ __forceinline__ TapFoot tap_foot(float h, float w, float m, const Conv& g) {
-  const Bil q = bil(h, w, g.H, g.W);
-  const int c0 = min(max(q.w0, 0), g.W - 2);
-  const int r0 = min(max(q.h0, 0), g.H - 1), r1 = min(max(q.h0 + 1, 0), g.H - 1);
+__device__ __forceinline__ TapFoot tap_foot(Pos s, float m, const Conv& g) {
+  const Bil q = bil(s.h, s.w, g.H, g.W);
+  const PairMap pm = pair_map(q, g.H, g.W);
   // weights of the left / right corner, then their place in the loaded pair
   const float wl = (q.l ? 1.f - q.lw : 0.f), wr = (q.r ? q.lw : 0.f);
-  const float a0 = q.w0 == c0 ? wl : (q.w0 < c0 ? wr : 0.f);          // w0 == -1: the right corner is element 0
-  const float a1 = q.w0 == c0 ? wr : (q.w0 > c0 ? wl : 0.f);          // w0 == W-1: the left corner is element 1
+  const float a0 = pm.e0(wl, wr), a1 = pm.e1(wl, wr);
   const float ht = (q.t ? 1.f - q.lh : 0.f) * m, hb = (q.b ? q.lh : 0.f) * m;
   TapFoot f;
-  f.top = (unsigned)(r0 * g.W + c0) * 4u; f.bot = (unsigned)(r1 * g.W + c0) * 4u;      // byte offsets inside a plane
-  // a sample outside the image (or NaN) contributes nothing: select, not a product with 0
+  f.top = (unsigned)pm.top * 4u; f.bot = (unsigned)pm.bot * 4u;      // byte offsets inside a plane
+  // a tap outside the image (or at NaN) contributes nothing: select, not a product with 0
   f.wt0 = q.in ? ht * a0 : 0.f; f.wt1 = q.in ? ht * a1 : 0.f;
   f.wb0 = q.in ? hb * a0 : 0.f; f.wb1 = q.in ? hb * a1 : 0.f;
   return f;
 }
 
-__global__ __launch_bounds__(256) void dcn_im2col_pair_kernel(const float* __restrict__ x,
-                                                              const float* __restrict__ offset,
-                                                              const float* __restrict__ mask,
-                                                              float* __restrict__ cols, Conv g, int nimg) {
+template <bool PAIR>
+__device__ __forceinline__ void im2col_body(const float* __restrict__ x, const float* __restrict__ offset,
+                                            const float* __restrict__ mask, float* __restrict__ cols, const Conv& g, int nimg) {
   const int P = g.Ho * g.Wo, K = g.kh * g.kw;
   // XCD-aware order: the (P / 256) workgroups of one (channel group, image) read the same kCP input planes through nine
   // shifted footprints -- on one XCD they share its L2 (FETCH_SIZE of the 24-image call: 4.6 GB for a 142 MB input before)
@@ -197,14 +145,13 @@ __global__ __launch_bounds__(256) void dcn_im2col_pair_kernel(const float* __res
   const float* msk_n = mask + (size_t)n * K * P + p;
   float oh = off_n[0], ow = off_n[P], m = msk_n[0];
   for (int t = 0; t < K; ++t) {
-    const int i = t / g.kw, j = t - i * g.kw;
-    const TapFoot f = tap_foot(py * g.stride - g.pad + i * g.dil + oh, px * g.stride - g.pad + j * g.dil + ow, m, g);
+    const TapFoot f = tap_foot(tap_pos(g, py, px, t, oh, ow), m, g);
     pair_t a[kCP], b[kCP];
 #pragma unroll
     for (int c = 0; c < kCP; ++c) {
       const char* pl = im + (size_t)(c < nc ? c : 0) * plane * 4;
-      a[c] = *reinterpret_cast<const pair_t*>(pl + f.top);
-      b[c] = *reinterpret_cast<const pair_t*>(pl + f.bot);
+      a[c] = load_pair<PAIR>(pl + f.top);
+      b[c] = load_pair<PAIR>(pl + f.bot);
     }
     if (t + 1 < K) {                                     // the next tap's offsets and mask ride in the same round
       oh = off_n[(size_t)(2 * t + 2) * P]; ow = off_n[(size_t)(2 * t + 3) * P]; m = msk_n[(size_t)(t + 1) * P];
@@ -222,32 +169,42 @@ __global__ __launch_bounds__(256) void dcn_im2col_pair_kernel(const float* __res
   }
 }
 
-// grad wrt input: scatter grad_cols * mask * corner weights (atomics); grid as im2col.  Lanes are
+__global__ __launch_bounds__(256) void dcn_im2col_pair_kernel(                                               // W >= 2
+    const float* __restrict__ x, const float* __restrict__ offset, const float* __restrict__ mask,
+    float* __restrict__ cols, Conv g, int nimg) {
+  im2col_body<true>(x, offset, mask, cols, g, nimg);
+}
+__global__ __launch_bounds__(256) void dcn_im2col_kernel(                                                    // W == 1
+    const float* __restrict__ x, const float* __restrict__ offset, const float* __restrict__ mask,
+    float* __restrict__ cols, Conv g, int nimg) {
+  im2col_body<false>(x, offset, mask, cols, g, nimg);
+}
+
+// grad wrt input: scatter grad_cols * mask * corner weights (atomics), used when the call has no workspace.  A thread
+// owns one output pixel and kCG consecutive channels, a tap's cell is computed once for all of them.  Lanes are
 // neighbouring pixels, so a wave instruction touches only 2-3 lines (atomics cost per instruction x line).
-__global__ __launch_bounds__(256) void dcn_col2im_kernel(const float* __restrict__ grad_cols,
-                                                         const float* __restrict__ offset,
-                                                         const float* __restrict__ mask,
-                                                         float* __restrict__ grad_x, Conv g) {
+// grid: (ceil(P/256), ceil(C/kCG), N)
+constexpr int kCG = 8;
+__global__ __launch_bounds__(256) void dcn_col2im_kernel(const float* __restrict__ grad_cols, const float* __restrict__ offset,
+                                                         const float* __restrict__ mask, float* __restrict__ grad_x, Conv g) {
   const int P = g.Ho * g.Wo, K = g.kh * g.kw;
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= P) return;
-  const int n = blockIdx.z, c0 = blockIdx.y * kCG;
-  const Foot f = footprints(offset, mask, n, p, g);
-  for (int c = c0; c < min(c0 + kCG, g.C); ++c) {
-    float* gim = grad_x + ((size_t)n * g.C + c) * g.H * g.W;
-    const float* gc = grad_cols + ((size_t)n * g.C + c) * K * P + p;
-#pragma unroll
-    for (int t = 0; t < kMaxTaps; ++t) {
-      if (t >= K) continue;
-      const Bil& q = f.q[t];
-      if (!q.in) continue;
-      const float gv = gc[(size_t)t * P] * f.m[t];
+  const int n = blockIdx.z, c0 = blockIdx.y * kCG, nc = min(kCG, g.C - c0);
+  const int py = p / g.Wo, px = p % g.Wo;
+  const size_t plane = (size_t)g.H * g.W, KP = (size_t)K * P;
+  float* gim = grad_x + ((size_t)n * g.C + c0) * plane;
+  const float* gc = grad_cols + ((size_t)n * g.C + c0) * KP + p;
+  for (int t = 0; t < K; ++t) {
+    const size_t o = ((size_t)n * 2 * K + 2 * t) * P + p;
+    const Pos s = tap_pos(g, py, px, t, offset[o], offset[o + P]);
+    const Bil q = bil(s.h, s.w, g.H, g.W);
+    if (!q.in) continue;
+    const float m = mask[((size_t)n * K + t) * P + p];
+    for (int c = 0; c < nc; ++c) {
+      const float gv = gc[(size_t)c * KP + (size_t)t * P] * m;
       if (gv == 0.f) continue;
-      const float hh = 1.f - q.lh, hw = 1.f - q.lw;
-      if (q.t && q.l) unsafeAtomicAdd(gim + q.h0 * g.W + q.w0, hh * hw * gv);
-      if (q.t && q.r) unsafeAtomicAdd(gim + q.h0 * g.W + q.w0 + 1, hh * q.lw * gv);
-      if (q.b && q.l) unsafeAtomicAdd(gim + (q.h0 + 1) * g.W + q.w0, q.lh * hw * gv);
-      if (q.b && q.r) unsafeAtomicAdd(gim + (q.h0 + 1) * g.W + q.w0 + 1, q.lh * q.lw * gv);
+      for_corners(q, g.W, [&](int pix, float w) { unsafeAtomicAdd(gim + (size_t)c * plane + pix, w * gv); });
     }
   }
 }
@@ -272,24 +229,17 @@ __global__ __launch_bounds__(256) void dcn_revmap_kernel(const float* __restrict
   if (p >= P) return;
   const int t = blockIdx.y, n = blockIdx.z;
   const int py = p / g.Wo, px = p % g.Wo;
-  const int i = t / g.kw, j = t % g.kw;
   const size_t o = ((size_t)n * 2 * K + 2 * t) * P + p;
-  const Bil q = bil(py * g.stride - g.pad + i * g.dil + offset[o], px * g.stride - g.pad + j * g.dil + offset[o + P],
-                    g.H, g.W);
+  const Pos s = tap_pos(g, py, px, t, offset[o], offset[o + P]);
+  const Bil q = bil(s.h, s.w, g.H, g.W);
   if (!q.in) return;
   const float m = FILL ? mask[((size_t)n * K + t) * P + p] : 0.f;
-  const float hh = 1.f - q.lh, hw = 1.f - q.lw;
   int* cur = cursor + ((size_t)n * K + t) * HW;      // bins are (image, tap, destination pixel): tap-major lists keep
   const int src = t * P + p;                         // neighbouring destination pixels in step (coalesced gathers)
-  auto put = [&](bool ok, int pix, float w) {
-    if (!ok) return;
+  for_corners(q, g.W, [&](int pix, float w) {
     if (FILL) rec[atomicAdd(cur + pix, 1)] = Entry{src, w * m};
     else atomicAdd(cur + pix, 1);
-  };
-  put(q.t && q.l, q.h0 * g.W + q.w0, hh * hw);
-  put(q.t && q.r, q.h0 * g.W + q.w0 + 1, hh * q.lw);
-  put(q.b && q.l, (q.h0 + 1) * g.W + q.w0, q.lh * hw);
-  put(q.b && q.r, (q.h0 + 1) * g.W + q.w0 + 1, q.lh * q.lw);
+  });
 }
 
 // block per image: counts -> first[] (exclusive prefix, offset by the image's slice of `rec`), cursor = first
@@ -376,9 +326,6 @@ __global__ __launch_bounds__(256) void dcn_col2im_gather_kernel(const float* __r
 // of rows, dword aligned on the global side, 1.5 x slower than 4-byte loads; a 6-pixel halo 13 % slower than 4 or 5;
 // global_load_lds_dword straight into the lane-linear LDS image instead of load + ds_write: 245 -> 237 / 360 -> 328 us, kept).
 // ---------------------------------------------------------------------------------------------
-#ifndef VIDAR_DCN_GLDS
-#define VIDAR_DCN_GLDS 1
-#endif
 #ifndef VIDAR_DCN_GRY
 #define VIDAR_DCN_GRY 2
 #endif
@@ -427,7 +374,6 @@ __global__ __launch_bounds__(256) void dcn_col2im_gather_lds_kernel(
     const int wy0 = tyi * kGTH + g.pad - i - kGHalo - 1, wx0 = txi * kGTW + g.pad - j - kGHalo - 1;
     const float* gct = gc + (size_t)t * P;
     __syncthreads();                          // the previous tap's gathers are done
-#if VIDAR_DCN_GLDS
     // staging straight into LDS (global_load_lds_dword: destination = wave-uniform base + lane x 4 -- window position
     // e = thread + k * 256 is lane-linear by construction); positions outside the image are never read and stay as they are
     {
@@ -447,35 +393,6 @@ __global__ __launch_bounds__(256) void dcn_col2im_gather_lds_kernel(
         }
       }
     }
-#else
-    // staging in rounds of 4 window positions per thread: their 4 x kGLC loads are requested before the first LDS store.
-    // (float4 pieces of rows -- the global side is only dword aligned -- measured 1.5 x SLOWER than these 4-byte loads,
-    //  profiles/r06_kbench_dcn_col2im_lds_gather.log)
-#pragma unroll
-    for (int k0 = 0; k0 < kGPos; k0 += 4) {
-      float v[4][kGLC];
-      bool ok[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int e = threadIdx.x + (k0 + u) * 256;
-        const int r = e / kGWP, cc = e - r * kGWP;
-        const int sy = wy0 + r, sx = wx0 + cc;
-        ok[u] = e < kGWS && sy >= 0 && sy < g.Ho && sx >= 0 && sx < g.Wo && cc < kGWW;
-        const int off = ok[u] ? sy * g.Wo + sx : 0;
-#pragma unroll
-        for (int c = 0; c < kGLC; ++c) v[u][c] = gct[(size_t)(c < nc ? c : 0) * KP + off];
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int e = threadIdx.x + (k0 + u) * 256;
-        if (e < kGWS) {
-#pragma unroll
-          for (int c = 0; c < kGLC; ++c) s_gc[c * kGWS + e] = ok[u] ? v[u][c] : 0.f;
-        }
-      }
-    }
-#endif
     __syncthreads();
     if (dx >= g.W) continue;
 #pragma unroll
@@ -518,46 +435,41 @@ int g_dcn_variant = 1;         // bit 0: col2im gathers through the LDS window k
 
 // grad wrt offset and mask: thread per (n, tap, pixel), loop over channels (no atomics)
 // grid: (ceil(P/256), K, N)
-__global__ __launch_bounds__(256) void dcn_col2im_coord_kernel(
-    const float* __restrict__ grad_cols, const float* __restrict__ x,
-    const float* __restrict__ offset, const float* __restrict__ mask,
-    float* __restrict__ grad_offset, float* __restrict__ grad_mask, Conv g) {
+template <bool PAIR>
+__device__ __forceinline__ void col2im_coord_body(const float* __restrict__ grad_cols, const float* __restrict__ x,
+                                                  const float* __restrict__ offset, const float* __restrict__ mask,
+                                                  float* __restrict__ grad_offset, float* __restrict__ grad_mask,
+                                                  const Conv& g) {
   const int P = g.Ho * g.Wo, K = g.kh * g.kw;
   // (the XCD-aware order of the other kernels -- the K workgroups of a pixel block on one XCD -- measured 8 % slower here)
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= P) return;
   const int t = blockIdx.y, n = blockIdx.z;
   const int py = p / g.Wo, px = p % g.Wo;
-  const int i = t / g.kw, j = t % g.kw;
   const size_t o = ((size_t)n * 2 * K + 2 * t) * P + p;
-  const float h = py * g.stride - g.pad + i * g.dil + offset[o];
-  const float w = px * g.stride - g.pad + j * g.dil + offset[o + P];
+  const Pos s = tap_pos(g, py, px, t, offset[o], offset[o + P]);
   const float m = mask[((size_t)n * K + t) * P + p];
-  const Bil q = bil(h, w, g.H, g.W);
+  const Bil q = bil(s.h, s.w, g.H, g.W);
   float gh = 0.f, gw = 0.f, gm = 0.f;
-  if (q.in && g.W >= 2) {
-    // pair loads like dcn_im2col_pair_kernel: per row one 8-byte load; the corner -> pair-element map and the zero
-    // padding are folded into 12 coefficients computed once per (pixel, tap)
+  if (q.in) {
+    // pair loads like im2col: per row one load; the corner -> pair-element map and the zero padding are folded into
+    // 12 coefficients computed once per (pixel, tap)
     const float hh = 1.f - q.lh, hw = 1.f - q.lw;
-    const int c0 = min(max(q.w0, 0), g.W - 2);
-    const int top = min(max(q.h0, 0), g.H - 1) * g.W + c0, bot = min(max(q.h0 + 1, 0), g.H - 1) * g.W + c0;
+    const PairMap pm = pair_map(q, g.H, g.W);
     const float tl = (q.t && q.l) ? 1.f : 0.f, tr = (q.t && q.r) ? 1.f : 0.f;
     const float bl = (q.b && q.l) ? 1.f : 0.f, br = (q.b && q.r) ? 1.f : 0.f;
-    const bool same = q.w0 == c0, left = q.w0 < c0;          // left: w0 == -1 (right corner is element 0)
-    auto e0 = [&](float cl, float cr) { return same ? cl : (left ? cr : 0.f); };
-    auto e1 = [&](float cl, float cr) { return same ? cr : (left ? 0.f : cl); };
-    const float m_t0 = e0(hh * hw * tl, hh * q.lw * tr), m_t1 = e1(hh * hw * tl, hh * q.lw * tr);
-    const float m_b0 = e0(q.lh * hw * bl, q.lh * q.lw * br), m_b1 = e1(q.lh * hw * bl, q.lh * q.lw * br);
-    const float h_t0 = e0(-hw * tl, -q.lw * tr), h_t1 = e1(-hw * tl, -q.lw * tr);
-    const float h_b0 = e0(hw * bl, q.lw * br), h_b1 = e1(hw * bl, q.lw * br);
-    const float w_t0 = e0(-hh * tl, hh * tr), w_t1 = e1(-hh * tl, hh * tr);
-    const float w_b0 = e0(-q.lh * bl, q.lh * br), w_b1 = e1(-q.lh * bl, q.lh * br);
+    const float m_t0 = pm.e0(hh * hw * tl, hh * q.lw * tr), m_t1 = pm.e1(hh * hw * tl, hh * q.lw * tr);
+    const float m_b0 = pm.e0(q.lh * hw * bl, q.lh * q.lw * br), m_b1 = pm.e1(q.lh * hw * bl, q.lh * q.lw * br);
+    const float h_t0 = pm.e0(-hw * tl, -q.lw * tr), h_t1 = pm.e1(-hw * tl, -q.lw * tr);
+    const float h_b0 = pm.e0(hw * bl, q.lw * br), h_b1 = pm.e1(hw * bl, q.lw * br);
+    const float w_t0 = pm.e0(-hh * tl, hh * tr), w_t1 = pm.e1(-hh * tl, hh * tr);
+    const float w_b0 = pm.e0(-q.lh * bl, q.lh * br), w_b1 = pm.e1(-q.lh * bl, q.lh * br);
     int c = 0;
     // one channel per iteration keeps 3 loads in flight per thread and waits for them 256 times in a row (the compiler
     // does not cluster the loads of an unrolled body by itself): the loads of kCB channels are issued together, the
     // sums are still taken in channel order (0.654 -> 0.577 ms at stage 4, profiles/r04_staged_variants_kernel_times.log)
     constexpr int kCB = 8;
-    const unsigned top_b = (unsigned)top * 4u, bot_b = (unsigned)bot * 4u, p_b = (unsigned)p * 4u;   // plane < 2^30 B
+    const unsigned top_b = (unsigned)pm.top * 4u, bot_b = (unsigned)pm.bot * 4u, p_b = (unsigned)p * 4u;   // plane < 2^30 B
     const size_t plane_b = (size_t)g.H * g.W * 4, col_b = (size_t)K * P * 4;
     for (; c + kCB <= g.C; c += kCB) {
       // wave-uniform bases + 32-bit lane offsets: scalar-base addressing, no 64-bit address pair per load
@@ -568,8 +480,8 @@ __global__ __launch_bounds__(256) void dcn_col2im_coord_kernel(
 #pragma unroll
       for (int u = 0; u < kCB; ++u) {
         gc[u] = *reinterpret_cast<const float*>(gc0 + u * col_b + p_b);
-        a[u] = *reinterpret_cast<const pair_t*>(im0 + u * plane_b + top_b);
-        b[u] = *reinterpret_cast<const pair_t*>(im0 + u * plane_b + bot_b);
+        a[u] = load_pair<PAIR>(im0 + u * plane_b + top_b);
+        b[u] = load_pair<PAIR>(im0 + u * plane_b + bot_b);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -582,29 +494,26 @@ __global__ __launch_bounds__(256) void dcn_col2im_coord_kernel(
     for (; c < g.C; ++c) {
       const float* im = x + ((size_t)n * g.C + c) * g.H * g.W;
       const float gc = grad_cols[(((size_t)n * g.C + c) * K + t) * P + p];
-      const pair_t a = *reinterpret_cast<const pair_t*>(im + top);
-      const pair_t b = *reinterpret_cast<const pair_t*>(im + bot);
+      const pair_t a = load_pair<PAIR>(im + pm.top), b = load_pair<PAIR>(im + pm.bot);
       gm += gc * (m_t0 * a.x + m_t1 * a.y + m_b0 * b.x + m_b1 * b.y);
       gh += gc * (h_t0 * a.x + h_t1 * a.y + h_b0 * b.x + h_b1 * b.y);
       gw += gc * (w_t0 * a.x + w_t1 * a.y + w_b0 * b.x + w_b1 * b.y);
-    }
-  } else if (q.in) {
-    const float hh = 1.f - q.lh, hw = 1.f - q.lw;
-    for (int c = 0; c < g.C; ++c) {
-      const float* im = x + ((size_t)n * g.C + c) * g.H * g.W;
-      const float gc = grad_cols[(((size_t)n * g.C + c) * K + t) * P + p];
-      const float v1 = (q.t && q.l) ? im[q.h0 * g.W + q.w0] : 0.f;
-      const float v2 = (q.t && q.r) ? im[q.h0 * g.W + q.w0 + 1] : 0.f;
-      const float v3 = (q.b && q.l) ? im[(q.h0 + 1) * g.W + q.w0] : 0.f;
-      const float v4 = (q.b && q.r) ? im[(q.h0 + 1) * g.W + q.w0 + 1] : 0.f;
-      gm += gc * (hh * hw * v1 + hh * q.lw * v2 + q.lh * hw * v3 + q.lh * q.lw * v4);
-      gh += gc * (-hw * v1 - q.lw * v2 + hw * v3 + q.lw * v4);
-      gw += gc * (-hh * v1 + hh * v2 - q.lh * v3 + q.lh * v4);
     }
   }
   grad_offset[o] = gh * m;
   grad_offset[o + P] = gw * m;
   grad_mask[((size_t)n * K + t) * P + p] = gm;
+}
+
+__global__ __launch_bounds__(256) void dcn_col2im_coord_kernel(                                               // W >= 2
+    const float* __restrict__ grad_cols, const float* __restrict__ x, const float* __restrict__ offset,
+    const float* __restrict__ mask, float* __restrict__ grad_offset, float* __restrict__ grad_mask, Conv g) {
+  col2im_coord_body<true>(grad_cols, x, offset, mask, grad_offset, grad_mask, g);
+}
+__global__ __launch_bounds__(256) void dcn_col2im_coord_1col_kernel(                                          // W == 1
+    const float* __restrict__ grad_cols, const float* __restrict__ x, const float* __restrict__ offset,
+    const float* __restrict__ mask, float* __restrict__ grad_offset, float* __restrict__ grad_mask, Conv g) {
+  col2im_coord_body<false>(grad_cols, x, offset, mask, grad_offset, grad_mask, g);
 }
 
 inline bool dcn_bad(int N, const Conv& g) {
@@ -630,12 +539,9 @@ int vidar_dcn_im2col_f32(const float* x, const float* offset, const float* mask,
   if (dcn_bad(N, g)) return VIDAR_ERR_BAD_ARG;
   if (N == 0) return 0;
   if (kh * kw > kMaxTaps) return VIDAR_ERR_BAD_ARG;
-  if (W >= 2)
-    hipLaunchKernelGGL(dcn_im2col_pair_kernel, dim3(xcd_plane_grid((Ho * Wo + 255) / 256, ((C + kCP - 1) / kCP) * N)), dim3(256),
-                       0, (hipStream_t)stream, x, offset, mask, cols, g, N);
-  else
-    hipLaunchKernelGGL(dcn_im2col_kernel, dim3((Ho * Wo + 255) / 256, (C + kCG - 1) / kCG, N), dim3(256),
-                       0, (hipStream_t)stream, x, offset, mask, cols, g);
+  hipLaunchKernelGGL(W >= 2 ? dcn_im2col_pair_kernel : dcn_im2col_kernel,
+                     dim3(xcd_plane_grid((Ho * Wo + 255) / 256, ((C + kCP - 1) / kCP) * N)), dim3(256), 0, (hipStream_t)stream,
+                     x, offset, mask, cols, g, N);
   return vidar_last_error();
 }
 
@@ -685,7 +591,7 @@ int vidar_dcn_col2im_f32(const float* grad_cols, const float* x, const float* of
     hipLaunchKernelGGL(dcn_col2im_kernel, dim3((P + 255) / 256, (C + kCG - 1) / kCG, N), dim3(256), 0, s, grad_cols,
                        offset, mask, grad_x, g);
   }
-  hipLaunchKernelGGL(dcn_col2im_coord_kernel, dim3((P + 255) / 256, K, N), dim3(256), 0,
+  hipLaunchKernelGGL(W >= 2 ? dcn_col2im_coord_kernel : dcn_col2im_coord_1col_kernel, dim3((P + 255) / 256, K, N), dim3(256), 0,
                      s, grad_cols, x, offset, mask, grad_offset, grad_mask, g);
   return vidar_last_error();
 }
