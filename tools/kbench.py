@@ -491,7 +491,7 @@ def bench_gemm(which):
     # backbone: out[b] = W [Co,Ci] x[b] [Ci,HW]
     for (Bn, Co, Ci, HW, tag) in ((24, 1024, 256, 5800, "layer3 conv3"), (24, 256, 1024, 5800, "layer3 conv1"),
                                   (24, 256, 2304, 5800, "layer3 dcn"), (24, 512, 128, 23200, "layer2 conv3"),
-                                  (24, 2048, 512, 1450, "layer4 conv3")):
+                                  (24, 2048, 512, 1450, "layer4 conv3"), (24, 256, 64, 92800, "layer1 conv3")):
         w, x = rnd(Co, Ci) * 0.05, rnd(Bn, Ci, HW)
         sc, sh, res = rnd(Co), rnd(Co), rnd(Bn, Co, HW)
         fl = 2.0 * Bn * Co * Ci * HW
@@ -503,6 +503,11 @@ def bench_gemm(which):
         line(f"conv fwd {Bn}x[{Co},{Ci}]x[{Ci},{HW}] {tag}", fl, nb, **ms)
         gy = rnd(6, Co, HW); x6 = x[:6]
         fl6 = fl / 4
+        ms = {}                                    # the 6 current images of a step (the 24 above are its history frames)
+        for m, p in (("f32", G.F32), ("bf16x3", G.BF16X3)):
+            ms[m] = timeit(lambda: G.conv_forward(w, x6, precision=p))
+            ms[m + "_bn_res_relu"] = timeit(lambda: G.conv_forward(w, x6, sc, sh, res[:6], True, p))
+        line(f"conv fwd 6x[{Co},{Ci}]x[{Ci},{HW}] {tag}", fl6, nb / 4, **ms)
         ms = dict(lib=timeit(lambda: torch.bmm(w.view(1, Co, Ci).transpose(1, 2).expand(6, -1, -1), gy)))
         for m, p in (("f32", G.F32), ("bf16x3", G.BF16X3)):
             ms[m] = timeit(lambda: G.conv_grad_input(w, gy, p))

@@ -37,7 +37,8 @@
 //
 // Epilogue: y = relu?( acc * scale[m|n] + shift[m|n] + residual[m,n] ) -- the bias of F.linear, the frozen
 // BatchNorm + residual + ReLU that follows every 1x1 convolution of the ResNet bottlenecks
-// (config vidar_1_8_nusc_1future.py:88-106: norm_eval, requires_grad False), the FFN's ReLU.
+// (config vidar_1_8_nusc_1future.py:88-106: norm_eval, requires_grad False), the FFN's ReLU.  Full tiles of the fp32
+// convolution forward run it between the MFMAs of their last k-step (last_step_piped), everything else after them.
 // Split-K / batch-reduced products (weight gradients) write fp32 slabs and a second kernel sums them in a
 // fixed order (deterministic; no atomics).
 #include <hip/hip_runtime.h>
@@ -305,7 +306,6 @@ __device__ __forceinline__ void fetch(Staged<PREC>& sa, Staged<PREC>& sb, const 
   else load_mnmajor<PREC>(sb, T.rsB, g.ldb, krel, vob);
 }
 
-// the k loop of one tile.  On entry the staging registers hold (or are about to receive) the tile's first k-step.
 // sum over the staged k of a thread's A values, per row of its row quad (MN-major staging: every float4 of a thread is
 // the same four consecutive rows at another k).  k past the operand's END reads 0 (the descriptor's range check), but a
 // float4 that straddles m >= M inside the operand does NOT: with lda == M it reads the first elements of the NEXT k-row,
@@ -318,16 +318,19 @@ __device__ __forceinline__ void add_rowsum(f32x4& rs, const Staged<PREC>& sa) {
   for (int i = 0; i < Staged<PREC>::CH * 2; ++i) rs += sa.v[i >> 1][i & 1];
 }
 
+// the k loop of one tile, k-steps [T.kbeg, kstop).  On entry the staging registers hold (or are about to receive) the
+// tile's first k-step; a step requests its successor while that lies inside the TILE (k0 + BK < T.kend), so with
+// kstop < T.kend the loop leaves the staging registers holding the first k-step it did not run.
 template <int PREC, int ALAY, int BLAY>
 __device__ __forceinline__ void mainloop(f32x16 (&acc)[2][2], Staged<PREC>& sa, Staged<PREC>& sb, const GemmArgs& g,
-                                         const Tile& T, uint32_t* imgA, uint32_t* imgB, int tid, uint32_t voa, uint32_t vob,
-                                         f32x4& rowsum, bool want_rowsum) {
+                                         const Tile& T, int kstop, uint32_t* imgA, uint32_t* imgB, int tid, uint32_t voa,
+                                         uint32_t vob, f32x4& rowsum, bool want_rowsum) {
   constexpr int IMGS = (PREC == PREC_BF16X3) ? 2 : 1;
   constexpr int IMG_DWORDS = Geo<PREC>::IMG_DWORDS;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
   const int l31 = lane & 31, h = lane >> 5;
-  for (int k0 = T.kbeg; k0 < T.kend; k0 += BK) {
+  for (int k0 = T.kbeg; k0 < kstop; k0 += BK) {
     if (ALAY == LAY_MN && want_rowsum) add_rowsum<PREC>(rowsum, sa);
     if (ALAY == LAY_K) store_kmajor<PREC>(sa, imgA, tid); else store_mnmajor<PREC>(sa, imgA, tid);
     if (BLAY == LAY_K) store_kmajor<PREC>(sb, imgB, tid); else store_mnmajor<PREC>(sb, imgB, tid);
@@ -447,6 +450,120 @@ __device__ __forceinline__ void epilogue(const f32x16 (&acc)[2][2], const GemmAr
   else epilogue_impl<true>(acc, g, T, tid);
 }
 
+// ---- fp32 mode, K-major A: the last k-step of a full tile with the epilogue under its MFMAs --------------------------------
+// epilogue() above starts after the tile's last MFMA and pays eight dependent memory round trips per tile with the
+// matrix cores idle (the workgroups of a CU run in lockstep: nothing else fills them).  A tile that
+//   - applies an epilogue (no slabs) whose scale / shift, if any, are indexed by the row (vec_axis == 1), and
+//   - lies wholly inside the matrix (128 rows, 128 columns: no row predicate, no cut column)
+// runs its LAST k-step accumulator-major instead -- acc[0][0] through all 16 MFMAs of the step, then acc[0][1], ... (the k
+// order inside every accumulator is the one of mainloop: s outer, u inner) -- so that a finished 32 x 32 sub-tile can
+// be scaled, shifted, added to its residual and stored between the MFMAs of its successor:
+//   scale / shift   the tile's 128 + 128 values are read ONCE, one per thread, and passed through a 1 KB LDS table
+//                   (epilogue(): one buffer load per accumulator register, half a wave reading one address)
+//   residual        one window of 16 registers: element r of sub-tile s + 1 is requested right after element r of
+//                   sub-tile s has been consumed, 16 MFMAs (1024 matrix-core cycles) before its own use; the window of
+//                   sub-tile 0 is requested before the step's first MFMA
+//   next tile       its first operands are requested between the step's LDS stores (last_step_stage: the staging
+//                   registers are free from there on) and its MFMAs, as the k loop requests a next k-step
+// Only the last sub-tile's FMAs and stores follow the tile's last MFMA.  The table is double buffered by the parity of
+// the workgroup's tile count: a wave writes buffer p again two tiles later, behind barriers that every wave of the
+// workgroup passes only after its last read of the table in this tile.  The barrier behind the step's last fragment
+// read is LDS-only (lds_barrier): it keeps the stores and the next tile's loads in flight.
+// The arithmetic per element is epilogue()'s, y = acc * sc + sh + rs then the ReLU, with sc = 1 / sh = 0 / rs = 0 (a
+// zero-length descriptor) standing in for a missing operand exactly as there: the results are bit-identical.
+constexpr int TAB_DWORDS = 2 * (BM + BM);       // two buffers of 128 scale + 128 shift values
+
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+__device__ __forceinline__ bool piped_tile(const GemmArgs& g, const Tile& T) {      // workgroup-uniform
+  return !g.slabs && (g.vec_axis == 1 || (g.scale == nullptr && g.shift == nullptr)) && g.M - T.m0 >= BM &&
+         g.N - T.n0 >= BN && T.kbeg < T.kend;
+}
+
+// the value thread `tid` contributes to the tile's table: scale[m0 + tid] (tid < 128) or shift[m0 + tid - 128]
+__device__ __forceinline__ float table_value(const GemmArgs& g, const Tile& T, int tid) {
+  const float* v = tid < BM ? g.scale : g.shift;
+  float x = tid < BM ? 1.0f : 0.0f;
+  if (v != nullptr) x = v[T.m0 + (tid & (BM - 1))];
+  return x;
+}
+
+// the step's operands and the tile's table value: staging registers -> LDS
+template <int ALAY, int BLAY>
+__device__ __forceinline__ void last_step_stage(const Staged<PREC_F32>& sa, const Staged<PREC_F32>& sb, uint32_t* imgA,
+                                                uint32_t* imgB, float* tab, float tabv, int tid) {
+  if (ALAY == LAY_K) store_kmajor<PREC_F32>(sa, imgA, tid); else store_mnmajor<PREC_F32>(sa, imgA, tid);
+  if (BLAY == LAY_K) store_kmajor<PREC_F32>(sb, imgB, tid); else store_mnmajor<PREC_F32>(sb, imgB, tid);
+  tab[tid] = tabv;
+  __syncthreads();
+}
+
+template <int ALAY, int BLAY>
+__device__ __forceinline__ void last_step_piped(f32x16 (&acc)[2][2], const GemmArgs& g, const Tile& T, const uint32_t* imgA,
+                                                const uint32_t* imgB, const float* tab, int tid0) {
+  constexpr int PREC = PREC_F32;
+  // every per-lane address below is invariant over the tiles a workgroup walks, and hoisted out of the tile loop it
+  // would occupy registers through the k loop and epilogue() (the kernel has none to spare): an opaque copy of the
+  // thread id makes them this function's own, recomputed per tile
+  int tid = tid0;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63, wave = tid >> 6;
+  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+  const int l31 = lane & 31, h = lane >> 5;
+  // descriptors of the tile's own 128 x 128 window of C and of the residual
+  const __amdgpu_buffer_rsrc_t rsC = make_rsrc(g.C + (int64_t)T.batch * g.sC + (int64_t)T.m0 * g.ldc + T.n0,
+                                               ((int64_t)(BM - 1) * g.ldc + BN) * 4);
+  const uint32_t ldc = (uint32_t)g.ldc, ldr = (uint32_t)g.ldr;
+  const uint32_t voC = (uint32_t)(((wm + 4 * h) * ldc + wn + l31) * 4);
+  const bool has_res = g.residual != nullptr;
+  const __amdgpu_buffer_rsrc_t rsR =
+      make_rsrc(has_res ? g.residual + (int64_t)T.batch * g.sR + (int64_t)T.m0 * g.ldr + T.n0 : g.C,
+                has_res ? ((int64_t)(BM - 1) * g.ldr + BN) * 4 : 0);
+  const uint32_t voR = (uint32_t)(((wm + 4 * h) * ldr + wn + l31) * 4), voRz = has_res ? voR : 0u;
+  // without a residual every load must miss the zero-length descriptor and return 0: the range check subtracts the
+  // scalar offset from the length first, so the scalar offset has to be 0 then
+  const uint32_t rb = has_res ? 4u : 0u;
+  const float* tsc = tab + wm + 4 * h;
+  const float* tsh = tsc + BM;
+  const bool relu = g.relu != 0;
+  float rs[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) rs[r] = ld4(rsR, voRz, (uint32_t)((((r & 3) + 8 * (r >> 2)) * ldr) * rb));
+  __builtin_amdgcn_sched_barrier(0);
+  // The order below is pinned for the compiler: left to itself it keeps every fragment of the step in registers
+  // (sub-tiles (0, 0) and (1, 0) read the same B fragments) and, short of registers then, sinks each residual load down
+  // to its use behind a vmcnt(0).  The empty asm makes every sub-tile read its own fragments; the scheduling barrier
+  // after each group of four MFMAs keeps a residual load 16 MFMAs ahead of its use.
+#pragma unroll
+  for (int sub = 0; sub <= 4; ++sub) {
+    const int i = (sub >> 1) & 1, j = sub & 1;                  // the sub-tile whose MFMAs run (sub < 4)
+    const int pi = ((sub - 1) >> 1) & 1, pj = (sub - 1) & 1;    // the finished one (sub > 0)
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      f32x4 af = {0.f, 0.f, 0.f, 0.f}, bf = af;
+      if (sub < 4) {
+        af = __builtin_bit_cast(f32x4, frag<PREC, ALAY>(imgA, wm + 32 * i + l31, s, h));
+        bf = __builtin_bit_cast(f32x4, frag<PREC, BLAY>(imgB, wn + 32 * j + l31, s, h));
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (sub < 4) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[u], bf[u], acc[i][j], 0, 0, 0);
+        if (sub > 0) {
+          const int r = 4 * s + u;
+          const int prow = 32 * pi + 8 * s + u;                 // uniform part of the row inside the wave's tile
+          float y = acc[pi][pj][r] * tsc[prow] + tsh[prow] + rs[r];
+          if (relu && !(y > 0.0f)) y = 0.0f;
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, y), rsC, voC, (uint32_t)((prow * ldc + 32 * pj) * 4), 0);
+          if (sub < 4) rs[r] = ld4(rsR, voRz, (uint32_t)(((32 * i + 8 * s + u) * ldr + 32 * j) * rb));
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (sub == 3) lds_barrier();        // every fragment of the step has been read: the images are free
+  }
+}
+
 // Persistent workgroups: the grid is (at most) one residency of the chip, and a workgroup walks tiles t = blockIdx,
 // blockIdx + grid, ...  Between the k loop of a tile and its epilogue it decodes the NEXT tile and issues that tile's
 // first global loads, so the store burst of the epilogue (and the launch / address set-up a fresh workgroup would pay)
@@ -454,7 +571,9 @@ __device__ __forceinline__ void epilogue(const f32x16 (&acc)[2][2], const GemmAr
 template <int PREC, int ALAY, int BLAY>
 __global__ __launch_bounds__(THREADS, 3) void gemm_mfma_kernel(GemmArgs g) {
   constexpr int IMGS = (PREC == PREC_BF16X3) ? 2 : 1;
-  __shared__ __attribute__((aligned(16))) uint32_t lds[2 * IMGS * Geo<PREC>::IMG_DWORDS];
+  constexpr int IMGS_DWORDS = 2 * IMGS * Geo<PREC>::IMG_DWORDS;
+  // (ONE array: the scale / shift table of last_step_piped lies behind the images)
+  __shared__ __attribute__((aligned(16))) uint32_t lds[IMGS_DWORDS + (PREC == PREC_F32 && ALAY == LAY_K ? TAB_DWORDS : 0)];
   uint32_t* imgA = lds;
   uint32_t* imgB = lds + IMGS * Geo<PREC>::IMG_DWORDS;
   const int tid = threadIdx.x;
@@ -465,7 +584,7 @@ __global__ __launch_bounds__(THREADS, 3) void gemm_mfma_kernel(GemmArgs g) {
   if (t >= g.total) return;
   Tile cur = decode_tile<PREC, ALAY, BLAY>(g, t);
   if (cur.kbeg < cur.kend) fetch<PREC, ALAY, BLAY>(sa, sb, g, cur, cur.kbeg, tid, voa, vob);
-  for (;;) {
+  for (int parity = 0;; parity ^= 1) {
     f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -475,7 +594,20 @@ __global__ __launch_bounds__(THREADS, 3) void gemm_mfma_kernel(GemmArgs g) {
         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
     f32x4 rowsum = {0.f, 0.f, 0.f, 0.f};
     const bool want_rowsum = ALAY == LAY_MN && g.a_rowsum != nullptr && cur.n0 == 0;     // workgroup-uniform
-    mainloop<PREC, ALAY, BLAY>(acc, sa, sb, g, cur, imgA, imgB, tid, voa, vob, rowsum, want_rowsum);
+    const int tn = t + (int)gridDim.x;
+    const bool more = tn < g.total;
+    // fp32 mode, K-major A (a weight matrix: every product that has an epilogue): a full tile with an epilogue leaves its
+    // last k-step to last_step_piped.  The other instantiations are not touched.
+    constexpr bool PIPED = PREC == PREC_F32 && ALAY == LAY_K;
+    const bool piped = PIPED && piped_tile(g, cur);                                      // workgroup-uniform
+    float tabv = 0.0f;
+    if (piped) tabv = table_value(g, cur, tid);
+    const int kstop = piped ? cur.kbeg + (cur.kend - cur.kbeg - 1) / BK * BK : cur.kend;
+    mainloop<PREC, ALAY, BLAY>(acc, sa, sb, g, cur, kstop, imgA, imgB, tid, voa, vob, rowsum, want_rowsum);
+    float* tab = reinterpret_cast<float*>(lds) + IMGS_DWORDS + parity * (TAB_DWORDS / 2);
+    if constexpr (PIPED) {
+      if (piped) last_step_stage<ALAY, BLAY>(sa, sb, imgA, imgB, tab, tabv, tid);
+    }
     if (want_rowsum) {
       // the 8 threads that staged the same row quad (tid & 31, both modes) combine through LDS -- free after the k loop's
       // last barrier -- in a fixed order; rows m0 .. m0 + 127 of slab z
@@ -491,13 +623,17 @@ __global__ __launch_bounds__(THREADS, 3) void gemm_mfma_kernel(GemmArgs g) {
       }
       __syncthreads();
     }
-    const int tn = t + (int)gridDim.x;
-    const bool more = tn < g.total;
+    // the staging registers are free: a piped tile's last k-step is in LDS, any other tile has run all of its k-steps
     if (more) {        // only the tile NUMBER survives the epilogue (registers): the next tile is decoded twice
       const Tile nxt = decode_tile<PREC, ALAY, BLAY>(g, tn);
       if (nxt.kbeg < nxt.kend) fetch<PREC, ALAY, BLAY>(sa, sb, g, nxt, nxt.kbeg, tid, voa, vob);
     }
-    epilogue(acc, g, cur, tid);
+    if constexpr (PIPED) {
+      if (piped) last_step_piped<ALAY, BLAY>(acc, g, cur, imgA, imgB, tab, tid);
+      else epilogue(acc, g, cur, tid);
+    } else {
+      epilogue(acc, g, cur, tid);
+    }
     if (!more) break;
     cur = decode_tile<PREC, ALAY, BLAY>(g, tn);
     t = tn;
@@ -521,8 +657,6 @@ __global__ __launch_bounds__(THREADS, 3) void gemm_mfma_kernel(GemmArgs g) {
 // consumers store a tile, the producers are already staging the next tile's first two k-steps; the consumers' vmcnt
 // only ever counts their own stores and is never waited on.
 constexpr int WS_THREADS = 512;
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // a position in the flat k-step stream of one workgroup
 template <int PREC, int ALAY, int BLAY>
