@@ -30,6 +30,20 @@ int vidar_abi_version(void);
 /* profiling aid: launches the empty kernel `vidar_marker_kernel` on `stream` (see tools/trace_stats.py) */
 int vidar_marker(int id, void* stream);
 
+/* Deterministic mode (process-wide, off at load; returns the previous value).  While it is on, the scatter backwards
+ * that implement it accumulate in 64-bit fixed point instead of with fp32 atomics (csrc/det_acc.h): their result is a
+ * function of the multiset of contributions only -- not of arrival order, launch geometry or kernel variant -- within
+ * N_a * delta / 2 + one fp32 rounding of the exact sum per address.  Covered: vidar_msda_bwd_f32 and
+ * vidar_msda_fused_bwd_f32 (grad_value; the plain scatter form for every size), vidar_ray_{ce,gumbel,dist}_bwd_f32,
+ * vidar_latent_render_{prob,gather,gather_grouped}_bwd_f32, vidar_knn1_d3_bwd_ws (grad_p2), vidar_dcn_col2im_f32
+ * (grad_x); vidar_drop_add_ln_bwd_f32 sums dgamma / dbeta in a fixed order instead.  In the mode
+ *   - their workspace queries return the bytes of the deterministic form (8 B per output element + the max words) and
+ *     the call returns VIDAR_ERR_BAD_ARG without such a workspace: it never falls back to float atomics;
+ *   - a non-finite contribution makes the WHOLE gradient NaN (the default mode poisons the touched addresses only).
+ * Every other entry point ignores the switch; the default mode is unchanged in every bit. */
+int vidar_set_deterministic(int on);
+int vidar_get_deterministic(void);
+
 /* ---------------------------------------------------------------------------
  * third_lib/dvr  (pybind surface: third_lib/dvr/dvr.cpp:36-69)
  *   sigma   [N,T,Z,Y,X] f32     origin [N,TO,3] f32 (voxel units)
@@ -147,6 +161,14 @@ int vidar_knn1_d3_fwd(const float* p1, const float* p2, const int64_t* lengths1,
 int vidar_knn1_d3_bwd(const float* p1, const float* p2, const int64_t* lengths1,
                       const int64_t* lengths2, const int64_t* idx, const float* grad_dist2,
                       float* grad_p1, float* grad_p2, int N, int P1, int P2, void* stream);
+/* The same with a caller-owned workspace, which the deterministic mode needs for grad_p2 (the entry above has nowhere
+ * to put the accumulators: VIDAR_ERR_BAD_ARG in the mode).  *bytes: 0 with the mode off (workspace may be NULL),
+ * 8 * (N*P2*3 + 1) with it on. */
+int vidar_knn1_d3_bwd_workspace_bytes(int N, int P2, int64_t* bytes);
+int vidar_knn1_d3_bwd_ws(const float* p1, const float* p2, const int64_t* lengths1,
+                         const int64_t* lengths2, const int64_t* idx, const float* grad_dist2,
+                         float* grad_p1, float* grad_p2, int N, int P1, int P2, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Multi-scale deformable attention.  Replaces mmcv._ext.ms_deform_attn_{forward,backward}
@@ -333,6 +355,8 @@ int vidar_latent_render_gather_grouped_bwd_f32(const float* path_prob, const flo
  * vidar_ray_bwd_workspace_bytes(F,Z,Y,X) bytes (caller-owned device scratch on the call's device / stream, nothing
  * survives the call) the kernels add into 8 private copies of the volume that a second kernel sums; with
  * workspace == NULL they add straight into grad_sigma.  Results agree to fp32 summation order.
+ * Deterministic mode (vidar_set_deterministic): the workspace query returns 8 * (F*Z*Y*X + 1) and the backwards
+ * accumulate in fixed point (the plain scatter, no private copies); the same bits for every K form and ray order.
  * ------------------------------------------------------------------------- */
 size_t vidar_ray_bwd_workspace_bytes(int F, int Z, int Y, int X);
 int vidar_ray_ce_fwd_f32(const float* sigma, const float* origin, const float* gt_pts,
@@ -442,10 +466,15 @@ int vidar_dcn_set_variant(int variant);
 int vidar_dcn_im2col_f32(const float* x, const float* offset, const float* mask, float* cols, int N,
                          int C, int H, int W, int Ho, int Wo, int kh, int kw, int stride, int pad,
                          int dil, void* stream);
+/* Deterministic mode (vidar_set_deterministic): grad_x is the fixed-point plain scatter for every shape and variant;
+ * its workspace depends on C, which vidar_dcn_col2im_workspace_bytes does not take: *bytes = 8 * (N*C*H*W + 1).  In the mode
+ * vidar_dcn_col2im_f32 returns VIDAR_ERR_BAD_ARG with a smaller workspace. */
+int vidar_dcn_col2im_det_workspace_bytes(int N, int C, int H, int W, int64_t* bytes);
 int vidar_dcn_col2im_f32(const float* grad_cols, const float* x, const float* offset,
                          const float* mask, float* grad_x, float* grad_offset, float* grad_mask,
                          int N, int C, int H, int W, int Ho, int Wo, int kh, int kw, int stride,
                          int pad, int dil, void* workspace, size_t workspace_bytes, void* stream);
+/* (the gather's scratch; NOT the answer in the deterministic mode, where vidar_dcn_col2im_det_workspace_bytes sizes it) */
 size_t vidar_dcn_col2im_workspace_bytes(int N, int H, int W, int Ho, int Wo, int kh, int kw);
 
 /* 3x3 convolution (stride 1, pad 1, dilation 1, groups 1) with FEW output channels as an implicit GEMM on the fp32

@@ -617,6 +617,66 @@ def bench_det(which):
         report("det_loss_tail", r.pop("loss_fwd_bwd_hip_ms"), **{k: round(v, 4) if isinstance(v, float) else v for k, v in r.items()})
 
 
+def bench_deterministic(which):
+    """every backward the deterministic mode covers (vidar_amd/deterministic.py) at its BASELINE shape, in both modes:
+    mode=0 the fp32-atomic default (with the strategy the step takes), mode=1 the measure + fixed-point (or fixed-order)
+    form.  `det` is the detection-loss bench, hence the long name."""
+    from vidar_amd import deterministic, gemm
+    from vidar_amd.synthetic import msda_operands, ray_set, dense_rays
+    from vidar_amd.plugin.modules.multi_scale_deformable_attn_function import _msda_backward
+    from vidar_amd.plugin.dense_heads.ray_ops import ray_ce, ray_gumbel, ray_dist, gumbel_noise
+    from vidar_amd.plugin.modules.ray_operations.latent_rendering import _PathProb, _RayGather
+    from vidar_amd.plugin.backbones import dcn_col2im
+    from vidar_amd.plugin.bricks import drop_add_layernorm
+    from vidar_amd.third_lib.chamferdist import _C
+    import torch.nn as nn
+    cases = []
+    fpn = [(116, 200), (58, 100), (29, 50), (15, 25)]
+    for name, B, shapes, Nq, P in (("TSA", 2, [(200, 200)], 40000, 4), ("SCA", 6, fpn, 10000, 8)):
+        value, sh, lsi, loc, w = msda_operands(0, B, shapes, Nq, P=P, device="cuda")
+        go = torch.randn(B, Nq, 256, device="cuda")
+        cases.append((f"msda_bwd {name}", lambda a=(value, sh, lsi, loc, w, go): _msda_backward(*a)))
+    sig, origin, points, tindex = ray_set(seed=0, N=1, T=1, rays_per_frame=30000)
+    sigma = torch.randn(1, 16, 200, 200, device="cuda", requires_grad=True)
+    o, p, ti = (torch.from_numpy(a[0]).cuda() for a in (origin, points, tindex))
+    pts, tix = dense_rays(1, 16, 200, 200, "cuda")
+    ce, _ = ray_ce(sigma, o, p, ti)
+    dg = ray_gumbel(sigma, o, pts, tix, gumbel_noise(pts.shape[0], 512))
+    dd, _, _ = ray_dist(sigma, o, p, ti, gumbel_noise(p.shape[0], 513))
+    for name, q in (("ray_ce_bwd P=30000", ce), (f"ray_gumbel_bwd R={pts.shape[0]}", dg), ("ray_dist_bwd P=30000", dd)):
+        cases.append((name, lambda q=q, g=torch.ones_like(q): torch.autograd.grad(q, sigma, g, retain_graph=True)))
+    occ = torch.randn(1, 200, 200, 16, device="cuda", requires_grad=True)
+    a = torch.randn(1, 200, 200, 16, device="cuda", requires_grad=True)
+    pr = _PathProb.apply(occ, 256, 1.0, 0)
+    pd = pr.detach().requires_grad_(True)
+    f = _RayGather.apply(pd, a, 256, 1.0, 1e-3)
+    cases.append(("lr_prob_bwd step=1.0", lambda g=torch.randn_like(pr): torch.autograd.grad(pr, occ, g, retain_graph=True)))
+    cases.append(("lr_gather_bwd step=1.0", lambda g=torch.randn_like(f): torch.autograd.grad(f, [pd, a], g, retain_graph=True)))
+    rng = np.random.default_rng(0)
+    c1 = torch.from_numpy(rng.uniform(-50, 50, (1, 30000, 3)).astype(np.float32)).cuda()
+    c2 = torch.from_numpy(rng.uniform(-50, 50, (1, 30000, 3)).astype(np.float32)).cuda()
+    l = torch.tensor([30000], device="cuda")
+    idx, _ = _C.knn_points_idx(c1, c2, l, l, 1, -1)
+    gd = torch.randn(1, 30000, 1, device="cuda")
+    cases.append(("knn1_d3_bwd 30000x30000", lambda: _C.knn_points_backward(c1, c2, l, l, idx, gd)))
+    g = torch.Generator().manual_seed(0)
+    N, C, H, W = 6, 256, 58, 100
+    x = torch.randn(N, C, H, W, generator=g).cuda(); mask = torch.rand(N, 9, H, W, generator=g).cuda()
+    gcols = torch.randn(N, C * 9, H * W, generator=g).cuda(); off = (torch.randn(N, 18, H, W, generator=g) * 1.5).cuda()
+    cases.append((f"dcn_col2im N={N} C={C} {H}x{W} offsets~1.5px", lambda: dcn_col2im(gcols, x, off, mask, 3, 3, 1, 1, 1, H, W)))
+    norm = nn.LayerNorm(256).cuda()
+    xs = torch.randn(1, 40000, 256, device="cuda", requires_grad=True); rs = torch.randn(1, 40000, 256, device="cuda", requires_grad=True)
+    y = drop_add_layernorm(xs, rs, norm, 0.1, True)
+    cases.append(("drop_add_ln bwd", lambda gy=torch.randn_like(y): torch.autograd.grad(y, [xs, rs, norm.weight, norm.bias], gy, retain_graph=True)))
+    g2 = torch.randn(40000, 256, device="cuda")
+    cases.append(("colsum 40000x256", lambda: gemm._colsum(g2)))
+    for name, fn in cases:
+        for mode in (False, True):
+            with deterministic.use(mode):
+                ms = sorted(timeit(fn) for _ in range(3))[1]
+            report(name, ms, mode=int(mode))
+
+
 def bench_imgprep(which):
     """the device image pipeline on one sample (30 images of 900 x 1600, random noise) for the three released pipelines,
     against the host path (numpy / PIL / torch, this process, its torch threads) on the same images and the same drawn

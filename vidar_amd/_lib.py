@@ -51,6 +51,8 @@ _KIND = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_int64, "z": ctyp
 _ABI = {
     "vidar_abi_version": "i",
     "vidar_marker": "i i p",
+    "vidar_set_deterministic": "i i",
+    "vidar_get_deterministic": "i",
     "vidar_dvr_max_d": "i",
     "vidar_dvr_render_forward_f32": "i 6p 8i p",
     "vidar_dvr_render_f32": "i 7p 8i p",
@@ -67,6 +69,8 @@ _ABI = {
     "vidar_knn1_d3_workspace_bytes": "z 2i",
     "vidar_knn1_d3_fwd": "i 7p 3i p",
     "vidar_knn1_d3_bwd": "i 8p 3i p",
+    "vidar_knn1_d3_bwd_workspace_bytes": "i 2i p",
+    "vidar_knn1_d3_bwd_ws": "i 8p 3i p z p",
     "vidar_msda_fwd_f32": "i 6p 7i p",
     "vidar_msda_bwd_workspace_bytes": "z 6i",
     "vidar_msda_set_item_order": "i i",
@@ -107,6 +111,7 @@ _ABI = {
     "vidar_dcn_im2col_f32": "i 4p 11i p",
     "vidar_dcn_col2im_f32": "i 7p 11i p z p",
     "vidar_dcn_col2im_workspace_bytes": "z 7i",
+    "vidar_dcn_col2im_det_workspace_bytes": "i 4i p",
     "vidar_conv3x3_few_workspace_bytes": "z i",
     "vidar_conv3x3_few_f32": "i 4p 5i p z p",
     "vidar_affine_act_fwd_f32": "i 5p 4i p",

@@ -1,5 +1,6 @@
 // ABI bookkeeping for libvidar_hip.so
 #include <hip/hip_runtime.h>
+#include <atomic>
 
 #include "vidar_hip.h"
 #include "vidar_common.h"
@@ -8,11 +9,15 @@ namespace {
 __global__ void vidar_marker_kernel(int* sink, int id) {
   if (sink != nullptr) *sink = id;
 }
+std::atomic<int> g_deterministic{0};   // vidar_set_deterministic
 }  // namespace
 
 extern "C" {
 
 int vidar_abi_version(void) { return 2; }
+
+int vidar_set_deterministic(int on) { return g_deterministic.exchange(on != 0, std::memory_order_relaxed); }
+int vidar_get_deterministic(void) { return g_deterministic.load(std::memory_order_relaxed); }
 
 // Launches a one-thread kernel named `vidar_marker_kernel`: profiling tools use a pair of them to
 // delimit the timed region of bench.py inside a rocprofv3 kernel trace (warm-up excluded).

@@ -18,6 +18,7 @@
 
 #include "vidar_hip.h"
 #include "vidar_common.h"
+#include "det_scatter.h"
 
 namespace {
 
@@ -185,17 +186,28 @@ __global__ __launch_bounds__(256) void dcn_im2col_kernel(                       
 // neighbouring pixels, so a wave instruction touches only 2-3 lines (atomics cost per instruction x line).
 // grid: (ceil(P/256), ceil(C/kCG), N)
 constexpr int kCG = 8;
+// Acc: the accumulate policy of det_acc.h -- det::AccAtomic (fp32 atomics, the default mode), or the two passes of the
+// deterministic mode: det::AccMeasure (which keeps every thread to the end, for its flush), then det::AccFixed.
+// AccMeasure::flush holds a workgroup barrier: with the measure policy no thread may `return` before it.
+template <class Acc, class... AccParam>
 __global__ __launch_bounds__(256) void dcn_col2im_kernel(const float* __restrict__ grad_cols, const float* __restrict__ offset,
-                                                         const float* __restrict__ mask, float* __restrict__ grad_x, Conv g) {
+                                                         const float* __restrict__ mask, float* __restrict__ grad_x, Conv g,
+                                                         AccParam... acc_param) {
+  Acc acc(grad_x, acc_param...);
   const int P = g.Ho * g.Wo, K = g.kh * g.kw;
   const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= P) return;
+  if constexpr (!Acc::kMeasureOnly) {
+    if (p >= P) return;
+  }
   const int n = blockIdx.z, c0 = blockIdx.y * kCG, nc = min(kCG, g.C - c0);
   const int py = p / g.Wo, px = p % g.Wo;
   const size_t plane = (size_t)g.H * g.W, KP = (size_t)K * P;
   float* gim = grad_x + ((size_t)n * g.C + c0) * plane;
   const float* gc = grad_cols + ((size_t)n * g.C + c0) * KP + p;
   for (int t = 0; t < K; ++t) {
+    if constexpr (Acc::kMeasureOnly) {
+      if (p >= P) break;
+    }
     const size_t o = ((size_t)n * 2 * K + 2 * t) * P + p;
     const Pos s = tap_pos(g, py, px, t, offset[o], offset[o + P]);
     const Bil q = bil(s.h, s.w, g.H, g.W);
@@ -204,9 +216,10 @@ __global__ __launch_bounds__(256) void dcn_col2im_kernel(const float* __restrict
     for (int c = 0; c < nc; ++c) {
       const float gv = gc[(size_t)c * KP + (size_t)t * P] * m;
       if (gv == 0.f) continue;
-      for_corners(q, g.W, [&](int pix, float w) { unsafeAtomicAdd(gim + (size_t)c * plane + pix, w * gv); });
+      for_corners(q, g.W, [&](int pix, float w) { acc.add(gim + (size_t)c * plane + pix, w * gv); });
     }
   }
+  if constexpr (Acc::kMeasureOnly) acc.flush();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -552,6 +565,12 @@ size_t vidar_dcn_col2im_workspace_bytes(int N, int H, int W, int Ho, int Wo, int
   return sizeof(int) * 2 * hw + sizeof(Entry) * ent;
 }
 
+int vidar_dcn_col2im_det_workspace_bytes(int N, int C, int H, int W, int64_t* bytes) {
+  if (N < 0 || C < 0 || H < 0 || W < 0 || !bytes) return VIDAR_ERR_BAD_ARG;
+  *bytes = (int64_t)det_workspace_bytes((size_t)N * C * H * W);
+  return 0;
+}
+
 int vidar_dcn_col2im_f32(const float* grad_cols, const float* x, const float* offset,
                          const float* mask, float* grad_x, float* grad_offset, float* grad_mask,
                          int N, int C, int H, int W, int Ho, int Wo, int kh, int kw, int stride,
@@ -563,7 +582,22 @@ int vidar_dcn_col2im_f32(const float* grad_cols, const float* x, const float* of
   if (N == 0) return 0;
   if (kh * kw > kMaxTaps) return VIDAR_ERR_BAD_ARG;
   const int P = Ho * Wo, K = kh * kw, HW = H * W;
-  if (workspace) {
+  if (det_mode()) {
+    // the plain scatter for every call and variant (the gather forms read record lists that atomic cursors filled):
+    // 4 corners per (image, channel, tap, output pixel)
+    const dim3 grid((P + 255) / 256, (C + kCG - 1) / kCG, N);
+    const int rc = det_scatter(
+        grad_x, nullptr, (size_t)N * C * HW, 0, (uint64_t)N * C * K * P * 4, false, workspace, workspace_bytes, s,
+        [&](uint32_t* word, uint32_t*) {
+          hipLaunchKernelGGL((dcn_col2im_kernel<det::AccMeasure, det::AccMeasure::Param>), grid, dim3(256), 0, s, grad_cols, offset, mask, grad_x, g,
+                             det::AccMeasure::Param{word});
+        },
+        [&](long long* acc, long long*, const uint32_t* word, const uint32_t*, int h) {
+          hipLaunchKernelGGL((dcn_col2im_kernel<det::AccFixed, det::AccFixed::Param>), grid, dim3(256), 0, s, grad_cols, offset, mask, grad_x, g,
+                             det::AccFixed::Param{acc, word, h});
+        });
+    if (rc != 0) return rc;
+  } else if (workspace) {
     const size_t need = vidar_dcn_col2im_workspace_bytes(N, H, W, Ho, Wo, kh, kw);
     if (need == 0 || workspace_bytes < need) return VIDAR_ERR_BAD_ARG;
     int* cursor = (int*)workspace;
@@ -588,7 +622,7 @@ int vidar_dcn_col2im_f32(const float* grad_cols, const float* x, const float* of
   } else {
     hipError_t e = hipMemsetAsync(grad_x, 0, sizeof(float) * (size_t)N * C * H * W, s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(dcn_col2im_kernel, dim3((P + 255) / 256, (C + kCG - 1) / kCG, N), dim3(256), 0, s, grad_cols,
+    hipLaunchKernelGGL(dcn_col2im_kernel<det::AccAtomic>, dim3((P + 255) / 256, (C + kCG - 1) / kCG, N), dim3(256), 0, s, grad_cols,
                        offset, mask, grad_x, g);
   }
   hipLaunchKernelGGL(W >= 2 ? dcn_col2im_coord_kernel : dcn_col2im_coord_1col_kernel, dim3((P + 255) / 256, K, N), dim3(256), 0,

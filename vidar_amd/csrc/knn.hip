@@ -20,6 +20,7 @@
 
 #include "vidar_hip.h"
 #include "vidar_common.h"
+#include "det_scatter.h"
 
 namespace {
 
@@ -101,11 +102,16 @@ __global__ __launch_bounds__(256) void knn1_finalize_kernel(
 }
 
 // grad_p1[n,i,:] = 2 g (p1 - p2[idx]);  grad_p2[n,idx,:] -= the same (knn_cpu.cpp:93-101)
-__global__ __launch_bounds__(256) void knn1_d3_bwd_kernel(
+// `acc`: the accumulate policy of det_acc.h for grad_p2; the measure pass of the deterministic mode leaves grad_p1 to
+// the fixed-point pass
+// (the measure kernel flushes behind this body with a workgroup barrier: a `return` here must stay a return from this
+// inlined function, never become one from a kernel)
+template <class Acc>
+__device__ __forceinline__ void knn1_d3_bwd_body(
     const float* __restrict__ p1, const float* __restrict__ p2, const int64_t* __restrict__ len1,
     const int64_t* __restrict__ len2, const int64_t* __restrict__ idx,
     const float* __restrict__ grad_dist, float* __restrict__ grad_p1, float* __restrict__ grad_p2,
-    int P1, int P2) {
+    int P1, int P2, Acc& acc) {
   const int n = blockIdx.y;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= P1) return;
@@ -118,12 +124,35 @@ __global__ __launch_bounds__(256) void knn1_d3_bwd_kernel(
       const float* b = p2 + ((size_t)n * P2 + j) * 3;
       gx = g2 * (a[0] - b[0]); gy = g2 * (a[1] - b[1]); gz = g2 * (a[2] - b[2]);
       float* o = grad_p2 + ((size_t)n * P2 + j) * 3;
-      unsafeAtomicAdd(o + 0, -gx); unsafeAtomicAdd(o + 1, -gy); unsafeAtomicAdd(o + 2, -gz);
+      acc.add(o + 0, -gx); acc.add(o + 1, -gy); acc.add(o + 2, -gz);
     }
   }
+  if (Acc::kMeasureOnly) return;
   float* o1 = grad_p1 + ((size_t)n * P1 + i) * 3;
   o1[0] = gx; o1[1] = gy; o1[2] = gz;
 }
+
+#define KNN_BWD_IN const float* __restrict__ p1, const float* __restrict__ p2, const int64_t* __restrict__ len1, \
+                   const int64_t* __restrict__ len2, const int64_t* __restrict__ idx, const float* __restrict__ grad_dist
+__global__ __launch_bounds__(256) void knn1_d3_bwd_kernel(KNN_BWD_IN, float* __restrict__ grad_p1,
+                                                          float* __restrict__ grad_p2, int P1, int P2) {
+  det::AccAtomic acc;
+  knn1_d3_bwd_body(p1, p2, len1, len2, idx, grad_dist, grad_p1, grad_p2, P1, P2, acc);
+}
+__global__ __launch_bounds__(256) void knn1_d3_bwd_measure_kernel(KNN_BWD_IN, float* __restrict__ grad_p2, int P1, int P2,
+                                                                  uint32_t* __restrict__ word) {
+  det::AccMeasure acc(nullptr, {word});
+  knn1_d3_bwd_body(p1, p2, len1, len2, idx, grad_dist, nullptr, grad_p2, P1, P2, acc);
+  acc.flush();
+}
+__global__ __launch_bounds__(256) void knn1_d3_bwd_fixed_kernel(KNN_BWD_IN, float* __restrict__ grad_p1,
+                                                                float* __restrict__ grad_p2, int P1, int P2,
+                                                                long long* __restrict__ acc64,
+                                                                const uint32_t* __restrict__ word, int h) {
+  det::AccFixed acc(grad_p2, {acc64, word, h});
+  knn1_d3_bwd_body(p1, p2, len1, len2, idx, grad_dist, grad_p1, grad_p2, P1, P2, acc);
+}
+#undef KNN_BWD_IN
 
 }  // namespace
 
@@ -156,12 +185,39 @@ int vidar_knn1_d3_fwd(const float* p1, const float* p2, const int64_t* lengths1,
   return vidar_last_error();
 }
 
+int vidar_knn1_d3_bwd_workspace_bytes(int N, int P2, int64_t* bytes) {
+  if (N < 0 || P2 < 0 || !bytes) return VIDAR_ERR_BAD_ARG;
+  *bytes = det_mode() ? (int64_t)det_workspace_bytes((size_t)N * P2 * 3) : 0;
+  return 0;
+}
+
 int vidar_knn1_d3_bwd(const float* p1, const float* p2, const int64_t* lengths1,
                       const int64_t* lengths2, const int64_t* idx, const float* grad_dist2,
                       float* grad_p1, float* grad_p2, int N, int P1, int P2, void* stream) {
+  return vidar_knn1_d3_bwd_ws(p1, p2, lengths1, lengths2, idx, grad_dist2, grad_p1, grad_p2, N, P1, P2, nullptr, 0,
+                              stream);
+}
+
+int vidar_knn1_d3_bwd_ws(const float* p1, const float* p2, const int64_t* lengths1,
+                         const int64_t* lengths2, const int64_t* idx, const float* grad_dist2,
+                         float* grad_p1, float* grad_p2, int N, int P1, int P2, void* workspace,
+                         size_t workspace_bytes, void* stream) {
   VIDAR_ENTER();
   if (N < 0 || P1 < 0 || P2 < 0) return VIDAR_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
+  if (det_mode() && P2 > 0) {     // three contributions per point of p1 (no p2 point: the default kernel zeroes grad_p1)
+    const dim3 grid((P1 + 255) / 256, N);
+    return det_scatter(
+        grad_p2, nullptr, (size_t)N * P2 * 3, 0, (uint64_t)N * P1 * 3, N == 0 || P1 == 0, workspace, workspace_bytes, s,
+        [&](uint32_t* word, uint32_t*) {
+          hipLaunchKernelGGL(knn1_d3_bwd_measure_kernel, grid, dim3(256), 0, s, p1, p2, lengths1, lengths2, idx,
+                             grad_dist2, grad_p2, P1, P2, word);
+        },
+        [&](long long* acc, long long*, const uint32_t* word, const uint32_t*, int h) {
+          hipLaunchKernelGGL(knn1_d3_bwd_fixed_kernel, grid, dim3(256), 0, s, p1, p2, lengths1, lengths2, idx,
+                             grad_dist2, grad_p1, grad_p2, P1, P2, acc, word, h);
+        });
+  }
   if (N > 0 && P2 > 0) {
     hipError_t e = hipMemsetAsync(grad_p2, 0, sizeof(float) * (size_t)N * P2 * 3, s);
     if (e != hipSuccess) return (int)e;

@@ -30,6 +30,7 @@
 #include "vidar_hip.h"
 #include "vidar_common.h"
 #include "scatter_copies.h"
+#include "det_scatter.h"
 
 namespace {
 
@@ -139,10 +140,12 @@ __device__ __forceinline__ Vec<V> tap_load(const float* __restrict__ map, const 
   }
   return acc;
 }
-__device__ __forceinline__ void tap_scatter1(float* __restrict__ map, const Tap& t, int C, int ch, float g) {
+// `acc`: the accumulate policy of det_acc.h (fp32 atomic / measure / fixed point) of the map
+template <class Acc>
+__device__ __forceinline__ void tap_scatter1(float* __restrict__ map, const Tap& t, int C, int ch, float g, Acc& acc) {
 #pragma unroll
   for (int c = 0; c < 4; ++c)
-    if (t.o[c] >= 0) unsafeAtomicAdd(map + (size_t)t.o[c] * C + ch, t.w[c] * g);
+    if (t.o[c] >= 0) acc.add(map + (size_t)t.o[c] * C + ch, t.w[c] * g);
 }
 // stage 2: the path probability that weights LoRA channels ch .. ch+V-1, i.e. of the bins (ch+i) / J
 template <int V>
@@ -248,9 +251,12 @@ __device__ __forceinline__ void lr_prob_fwd(const float* __restrict__ occ, float
 
 // stage 1 backward: grad_prob [bs,Q,Z] -> grad_occ [bs,Q,Z] (pre-zeroed, atomics); lane = (waypoint slot, bin): one
 // atomic instruction covers the contiguous bytes of a tap corner (atomics cost per instruction x line, see msda.hip)
-template <int LPW, int ZC>
+// (Acc: the accumulate policy of det_acc.h.  The measure kernels flush behind the two backward bodies with a workgroup
+// barrier: their early `return`s leave the inlined body, and must never become returns from a kernel.)
+template <int LPW, int ZC, class Acc>
 __device__ __forceinline__ void lr_prob_bwd(const float* __restrict__ occ, const float* __restrict__ grad_prob,
-                                            float* __restrict__ grad_occ, int Q, int Zr, const Geo& g, int ncopies) {
+                                            float* __restrict__ grad_occ, int Q, int Zr, const Geo& g, int ncopies,
+                                            Acc& acc) {
   const int Z = ZC ? ZC : Zr;
   const int b = blockIdx.y;
   const int q = blockIdx.x * kCellsPerBlock + threadIdx.x / 64;
@@ -283,10 +289,10 @@ __device__ __forceinline__ void lr_prob_bwd(const float* __restrict__ occ, const
       const float x = tap_load<1>(map, t, Z, z).e[0];
       const float p = act_f(x, g.act);
       const float gs = (1.f - p) > 0.f ? -gp / (1.f - p) * act_d(x, p, g.act) : 0.f;
-      tap_scatter1(gmap, t, Z, z, gs);
+      tap_scatter1(gmap, t, Z, z, gs, acc);
     }
   }
-  if (ks == 0) tap_scatter1(gmap, tc, Z, z, go * pr.e[0] * act_d(xc, pc, g.act));
+  if (ks == 0) tap_scatter1(gmap, tc, Z, z, go * pr.e[0] * act_d(xc, pc, g.act), acc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -341,11 +347,12 @@ __device__ __forceinline__ void lr_gather_fwd(const float* __restrict__ prob, co
 // stage 2 backward: grad_feat [bs,Q,A] -> grad_prob [bs,Q,Z], grad_a [bs,Q,A] (pre-zeroed, atomics); lane = (waypoint
 // slot, channel), A > LPW is walked in chunks.  grad_prob of a bin is summed over the bin's channels inside the wave
 // and added by the bin's first lane of the chunk.
-template <int LPW, int ZC>
+template <int LPW, int ZC, class Acc>
 __device__ __forceinline__ void lr_gather_bwd(
     const float* __restrict__ prob, const float* __restrict__ a, const float* __restrict__ feat,
     const float* __restrict__ msum, const float* __restrict__ grad_feat,
-    float* __restrict__ grad_prob, float* __restrict__ grad_a, int Q, int Zr, int Ar, const Geo& g, int ncopies) {
+    float* __restrict__ grad_prob, float* __restrict__ grad_a, int Q, int Zr, int Ar, const Geo& g, int ncopies,
+    Acc& acc_prob, Acc& acc_a) {
   const int Z = ZC ? ZC : Zr, A = ZC ? ZC : Ar, J = ZC ? 1 : Ar / Zr;
   const int b = blockIdx.y;
   const int q = blockIdx.x * kCellsPerBlock + threadIdx.x / 64;
@@ -374,11 +381,11 @@ __device__ __forceinline__ void lr_gather_bwd(
         if (on) {
           const float m = tap_load<1>(pm, t, Z, bin).e[0];
           const float av = tap_load<1>(am, t, A, ch).e[0];
-          tap_scatter1(gam, t, A, ch, s * m);
+          tap_scatter1(gam, t, A, ch, s * m, acc_a);
           gp = s * (av - f);
         }
         if (J > 1) gp = group_sum<LPW>(gp, ahead);
-        if (first) tap_scatter1(gpm, t, Z, bin, gp);
+        if (first) tap_scatter1(gpm, t, Z, bin, gp, acc_prob);
       }
     }
   }
@@ -394,7 +401,8 @@ __global__ __launch_bounds__(kThreads) void lr_prob_fwd_kernel(const float* __re
 __global__ __launch_bounds__(kThreads) void lr_prob_bwd_kernel(const float* __restrict__ occ,
                                                                const float* __restrict__ grad_prob,
                                                                float* __restrict__ grad_occ, int Q, Geo g, int ncopies) {
-  lr_prob_bwd<16, 16>(occ, grad_prob, grad_occ, Q, 16, g, ncopies);
+  det::AccAtomic acc;
+  lr_prob_bwd<16, 16>(occ, grad_prob, grad_occ, Q, 16, g, ncopies, acc);
 }
 __global__ __launch_bounds__(kThreads) void lr_gather_fwd_kernel(const float* __restrict__ prob,
                                                                  const float* __restrict__ a, float* __restrict__ feat,
@@ -405,7 +413,8 @@ __global__ __launch_bounds__(kThreads) void lr_gather_bwd_kernel(
     const float* __restrict__ prob, const float* __restrict__ a, const float* __restrict__ feat,
     const float* __restrict__ msum, const float* __restrict__ grad_feat,
     float* __restrict__ grad_prob, float* __restrict__ grad_a, int Q, Geo g, int ncopies) {
-  lr_gather_bwd<16, 16>(prob, a, feat, msum, grad_feat, grad_prob, grad_a, Q, 16, 16, g, ncopies);
+  det::AccAtomic acc;
+  lr_gather_bwd<16, 16>(prob, a, feat, msum, grad_feat, grad_prob, grad_a, Q, 16, 16, g, ncopies, acc, acc);
 }
 template <int LPW, int V>
 __global__ __launch_bounds__(kThreads) void lr_prob_fwd_any_kernel(const float* __restrict__ occ,
@@ -417,7 +426,8 @@ __global__ __launch_bounds__(kThreads) void lr_prob_bwd_any_kernel(const float* 
                                                                    const float* __restrict__ grad_prob,
                                                                    float* __restrict__ grad_occ, int Q, int Z, Geo g,
                                                                    int ncopies) {
-  lr_prob_bwd<LPW, 0>(occ, grad_prob, grad_occ, Q, Z, g, ncopies);
+  det::AccAtomic acc;
+  lr_prob_bwd<LPW, 0>(occ, grad_prob, grad_occ, Q, Z, g, ncopies, acc);
 }
 template <int LPW, int V>
 __global__ __launch_bounds__(kThreads) void lr_gather_fwd_any_kernel(const float* __restrict__ prob,
@@ -431,7 +441,49 @@ __global__ __launch_bounds__(kThreads) void lr_gather_bwd_any_kernel(
     const float* __restrict__ prob, const float* __restrict__ a, const float* __restrict__ feat,
     const float* __restrict__ msum, const float* __restrict__ grad_feat,
     float* __restrict__ grad_prob, float* __restrict__ grad_a, int Q, int Z, int A, Geo g, int ncopies) {
-  lr_gather_bwd<LPW, 0>(prob, a, feat, msum, grad_feat, grad_prob, grad_a, Q, Z, A, g, ncopies);
+  det::AccAtomic acc;
+  lr_gather_bwd<LPW, 0>(prob, a, feat, msum, grad_feat, grad_prob, grad_a, Q, Z, A, g, ncopies, acc, acc);
+}
+
+// Deterministic mode (det_acc.h): the shape-generic bodies with the measure policy, then with the fixed-point policy,
+// adding straight into the accumulator volumes (no private copies).
+template <int LPW>
+__global__ __launch_bounds__(kThreads) void lr_prob_bwd_measure_kernel(const float* __restrict__ occ,
+                                                                       const float* __restrict__ grad_prob,
+                                                                       float* __restrict__ grad_occ, int Q, int Z, Geo g,
+                                                                       uint32_t* __restrict__ word) {
+  det::AccMeasure acc(nullptr, {word});
+  lr_prob_bwd<LPW, 0>(occ, grad_prob, grad_occ, Q, Z, g, 1, acc);
+  acc.flush();
+}
+template <int LPW>
+__global__ __launch_bounds__(kThreads) void lr_prob_bwd_fixed_kernel(const float* __restrict__ occ,
+                                                                     const float* __restrict__ grad_prob,
+                                                                     float* __restrict__ grad_occ, int Q, int Z, Geo g,
+                                                                     long long* __restrict__ acc64,
+                                                                     const uint32_t* __restrict__ word, int h) {
+  det::AccFixed acc(grad_occ, {acc64, word, h});
+  lr_prob_bwd<LPW, 0>(occ, grad_prob, grad_occ, Q, Z, g, 1, acc);
+}
+template <int LPW>
+__global__ __launch_bounds__(kThreads) void lr_gather_bwd_measure_kernel(
+    const float* __restrict__ prob, const float* __restrict__ a, const float* __restrict__ feat,
+    const float* __restrict__ msum, const float* __restrict__ grad_feat, float* __restrict__ grad_prob,
+    float* __restrict__ grad_a, int Q, int Z, int A, Geo g, uint32_t* __restrict__ word_prob,
+    uint32_t* __restrict__ word_a) {
+  det::AccMeasure acc_prob(nullptr, {word_prob}), acc_a(nullptr, {word_a});
+  lr_gather_bwd<LPW, 0>(prob, a, feat, msum, grad_feat, grad_prob, grad_a, Q, Z, A, g, 1, acc_prob, acc_a);
+  acc_prob.flush();
+  acc_a.flush();
+}
+template <int LPW>
+__global__ __launch_bounds__(kThreads) void lr_gather_bwd_fixed_kernel(
+    const float* __restrict__ prob, const float* __restrict__ a, const float* __restrict__ feat,
+    const float* __restrict__ msum, const float* __restrict__ grad_feat, float* __restrict__ grad_prob,
+    float* __restrict__ grad_a, int Q, int Z, int A, Geo g, long long* __restrict__ acc64_prob,
+    long long* __restrict__ acc64_a, const uint32_t* __restrict__ word_prob, const uint32_t* __restrict__ word_a, int h) {
+  det::AccFixed acc_prob(grad_prob, {acc64_prob, word_prob, h}), acc_a(grad_a, {acc64_a, word_a, h});
+  lr_gather_bwd<LPW, 0>(prob, a, feat, msum, grad_feat, grad_prob, grad_a, Q, Z, A, g, 1, acc_prob, acc_a);
 }
 
 inline bool lr_bad(int bs, int H, int W, int Z, int G, int act) {
@@ -494,6 +546,21 @@ int gather_bwd(const float* prob, const float* a, const float* feat, const float
                size_t workspace_bytes, hipStream_t s) {
   const size_t nz = (size_t)bs * H * W * Z, na = (size_t)bs * H * W * A;
   const int Q = H * W;
+  if (det_mode())       // 4 corners of G waypoints per (cell, channel), for either map
+    return det_scatter(
+        grad_prob, grad_a, nz, na, (uint64_t)na * g.G * 4, false, workspace, workspace_bytes, s,
+        [&](uint32_t* wp, uint32_t* wa) {
+          with_lanes(A, [&](auto l) {
+            lr_launch(lr_gather_bwd_measure_kernel<decltype(l)::value>, bs, Q, s, prob, a, feat, msum, grad_feat,
+                      grad_prob, grad_a, Q, Z, A, g, wp, wa);
+          });
+        },
+        [&](long long* ap, long long* aa, const uint32_t* wp, const uint32_t* wa, int h) {
+          with_lanes(A, [&](auto l) {
+            lr_launch(lr_gather_bwd_fixed_kernel<decltype(l)::value>, bs, Q, s, prob, a, feat, msum, grad_feat,
+                      grad_prob, grad_a, Q, Z, A, g, ap, aa, wp, wa, h);
+          });
+        });
   const auto launch = [&](float* sp, float* sa, int ncopies) {
     if (Z == 16 && A == 16)
       lr_launch(lr_gather_bwd_kernel, bs, Q, s, prob, a, feat, msum, grad_feat, sp, sa, Q, g, ncopies);
@@ -514,6 +581,7 @@ extern "C" {
 
 size_t vidar_latent_render_bwd_workspace_bytes(int bs, int H, int W, int Z, int maps) {
   if (bs <= 0 || H <= 0 || W <= 0 || Z <= 0 || maps < 1 || maps > 2) return 0;
+  if (det_mode()) return det_workspace_bytes((size_t)bs * H * W * Z * maps, maps);
   return scatter_workspace_bytes((size_t)bs * H * W * Z, maps);   // maps: 1 = prob_bwd (grad_occ), 2 = gather_bwd
 }
 
@@ -535,6 +603,23 @@ int vidar_latent_render_prob_bwd_f32(const float* occ, const float* grad_path_pr
   hipStream_t s = (hipStream_t)stream;
   Geo g{H, W, grid_num, step, act, 0.f};
   const size_t n = (size_t)bs * H * W * Z;
+  if (det_mode()) {     // 4 corners of the G waypoints and of the cell itself per (cell, bin)
+    const int Q = H * W;
+    return det_scatter(
+        grad_occ, nullptr, n, 0, (uint64_t)n * ((uint64_t)grid_num + 1) * 4, false, workspace, workspace_bytes, s,
+        [&](uint32_t* word, uint32_t*) {
+          with_lanes(Z, [&](auto l) {
+            lr_launch(lr_prob_bwd_measure_kernel<decltype(l)::value>, bs, Q, s, occ, grad_path_prob, grad_occ, Q, Z, g,
+                      word);
+          });
+        },
+        [&](long long* acc, long long*, const uint32_t* word, const uint32_t*, int h) {
+          with_lanes(Z, [&](auto l) {
+            lr_launch(lr_prob_bwd_fixed_kernel<decltype(l)::value>, bs, Q, s, occ, grad_path_prob, grad_occ, Q, Z, g,
+                      acc, word, h);
+          });
+        });
+  }
   const auto launch = [&](float* acc, float*, int ncopies) {
     launch_prob_bwd(occ, grad_path_prob, acc, bs, H, W, Z, g, ncopies, s);
   };

@@ -28,6 +28,7 @@
 
 #include "vidar_hip.h"
 #include "vidar_common.h"
+#include "det_scatter.h"
 
 namespace {
 
@@ -436,12 +437,18 @@ __device__ __forceinline__ float ld1(const float* __restrict__ p, int64_t o) {
   return o >= 0 ? p[o] : 0.f;
 }
 
+// Acc: the accumulate policy of det_acc.h for grad_value -- det::AccAtomic (fp32 atomics, the default mode), or the two
+// passes of the deterministic mode: det::AccMeasure, which ends before the store phase, then det::AccFixed.
+// AccMeasure::flush holds a workgroup barrier: every thread of a workgroup that runs the item loop must reach it, so no
+// early `return` may be added between the `blk >= nblocks` exit (whole workgroups) and the flush.
+template <class Acc, class... AccParam>
 __global__ __launch_bounds__(kThreads) void msda_bwd_kernel(
     const float* __restrict__ value, const int64_t* __restrict__ shapes,
     const int64_t* __restrict__ lsi, const float* __restrict__ loc, const float* __restrict__ attw,
     const float* __restrict__ grad_out, float* __restrict__ grad_value,
     float* __restrict__ grad_loc, float* __restrict__ grad_w, int Nv, int H, int Nq, int L, int P,
-    int64_t n_items, int nblocks, Prep pr, GoMap gm) {
+    int64_t n_items, int nblocks, Prep pr, GoMap gm, AccParam... acc_param) {
+  Acc acc(grad_value, acc_param...);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ Levels lv;
   const int LP = L * P;
@@ -483,10 +490,10 @@ __global__ __launch_bounds__(kThreads) void msda_bwd_kernel(
           sample_grads(c.lh, c.lw, w, Wl, Hl, d00, d01, d10, d11, gx, gy, gw);
           const float hh = 1.f - c.lh, hw = 1.f - c.lw;
           const float wg = w * go;
-          if (o00 >= 0) unsafeAtomicAdd(gvb + o00, hh * hw * wg);
-          if (o01 >= 0) unsafeAtomicAdd(gvb + o01, hh * c.lw * wg);
-          if (o10 >= 0) unsafeAtomicAdd(gvb + o10, c.lh * hw * wg);
-          if (o11 >= 0) unsafeAtomicAdd(gvb + o11, c.lh * c.lw * wg);
+          if (o00 >= 0) acc.add(gvb + o00, hh * hw * wg);
+          if (o01 >= 0) acc.add(gvb + o01, hh * c.lw * wg);
+          if (o10 >= 0) acc.add(gvb + o10, c.lh * hw * wg);
+          if (o11 >= 0) acc.add(gvb + o11, c.lh * c.lw * wg);
         }
         gx = half_wave_sum(gx); gy = half_wave_sum(gy); gw = half_wave_sum(gw);
         // all 32 lanes consumed (x, y, w) of this point before the shuffles finished
@@ -498,6 +505,7 @@ __global__ __launch_bounds__(kThreads) void msda_bwd_kernel(
       }
     }
   }
+  if constexpr (Acc::kMeasureOnly) { acc.flush(); return; }
   __syncthreads();
   // store phase: s_loc / s_w hold grad_loc / grad_w of `nvalid` items
   if (pr.g_off_raw == nullptr) {
@@ -1081,6 +1089,29 @@ static int msda_bwd_launch(const float* value, const int64_t* spatial_shapes,
   const GoMap gm{pr.merge ? pr.Qn : 1, Nq * H, pr.merge ? 1.f / pr.Qn : 1.f};
   hipStream_t s = (hipStream_t)stream;
   const size_t vbytes = sizeof(float) * (size_t)B * Nv * H * C;
+  if (det_mode() && vbytes != 0) {   // (an empty `value` has nothing to scatter: the default kernel writes grad_loc / grad_w)
+    // the plain scatter form for every size (no binned path: its records are filled through atomic cursors); grad_loc /
+    // grad_w are this form's, bit for bit those of a default-mode call without a workspace.  4 corners x 32 channels
+    // per sample.
+    const int64_t n_items = (int64_t)B * Nq * H;
+    const int nblocks = (int)((n_items + kBItems - 1) / kBItems);
+    const int grid = ((nblocks + 7) / 8) * 8;
+    const size_t lds = sizeof(float) * (kBItems * L * P * 3 + kBItems);
+    return det_scatter(
+        grad_value, nullptr, (size_t)B * Nv * H * C, 0, (uint64_t)n_items * L * P * 4 * kCh, n_items == 0, workspace,
+        workspace_bytes, s,
+        [&](uint32_t* word, uint32_t*) {
+          hipLaunchKernelGGL((msda_bwd_kernel<det::AccMeasure, det::AccMeasure::Param>), dim3(grid), dim3(kThreads), lds, s, value, spatial_shapes,
+                             level_start_index, sampling_loc, attn_weight, grad_out, grad_value, grad_sampling_loc,
+                             grad_attn_weight, Nv, H, Nq, L, P, n_items, nblocks, pr, gm, det::AccMeasure::Param{word});
+        },
+        [&](long long* acc, long long*, const uint32_t* word, const uint32_t*, int h) {
+          hipLaunchKernelGGL((msda_bwd_kernel<det::AccFixed, det::AccFixed::Param>), dim3(grid), dim3(kThreads), lds, s, value, spatial_shapes,
+                             level_start_index, sampling_loc, attn_weight, grad_out, grad_value, grad_sampling_loc,
+                             grad_attn_weight, Nv, H, Nq, L, P, n_items, nblocks, pr, gm,
+                             det::AccFixed::Param{acc, word, h});
+        });
+  }
   if (vbytes) {
     hipError_t e = hipMemsetAsync(grad_value, 0, vbytes, s);
     if (e != hipSuccess) return (int)e;
@@ -1128,7 +1159,7 @@ static int msda_bwd_launch(const float* value, const int64_t* spatial_shapes,
   const int nblocks = (int)((n_items + kBItems - 1) / kBItems);
   const int grid = ((nblocks + 7) / 8) * 8;
   const size_t lds = sizeof(float) * (kBItems * L * P * 3 + kBItems);
-  hipLaunchKernelGGL(msda_bwd_kernel, dim3(grid), dim3(kThreads), lds, s, value, spatial_shapes,
+  hipLaunchKernelGGL(msda_bwd_kernel<det::AccAtomic>, dim3(grid), dim3(kThreads), lds, s, value, spatial_shapes,
                      level_start_index, sampling_loc, attn_weight, grad_out, grad_value,
                      grad_sampling_loc, grad_attn_weight, Nv, H, Nq, L, P, n_items, nblocks, pr, gm);
   return vidar_last_error();
@@ -1152,6 +1183,7 @@ int vidar_msda_fwd_f32(const float* value, const int64_t* spatial_shapes,
 
 size_t vidar_msda_bwd_workspace_bytes(int B, int Nv, int H, int Nq, int L, int P) {
   if (B <= 0 || Nv <= 0 || H <= 0 || Nq <= 0 || L <= 0 || P <= 0) return 0;
+  if (det_mode()) return det_workspace_bytes((size_t)B * Nv * H * kCh);
   const BinPlan p = bin_plan(B, Nv, H, Nq, L, P);
   return p.ok ? p.bytes : 0;
 }

@@ -135,14 +135,16 @@ __global__ __launch_bounds__(256) void drop_add_ln_bwd_kernel(
 // second stage: grid (16 column blocks, kSlices row slices); block = 32 of the 2*256 affine-gradient columns x 8 row
 // lanes.  Every thread sums its share of the partial rows, the 8 lanes meet in LDS, one atomic per (block, column)
 // onto the result -- which workgroup 0 of the first stage zeroed (stream order makes that safe, no memset launch).
+// ORDERED (the deterministic mode, grid (16, 1)): one slice, so a column's partial rows are summed by one workgroup in
+// a fixed order and the result is stored, no atomic.
 constexpr int kSlices = 8;
-__global__ __launch_bounds__(256) void affine_grad_reduce_kernel(const float* __restrict__ partial, int nparts,
-                                                                 float* __restrict__ dgamma,
-                                                                 float* __restrict__ dbeta) {
+template <bool ORDERED>
+__device__ __forceinline__ void affine_grad_reduce(const float* __restrict__ partial, int nparts, float* __restrict__ dgamma,
+                                                   float* __restrict__ dbeta) {
   __shared__ float s_acc[8][32];
   const int c = threadIdx.x & 31, r = threadIdx.x >> 5;
   const int col = blockIdx.x * 32 + c;                       // 0 .. 2*kC-1
-  const int per = (nparts + kSlices - 1) / kSlices;
+  const int per = ORDERED ? nparts : (nparts + kSlices - 1) / kSlices;
   const int p0 = blockIdx.y * per, p1 = min(nparts, p0 + per);
   float a0 = 0.f, a1 = 0.f;
   int i = p0 + r;
@@ -157,8 +159,20 @@ __global__ __launch_bounds__(256) void affine_grad_reduce_kernel(const float* __
     float t = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) t += s_acc[k][c];
-    unsafeAtomicAdd(col < kC ? dgamma + col : dbeta + (col - kC), t);
+    float* out = col < kC ? dgamma + col : dbeta + (col - kC);
+    if (ORDERED) *out = t;
+    else unsafeAtomicAdd(out, t);
   }
+}
+__global__ __launch_bounds__(256) void affine_grad_reduce_kernel(const float* __restrict__ partial, int nparts,
+                                                                 float* __restrict__ dgamma,
+                                                                 float* __restrict__ dbeta) {
+  affine_grad_reduce<false>(partial, nparts, dgamma, dbeta);
+}
+__global__ __launch_bounds__(256) void affine_grad_ordered_kernel(const float* __restrict__ partial, int nparts,
+                                                                  float* __restrict__ dgamma,
+                                                                  float* __restrict__ dbeta) {
+  affine_grad_reduce<true>(partial, nparts, dgamma, dbeta);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -323,8 +337,12 @@ int vidar_drop_add_ln_bwd_f32(const float* grad_y, const float* sum_in, const fl
   const int nparts = (int)((waves + 3) / 4);
   hipLaunchKernelGGL(drop_add_ln_bwd_kernel, dim3((unsigned)nparts), dim3(256), 0, s, grad_y, sum_in, gamma, mean_in,
                      rstd_in, grad_x, grad_residual, (float*)workspace, grad_gamma, grad_beta, rows, p, seed);
-  hipLaunchKernelGGL(affine_grad_reduce_kernel, dim3(2 * kC / 32, kSlices), dim3(256), 0, s, (const float*)workspace, nparts,
-                     grad_gamma, grad_beta);
+  if (vidar_get_deterministic())
+    hipLaunchKernelGGL(affine_grad_ordered_kernel, dim3(2 * kC / 32, 1), dim3(256), 0, s, (const float*)workspace, nparts,
+                       grad_gamma, grad_beta);
+  else
+    hipLaunchKernelGGL(affine_grad_reduce_kernel, dim3(2 * kC / 32, kSlices), dim3(256), 0, s, (const float*)workspace,
+                       nparts, grad_gamma, grad_beta);
   return vidar_last_error();
 }
 

@@ -39,6 +39,7 @@
 #include "vidar_hip.h"
 #include "vidar_common.h"
 #include "scatter_copies.h"
+#include "det_scatter.h"
 
 namespace {
 
@@ -108,23 +109,26 @@ __device__ __forceinline__ float tri_load(const float* __restrict__ vol, const T
     if (t.o[c] >= 0) acc += t.w[c] * vol[t.o[c]];
   return acc;
 }
-__device__ __forceinline__ void tri_scatter(float* __restrict__ gvol, const Tri& t, float g) {
+// `acc`: the accumulate policy of det_acc.h (fp32 atomic / measure / fixed point)
+template <class Acc>
+__device__ __forceinline__ void tri_scatter(float* __restrict__ gvol, const Tri& t, float g, Acc& acc) {
   if (g == 0.f) return;
 #pragma unroll
   for (int c = 0; c < 8; ++c)
-    if (t.o[c] >= 0) unsafeAtomicAdd(gvol + t.o[c], t.w[c] * g);
+    if (t.o[c] >= 0) acc.add(gvol + t.o[c], t.w[c] * g);
 }
 // the four corners with x-corner `cx` only.  fp32 global atomics cost per (instruction x 128-byte line touched)
 // (tools/micro/atomic_bench.hip): the backward kernels pair adjacent lanes on ONE waypoint -- even lane x0, odd lane
 // x0 + 1, neighbouring addresses of the x-fastest volume -- so an atomic instruction of 32 waypoints touches the lines
 // of 32 corners instead of 64: half the requests of a lane-per-waypoint scatter for the same 8 adds per waypoint.
-__device__ __forceinline__ void tri_scatter_x(float* __restrict__ gvol, const Tri& t, float g, int cx) {
+template <class Acc>
+__device__ __forceinline__ void tri_scatter_x(float* __restrict__ gvol, const Tri& t, float g, int cx, Acc& acc) {
   if (g == 0.f) return;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const int o = cx ? t.o[2 * c + 1] : t.o[2 * c];
     const float w = cx ? t.w[2 * c + 1] : t.w[2 * c];
-    if (o >= 0) unsafeAtomicAdd(gvol + o, w * g);
+    if (o >= 0) acc.add(gvol + o, w * g);
   }
 }
 
@@ -365,11 +369,13 @@ struct SampleCoef {   // saved: aux [R, 3]; d dist / d logit = pd * p * (ind - p
 // The adds go into private copies of the volume (scatter_copies.h).  (Leaving the 512-waypoint loop after the run of
 // live waypoints -- the waypoints inside the volume are ONE run of consecutive k, tests/test_ray_early_exit_cpu.py --
 // was measured too: no change, the masked passes cost almost nothing next to the atomics; removed.)
-template <bool K512, bool END_POINT, class Coef>
+// (Acc: the accumulate policy of det_acc.h.  The measure kernel flushes behind this body with a workgroup barrier: the
+// early `return`s below leave this inlined function, and must never become returns from a kernel.)
+template <bool K512, bool END_POINT, class Coef, class Acc>
 __device__ __forceinline__ void ray_bwd_body(
     const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
     const float* __restrict__ tindex, const float* __restrict__ saved, const float* __restrict__ grad,
-    float* __restrict__ grad_sigma, int R, VolDims v, float step, int ncopies, int K) {
+    float* __restrict__ grad_sigma, int R, VolDims v, float step, int ncopies, int K, Acc& acc) {
   const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
   if (r >= R) return;
   const int lane = threadIdx.x % kWave;
@@ -383,7 +389,7 @@ __device__ __forceinline__ void ray_bwd_body(
   float* gvol = grad_sigma + scatter_copy_of_block(ncopies) * v.F * v.Z * v.Y * v.X + slice;
   const Coef coef(saved, r);
   if (END_POINT && lane == 0)
-    tri_scatter(gvol, t0, coef(g, expf(tri_load(vol, t0) - coef.lse), dist_to(ray, ray.px, ray.py, ray.pz), true));
+    tri_scatter(gvol, t0, coef(g, expf(tri_load(vol, t0) - coef.lse), dist_to(ray, ray.px, ray.py, ray.pz), true), acc);
   const int cx = lane & 1;
   const int passes = K512 ? 2 * kPerLane : (K + kWave / 2 - 1) / (kWave / 2);
   for (int j = 0; j < passes; ++j) {                   // 32 waypoints per pass, a lane pair per waypoint
@@ -393,7 +399,7 @@ __device__ __forceinline__ void ray_bwd_body(
     waypoint(ray, k, step, sx, sy, sz);
     const Tri t = make_tri(sx, sy, sz, v);
     if (t.masked) continue;
-    tri_scatter_x(gvol, t, coef(g, expf(tri_load(vol, t) - coef.lse), dist_to(ray, sx, sy, sz), false), cx);
+    tri_scatter_x(gvol, t, coef(g, expf(tri_load(vol, t) - coef.lse), dist_to(ray, sx, sy, sz), false), cx, acc);
   }
 }
 
@@ -415,11 +421,13 @@ RAY_KERNEL ray_ce_fwd_any_kernel(RAY_IN, float* __restrict__ ce, float* __restri
 }
 RAY_KERNEL ray_ce_bwd_kernel(RAY_IN, const float* __restrict__ lse, const float* __restrict__ grad_ce,
                              float* __restrict__ grad_sigma, int R, VolDims v, float step, int ncopies) {
-  ray_bwd_body<true, true, CeCoef>(sigma, origin, pts, tindex, lse, grad_ce, grad_sigma, R, v, step, ncopies, kK);
+  det::AccAtomic acc;
+  ray_bwd_body<true, true, CeCoef>(sigma, origin, pts, tindex, lse, grad_ce, grad_sigma, R, v, step, ncopies, kK, acc);
 }
 RAY_KERNEL ray_ce_bwd_any_kernel(RAY_IN, const float* __restrict__ lse, const float* __restrict__ grad_ce,
                                  float* __restrict__ grad_sigma, int R, VolDims v, float step, int ncopies, int K) {
-  ray_bwd_body<false, true, CeCoef>(sigma, origin, pts, tindex, lse, grad_ce, grad_sigma, R, v, step, ncopies, K);
+  det::AccAtomic acc;
+  ray_bwd_body<false, true, CeCoef>(sigma, origin, pts, tindex, lse, grad_ce, grad_sigma, R, v, step, ncopies, K, acc);
 }
 
 RAY_KERNEL ray_gumbel_fwd_kernel(RAY_IN, const float* __restrict__ noise, float* __restrict__ dist,
@@ -432,11 +440,13 @@ RAY_KERNEL ray_gumbel_fwd_any_kernel(RAY_IN, const float* __restrict__ noise, fl
 }
 RAY_KERNEL ray_gumbel_bwd_kernel(RAY_IN, const float* __restrict__ aux, const float* __restrict__ grad_dist,
                                  float* __restrict__ grad_sigma, int R, VolDims v, float step, int ncopies) {
-  ray_bwd_body<true, false, SampleCoef>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, v, step, ncopies, kK);
+  det::AccAtomic acc;
+  ray_bwd_body<true, false, SampleCoef>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, v, step, ncopies, kK, acc);
 }
 RAY_KERNEL ray_gumbel_bwd_any_kernel(RAY_IN, const float* __restrict__ aux, const float* __restrict__ grad_dist,
                                      float* __restrict__ grad_sigma, int R, VolDims v, float step, int ncopies, int K) {
-  ray_bwd_body<false, false, SampleCoef>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, v, step, ncopies, K);
+  det::AccAtomic acc;
+  ray_bwd_body<false, false, SampleCoef>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, v, step, ncopies, K, acc);
 }
 
 RAY_KERNEL ray_dist_fwd_kernel(RAY_IN, const float* __restrict__ noise, float* __restrict__ dist,
@@ -446,7 +456,8 @@ RAY_KERNEL ray_dist_fwd_kernel(RAY_IN, const float* __restrict__ noise, float* _
 }
 RAY_KERNEL ray_dist_bwd_kernel(RAY_IN, const float* __restrict__ aux, const float* __restrict__ grad_dist,
                                float* __restrict__ grad_sigma, int R, VolDims v, float step, int ncopies, int K) {
-  ray_bwd_body<false, true, SampleCoef>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, v, step, ncopies, K);
+  det::AccAtomic acc;
+  ray_bwd_body<false, true, SampleCoef>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, v, step, ncopies, K, acc);
 }
 
 RAY_KERNEL ray_argmax_kernel(RAY_IN, float* __restrict__ pred_dist, float* __restrict__ gt_dist, int R, VolDims v,
@@ -456,6 +467,24 @@ RAY_KERNEL ray_argmax_kernel(RAY_IN, float* __restrict__ pred_dist, float* __res
 RAY_KERNEL ray_argmax_any_kernel(RAY_IN, float* __restrict__ pred_dist, float* __restrict__ gt_dist, int R, VolDims v,
                                  float step, int K) {
   ray_argmax_body<false>(sigma, origin, pts, tindex, pred_dist, gt_dist, R, v, step, K);
+}
+
+// Deterministic mode (det_acc.h): the same body with the measure policy, then with the fixed-point policy, adding
+// straight into the one accumulator volume (no private copies).  Both K forms produce the same contributions.
+template <bool K512, bool END_POINT, class Coef>
+RAY_KERNEL ray_bwd_measure_kernel(RAY_IN, const float* __restrict__ saved, const float* __restrict__ grad,
+                                  float* __restrict__ grad_sigma, int R, VolDims v, float step, int K,
+                                  uint32_t* __restrict__ word) {
+  det::AccMeasure acc(nullptr, {word});
+  ray_bwd_body<K512, END_POINT, Coef>(sigma, origin, pts, tindex, saved, grad, grad_sigma, R, v, step, 1, K, acc);
+  acc.flush();
+}
+template <bool K512, bool END_POINT, class Coef>
+RAY_KERNEL ray_bwd_fixed_kernel(RAY_IN, const float* __restrict__ saved, const float* __restrict__ grad,
+                                float* __restrict__ grad_sigma, int R, VolDims v, float step, int K,
+                                long long* __restrict__ acc64, const uint32_t* __restrict__ word, int h) {
+  det::AccFixed acc(grad_sigma, {acc64, word, h});
+  ray_bwd_body<K512, END_POINT, Coef>(sigma, origin, pts, tindex, saved, grad, grad_sigma, R, v, step, 1, K, acc);
 }
 #undef RAY_KERNEL
 #undef RAY_IN
@@ -477,12 +506,37 @@ inline void rm_launch(K512Kernel k512, AnyKernel any, int R, int K, hipStream_t 
     hipLaunchKernelGGL(any, rm_grid(R), dim3(kThreads), 0, s, args..., K);
 }
 
+
+// a ray backward in the deterministic mode: at most 8 corners of K (+ the end point) entries per ray
+template <bool END_POINT, class Coef>
+int rm_bwd_det(const float* sigma, const float* origin, const float* pts, const float* tindex, const float* saved,
+               const float* grad, float* grad_sigma, int R, int K, VolDims v, float step, void* workspace,
+               size_t workspace_bytes, hipStream_t s) {
+  const int Kk = rm_k512(K) ? kK : K;
+  return det_scatter(
+      grad_sigma, nullptr, rm_cells(v), 0, (uint64_t)R * ((uint64_t)K + END_POINT) * 8, R == 0, workspace,
+      workspace_bytes, s,
+      [&](uint32_t* word, uint32_t*) {
+        const auto k = rm_k512(K) ? ray_bwd_measure_kernel<true, END_POINT, Coef>
+                                  : ray_bwd_measure_kernel<false, END_POINT, Coef>;
+        hipLaunchKernelGGL(k, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, pts, tindex, saved, grad, grad_sigma, R,
+                           v, step, Kk, word);
+      },
+      [&](long long* acc, long long*, const uint32_t* word, const uint32_t*, int h) {
+        const auto k = rm_k512(K) ? ray_bwd_fixed_kernel<true, END_POINT, Coef>
+                                  : ray_bwd_fixed_kernel<false, END_POINT, Coef>;
+        hipLaunchKernelGGL(k, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, pts, tindex, saved, grad, grad_sigma, R,
+                           v, step, Kk, acc, word, h);
+      });
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t vidar_ray_bwd_workspace_bytes(int F, int Z, int Y, int X) {
   if (F <= 0 || Z <= 0 || Y <= 0 || X <= 0) return 0;
+  if (det_mode()) return det_workspace_bytes(rm_cells(VolDims{F, Z, Y, X}));
   return scatter_workspace_bytes(rm_cells(VolDims{F, Z, Y, X}), 1);
 }
 
@@ -513,6 +567,9 @@ int vidar_ray_ce_bwd_f32(const float* sigma, const float* origin, const float* g
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   VolDims v{F, Z, Y, X};
+  if (det_mode())
+    return rm_bwd_det<true, CeCoef>(sigma, origin, gt_pts, tindex, lse, grad_ce, grad_sigma, R, K, v, step, workspace,
+                                       workspace_bytes, s);
   return scatter_with_copies(grad_sigma, nullptr, rm_cells(v), R == 0, workspace, workspace_bytes, s,
                              [&](float* acc, float*, int ncopies) {
     rm_launch(ray_ce_bwd_kernel, ray_ce_bwd_any_kernel, R, K, s, sigma, origin, gt_pts, tindex, lse, grad_ce, acc, R, v,
@@ -540,6 +597,9 @@ int vidar_ray_gumbel_bwd_f32(const float* sigma, const float* origin, const floa
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   VolDims v{F, Z, Y, X};
+  if (det_mode())
+    return rm_bwd_det<false, SampleCoef>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, K, v, step, workspace,
+                                       workspace_bytes, s);
   return scatter_with_copies(grad_sigma, nullptr, rm_cells(v), R == 0, workspace, workspace_bytes, s,
                              [&](float* acc, float*, int ncopies) {
     rm_launch(ray_gumbel_bwd_kernel, ray_gumbel_bwd_any_kernel, R, K, s, sigma, origin, pts, tindex, aux, grad_dist, acc,
@@ -567,6 +627,9 @@ int vidar_ray_dist_bwd_f32(const float* sigma, const float* origin, const float*
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   VolDims v{F, Z, Y, X};
+  if (det_mode())
+    return rm_bwd_det<true, SampleCoef>(sigma, origin, gt_pts, tindex, aux, grad_dist, grad_sigma, R, K, v, step, workspace,
+                                       workspace_bytes, s);
   return scatter_with_copies(grad_sigma, nullptr, rm_cells(v), R == 0, workspace, workspace_bytes, s,
                              [&](float* acc, float*, int ncopies) {
     hipLaunchKernelGGL(ray_dist_bwd_kernel, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, gt_pts, tindex, aux,

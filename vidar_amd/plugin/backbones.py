@@ -6,6 +6,7 @@ map key for key.  Plain convolutions run on MIOpen through torch; the deformable
 gfx950 kernel pair of csrc/dcn.hip and the deformable convolution itself is a hipBLASLt GEMM."""
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 
@@ -18,6 +19,7 @@ from torch.autograd.function import once_differentiable
 from .registry import BACKBONES, NECKS
 from .._lib import lib, check, ptr, stream_of, workspace, TIMER
 from .. import gemm as G
+from .. import deterministic
 
 
 def dcn_col2im(grad_cols, x, offset, mask, kh, kw, stride, pad, dil, Ho, Wo, gather=True):
@@ -25,8 +27,15 @@ def dcn_col2im(grad_cols, x, offset, mask, kh, kw, stride, pad, dil, Ho, Wo, gat
     gather=True: grad_x through the per-call reverse map (no atomics); False: atomic scatter."""
     N, C, H, W = x.shape
     gx = torch.empty_like(x); goff = torch.empty_like(offset); gm = torch.empty_like(mask)
-    ws, ws_ptr, nbytes = workspace(lib().vidar_dcn_col2im_workspace_bytes, N, H, W, Ho, Wo, kh, kw, like=x) \
-        if gather else (None, None, 0)
+    if deterministic.sync():          # grad_x: the fixed-point scatter, whatever `gather` and the variant say
+        nbytes = ctypes.c_int64(0)
+        check(lib().vidar_dcn_col2im_det_workspace_bytes(N, C, H, W, ctypes.addressof(nbytes)), "dcn_col2im")
+        nbytes = nbytes.value
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        ws_ptr = ptr(ws)
+    else:
+        ws, ws_ptr, nbytes = workspace(lib().vidar_dcn_col2im_workspace_bytes, N, H, W, Ho, Wo, kh, kw, like=x) \
+            if gather else (None, None, 0)
     with TIMER.span("dcn_col2im", 4 * (3 * x.numel() + 2 * offset.numel() + 2 * mask.numel() + grad_cols.numel())):
         check(lib().vidar_dcn_col2im_f32(ptr(grad_cols), ptr(x), ptr(offset), ptr(mask), ptr(gx), ptr(goff), ptr(gm),
                                          N, C, H, W, Ho, Wo, kh, kw, stride, pad, dil, ws_ptr, nbytes, stream_of(x)),

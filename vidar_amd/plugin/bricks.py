@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 from .registry import FEEDFORWARD_NETWORK, POSITIONAL_ENCODING
 from .. import gemm as _gemm
+from .. import deterministic
 
 
 def xavier_init(module, gain=1, bias=0, distribution="normal"):
@@ -83,6 +84,8 @@ class _LinearColsum(torch.autograd.Function):
                 gw, gb = _gemm.linear_grad_weight(g2, x2, _gemm.F32, with_bias=True)
                 return gx, gw, gb
             gw = (x2.t() @ g2).t()
+        if deterministic.enabled():                                    # a fixed order in place of the atomic column sum
+            return gx, gw, g2.sum(0)
         gb = torch.empty(g2.shape[1], dtype=torch.float32, device=g2.device)
         check(lib().vidar_colsum_f32(ptr(g2), ptr(gb), g2.shape[0], g2.shape[1], stream_of(g2)), "colsum")
         return gx, gw, gb
@@ -277,6 +280,7 @@ class _DropAddLayerNorm(torch.autograd.Function):
         gy = gy.contiguous()
         gx = torch.empty_like(s); gres = torch.empty_like(s)
         dgamma = torch.empty_like(gamma); dbeta = torch.empty_like(gamma)
+        deterministic.sync()                 # in the mode the partial rows of dgamma / dbeta are summed in a fixed order
         ws, ws_ptr, _ = workspace(lib().vidar_drop_add_ln_bwd_workspace_bytes, rows, like=s)
         check(lib().vidar_drop_add_ln_bwd_f32(ptr(gy), ptr(s), ptr(gamma), ptr(mean), ptr(rstd), ptr(gx), ptr(gres),
                                               ptr(dgamma), ptr(dbeta), ws_ptr, rows, 256, p, seed, stream_of(s)),

@@ -12,6 +12,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from ..._lib import lib, check, ptr, stream_of, workspace, TIMER
+from ... import deterministic
 
 K_SAMPLES = 512
 
@@ -60,6 +61,7 @@ class _RayCE(Function):
         step, K = ctx.cfg
         F_, R, Z, Y, X = _dims(sigma, gt)
         g = torch.empty_like(sigma)
+        deterministic.sync()
         ws, wsp, wsn = workspace(lib().vidar_ray_bwd_workspace_bytes, F_, Z, Y, X, like=sigma)
         with TIMER.span("ray_ce_bwd", 4 * (2 * sigma.numel() + R * 6)):
           check(lib().vidar_ray_ce_bwd_f32(ptr(sigma), ptr(origin), ptr(gt), ptr(tindex), ptr(lse),
@@ -91,6 +93,7 @@ class _RayGumbel(Function):
         step, K = ctx.cfg
         F_, R, Z, Y, X = _dims(sigma, pts)
         g = torch.empty_like(sigma)
+        deterministic.sync()
         ws, wsp, wsn = workspace(lib().vidar_ray_bwd_workspace_bytes, F_, Z, Y, X, like=sigma)
         with TIMER.span("ray_gumbel_bwd", 4 * (2 * sigma.numel() + R * 8)):
           check(lib().vidar_ray_gumbel_bwd_f32(ptr(sigma), ptr(origin), ptr(pts), ptr(tindex), ptr(aux),
@@ -124,6 +127,7 @@ class _RayDist(Function):
         step, K = ctx.cfg
         F_, R, Z, Y, X = _dims(sigma, gt)
         g = torch.empty_like(sigma)
+        deterministic.sync()
         ws, wsp, wsn = workspace(lib().vidar_ray_bwd_workspace_bytes, F_, Z, Y, X, like=sigma)
         with TIMER.span("ray_dist_bwd", 4 * (2 * sigma.numel() + R * 8)):
           check(lib().vidar_ray_dist_bwd_f32(ptr(sigma), ptr(origin), ptr(gt), ptr(tindex), ptr(aux),

@@ -8,6 +8,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from ..._lib import lib, check, ptr, stream_of, workspace, TIMER
+from ... import deterministic
 
 
 def msda_fwd_bytes(B, Nv, H, C, Nq, L, P):
@@ -39,7 +40,10 @@ BINNED_MIN_SAMPLES = 1 << 18
 
 
 def _bwd_workspace(value, B, Nv, H, Nq, L, P, binned):
-    """-> (tensor or None, pointer, byte count) of the binned scatter's scratch; (None, None, 0) = atomic scatter"""
+    """-> (tensor or None, pointer, byte count) of the binned scatter's scratch; (None, None, 0) = atomic scatter.
+    Deterministic mode: always the fixed-point accumulators of grad_value (the library sizes them), whatever `binned`."""
+    if deterministic.sync():
+        return workspace(lib().vidar_msda_bwd_workspace_bytes, B, Nv, H, Nq, L, P, like=value)
     if binned is None:
         binned = B * Nq * H * L * P >= BINNED_MIN_SAMPLES
     if not binned:

@@ -15,6 +15,7 @@ from torch.autograd.function import once_differentiable
 from ...bricks import Linear
 from ...registry import ATTENTION
 from ...._lib import lib, check, ptr, stream_of, workspace, TIMER
+from .... import deterministic
 
 _ACT = {"sigmoid": 0, "exp": 1}
 
@@ -46,6 +47,7 @@ class _PathProb(Function):
         grid_num, step, act = ctx.cfg
         bs, H, W, Z = occ.shape
         g = torch.empty_like(occ)
+        deterministic.sync()
         ws, wsp, wsn = workspace(lib().vidar_latent_render_bwd_workspace_bytes, bs, H, W, Z, 1, like=occ)
         with TIMER.span("lr_prob_bwd", 4 * occ.numel() * 3):
           check(lib().vidar_latent_render_prob_bwd_f32(ptr(occ), ptr(grad_prob.float().contiguous()),
@@ -85,6 +87,7 @@ class _RayGather(Function):
         bs, H, W, Z = prob.shape
         A = a.shape[-1]
         gp = torch.empty_like(prob); ga = torch.empty_like(a)
+        deterministic.sync()
         ws, wsp, wsn = workspace(lib().vidar_latent_render_bwd_workspace_bytes, bs, H, W, max(Z, A), 2, like=prob)
         grad_feat = grad_feat.float().contiguous()
         with TIMER.span("lr_gather_bwd", 4 * (3 * prob.numel() + 4 * a.numel())):

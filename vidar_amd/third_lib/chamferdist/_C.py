@@ -9,7 +9,10 @@ from __future__ import annotations
 
 import torch
 
+import ctypes
+
 from ..._lib import lib, check, ptr, stream_of, TIMER
+from ... import deterministic
 
 
 def knn_check_version(version: int, D: int, K: int) -> bool:
@@ -116,6 +119,8 @@ def knn_points_idx(p1, p2, lengths1, lengths2, K: int = 1, version: int = -1):
 
 def knn_points_backward(p1, p2, lengths1, lengths2, idxs, grad_dists):
     """-> (grad_p1 [N,P1,3], grad_p2 [N,P2,3])   (knn_cpu.cpp:64-106)"""
+    if idxs.shape[-1] != 1 or p1.shape[-1] != 3:
+        deterministic.require("knn generic backward")             # before anything touches the GPU
     p1, p2, l1, l2 = _prep(p1, p2, lengths1, lengths2)
     if idxs.shape[-1] != 1 or p1.shape[2] != 3:
         return _generic_knn_backward(p1, p2, l1.to(p1.device), l2.to(p1.device), idxs.contiguous(),
@@ -124,7 +129,13 @@ def knn_points_backward(p1, p2, lengths1, lengths2, idxs, grad_dists):
     P2 = p2.shape[1]
     g1 = torch.empty_like(p1)
     g2 = torch.empty_like(p2)
-    check(lib().vidar_knn1_d3_bwd(ptr(p1), ptr(p2), ptr(l1), ptr(l2), ptr(idxs.contiguous()),
-                                  ptr(grad_dists.contiguous().float()), ptr(g1), ptr(g2), N, P1, P2,
-                                  stream_of(p1)), "knn_points_backward")
+    ws, wsn = None, 0
+    if deterministic.sync():                # the fixed-point accumulators of grad_p2
+        nbytes = ctypes.c_int64(0)
+        check(lib().vidar_knn1_d3_bwd_workspace_bytes(N, P2, ctypes.addressof(nbytes)), "knn_points_backward")
+        wsn = nbytes.value
+        ws = torch.empty(wsn, dtype=torch.uint8, device=p1.device)
+    check(lib().vidar_knn1_d3_bwd_ws(ptr(p1), ptr(p2), ptr(l1), ptr(l2), ptr(idxs.contiguous()),
+                                     ptr(grad_dists.contiguous().float()), ptr(g1), ptr(g2), N, P1, P2,
+                                     ptr(ws), wsn, stream_of(p1)), "knn_points_backward")
     return g1, g2

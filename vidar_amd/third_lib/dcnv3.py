@@ -8,6 +8,7 @@ from __future__ import annotations
 import torch
 
 from .._lib import lib, check, ptr, stream_of, workspace
+from .. import deterministic
 from ._common import check_input
 
 
@@ -53,6 +54,7 @@ def dcnv3_forward(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, p
 def dcnv3_backward(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
                    group, group_channels, offset_scale, grad_output, im2col_step):
     """-> [grad_input, grad_offset, grad_mask]"""
+    deterministic.require("dcnv3 backward")
     (N, H, W, Ho, Wo), g = _geometry(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
                                      dilation_h, dilation_w, group, group_channels)
     check_input(grad_output, "grad_output")

@@ -5,6 +5,7 @@ from __future__ import annotations
 import torch
 
 from .._lib import lib, check, ptr, stream_of
+from .. import deterministic
 from ._common import check_input, ray_dims
 
 MAX_D = 1446  # dvr.cu:9
@@ -29,6 +30,7 @@ def render_forward(sigma, origin, points, tindex, grid, phase_name):
 
 def render(sigma, origin, points, tindex, loss_name):
     """-> [pred_dist, gt_dist, grad_sigma]"""
+    deterministic.require("dvr.render")
     for x, nm in ((sigma, "sigma"), (origin, "origin"), (points, "points"), (tindex, "tindex")):
         check_input(x, nm)
     if loss_name not in _LOSS:

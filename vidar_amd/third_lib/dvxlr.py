@@ -5,6 +5,7 @@ from __future__ import annotations
 import torch
 
 from .._lib import lib, check, ptr, stream_of, workspace
+from .. import deterministic
 from ._common import check_input, ray_dims
 
 MAX_D = 1026  # dvxlr.cu:10
@@ -27,6 +28,7 @@ def render(sigma, origin, points, tindex):
 def get_grad_sigma(elementwise_mult, indices, tindex, sigma_shape):
     """`sigma_shape` is a tensor shaped like sigma (the reference passes sigma itself and uses
     zeros_like, dvxlr.cu:138).  -> [grad_sigma]"""
+    deterministic.require("dvxlr.get_grad_sigma")
     for x, nm in ((elementwise_mult, "elementwise_mult"), (indices, "indices"), (tindex, "tindex")):
         check_input(x, nm)
     N, T, Z, Y, X = sigma_shape.shape

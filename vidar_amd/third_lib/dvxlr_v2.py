@@ -4,6 +4,7 @@ from __future__ import annotations
 import torch
 
 from .._lib import lib, check, ptr, stream_of, workspace
+from .. import deterministic
 from ._common import check_input, ray_dims
 
 MAX_D = 1026
@@ -30,6 +31,7 @@ def render_v2(sigma, origin, points, tindex, sigma_regul):
 
 def get_grad_sigma_v2(elementwise_mult, indices, tindex, sigma_shape, indicator, grad_ray_pred):
     """-> [grad_sigma, grad_sigma_regul]"""
+    deterministic.require("dvxlr_v2.get_grad_sigma")
     for x, nm in ((elementwise_mult, "elementwise_mult"), (indices, "indices"), (tindex, "tindex"),
                   (indicator, "indicator"), (grad_ray_pred, "grad_ray_pred")):
         check_input(x, nm)
