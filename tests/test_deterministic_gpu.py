@@ -291,10 +291,12 @@ def test_ray_backward(op, opt):
 # ---------------------------------------------------------------------------------------------
 # LatentRendering, 24 x 24 BEV
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("Z,A", [(16, 16), (4, 16)])
+@pytest.mark.parametrize("Z,A", [(16, 16), (4, 16), (1, 16), (32, 96)])
 def test_latent_render_backwards(Z, A):
     """both stages: three calls give the same bits; against oracle/latent_render.py at the 3e-4 / 3e-5 * scale of
-    tests/test_latent_render_groups_gpu.py"""
+    tests/test_latent_render_groups_gpu.py.  The four cases reach the four lane widths of the mode's kernels: 16 and 4
+    lanes per waypoint, (1, 16) one lane in stage 1 with J = 16, (32, 96) 64 lanes in both stages, two channel chunks and
+    a bin that straddles the chunk boundary (STRADDLE of tests/test_latent_render_groups_gpu.py)"""
     from vidar_amd.plugin.modules.ray_operations.latent_rendering import latent_render_gather, latent_render_path_prob
     from test_latent_render_groups_gpu import oracle_stages, close
     bs, Hh, W, G, step, act, J = 1, 24, 24, 256, 0.5, "sigmoid", A // Z

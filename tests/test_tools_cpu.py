@@ -66,3 +66,24 @@ def test_devcode_kernel_parser_and_resource_name_shortening():
     assert devcode.kernels(moved)["_ZN1a3fooEv"] == k["_ZN1a3fooEv"]
     assert kernel_resources.short("void (anonymous namespace)::dvr_render_kernel<256>(float const*, int)") == "dvr_render_kernel<256>"
     assert kernel_resources.short("(anonymous namespace)::msda_fwd_kernel(float const*, long const*)") == "msda_fwd_kernel"
+
+
+def test_devcode_lib_diff_maps_renamed_kernels():
+    """`lib-diff PARENT.so TREE.so old=new ...`: a parent kernel is compared with the tree kernel its name maps to -- `*`
+    repeats the matched text, the first matching pair wins, the ' #n' of a name several translation units carry stays,
+    and a name no pair matches is compared under itself"""
+    sys.path.insert(0, str(ROOT / "tools"))
+    rename = _load("devcode").rename
+    pairs = ["ray_bwd_measure_kernel<*>=ray_bwd_det_kernel<*, det::AccMeasure>",
+             "knn1_d3_bwd_fixed_kernel=knn1_d3_bwd_det_kernel<det::AccFixed>",
+             "dcn_col2im_kernel<*, *::Param>=dcn_col2im_kernel<*>",
+             "knn1_d3_bwd_fixed_kernel=never_reached"]
+    assert rename("ray_bwd_measure_kernel<true, false, SampleCoef>", pairs) == \
+        "ray_bwd_det_kernel<true, false, SampleCoef, det::AccMeasure>"
+    assert rename("knn1_d3_bwd_fixed_kernel", pairs) == "knn1_d3_bwd_det_kernel<det::AccFixed>"
+    assert rename("dcn_col2im_kernel<det::AccFixed, det::AccFixed::Param>", pairs) == "dcn_col2im_kernel<det::AccFixed>"
+    assert rename("dcn_col2im_kernel<det::AccAtomic>", pairs) == "dcn_col2im_kernel<det::AccAtomic>"
+    assert rename("ray_bwd_measure_kernel<true, true, CeCoef> #2", pairs) == \
+        "ray_bwd_det_kernel<true, true, CeCoef, det::AccMeasure> #2"
+    assert rename("det_finalise_kernel #3", pairs) == "det_finalise_kernel #3"
+    assert rename("ray_bwd_measure_kernel_x<1>", pairs) == "ray_bwd_measure_kernel_x<1>"

@@ -3,10 +3,16 @@
     python tools/devcode.py diff A.hip B.hip [-- extra hipcc flags]    # is the gfx950 code of two sources identical?
     python tools/devcode.py head-diff vidar_amd/csrc/dcn.hip [-- flags] # working tree vs the committed file (HEAD)
     python tools/devcode.py asm vidar_amd/csrc/dcn.hip KERNEL [-- flags] # disassembly of the kernels whose name contains KERNEL
+    python tools/devcode.py lib-diff PARENT.so TREE.so ['old<*>=new<*, T>' ...]  # two built libraries, kernel by kernel
+
+lib-diff is for changes that touch headers (head-diff compiles HEAD's source against the working tree's headers): build
+the parent commit elsewhere and compare the libraries.  Kernels are matched by their short demangled name; an
+`old=new` pair maps a renamed kernel, `*` standing for the same text on both sides.
 
 Used to prove that a refactor, or a compile-time variant that is off by default, leaves the shipped device code
 untouched (the round's rule: nothing that changes device code goes in without a GPU run), and to read what the
 compiler made of a loop (loads in flight, s_waitcnt placement).  Per-file flags are those of vidar_amd/build.py."""
+import difflib
 import re
 import subprocess
 import sys
@@ -16,7 +22,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tools"))
-from kernel_resources import LLVM, code_objects  # noqa: E402
+from kernel_resources import LLVM, code_objects, demangle, short  # noqa: E402
 from vidar_amd.build import COMMON, HIPCC, PER_FILE  # noqa: E402
 
 
@@ -46,6 +52,56 @@ def kernels(text):
     return body
 
 
+def lib_kernels(so, work):
+    """{short demangled name: instructions} of a built library; a name that several translation units carry (the
+    shells' own kernels) gets ' #2', ' #3' in the order of the code objects"""
+    work.mkdir()
+    body = {}
+    for co in code_objects(Path(so), work):
+        out = subprocess.run([str(LLVM / "llvm-objdump"), "-d", str(co)], text=True, capture_output=True, check=True).stdout
+        ks = kernels(out.splitlines())
+        for mangled, name in zip(ks, map(short, demangle(list(ks)))):
+            n, key = 1, name
+            while key in body:
+                n += 1
+                key = f"{name} #{n}"
+            body[key] = ks[mangled]
+    return body
+
+
+def rename(name, pairs):
+    """`name` under the first 'old=new' pair whose old side matches it ('*': any text, repeated in `new`), else itself"""
+    for pair in pairs:
+        old, new = pair.split("=", 1)
+        m = re.fullmatch("(.*)".join(map(re.escape, old.split("*"))) + r"( #\d+)?", name)
+        if m:
+            *stars, dup = m.groups()
+            parts = new.split("*")             # the i-th `*` of `new` is the i-th of `old`
+            return "".join(a + b for a, b in zip(parts, stars[:len(parts) - 1] + [""])) + (dup or "")
+    return name
+
+
+def lib_diff(parent, tree, pairs, work):
+    ka = {rename(k, pairs): (k, v) for k, v in lib_kernels(parent, work / "a").items()}
+    kb = lib_kernels(tree, work / "b")
+    same = 0
+    for k in sorted(set(ka) | set(kb)):
+        (old, a), b = ka.get(k, (k, None)), kb.get(k)
+        if a == b:
+            same += 1
+            continue
+        was = "" if old == k else f"  (was {old})"
+        if a is None or b is None:
+            print(f"only in {'tree' if a is None else 'parent'}: {k}")
+        else:
+            print(f"differs: {k}{was}  ({len(a)} -> {len(b)} instructions)")
+            for ln in difflib.unified_diff(a, b, "parent", "tree", n=0, lineterm=""):
+                if not ln.startswith(("---", "+++", "@@")):
+                    print("    " + ln)
+    print(f"identical: {same} of {len(set(ka) | set(kb))} kernels")
+    return 0 if same == len(set(ka) | set(kb)) else 1
+
+
 def main():
     argv = sys.argv[1:]
     extra = []
@@ -72,6 +128,8 @@ def main():
             for k in changed:
                 print(f"differs: {k[:100]}  ({len(ka.get(k, []))} -> {len(kb.get(k, []))} instructions)")
             return 1
+        if cmd == "lib-diff":
+            return lib_diff(argv[1], argv[2], argv[3:], work)
         if cmd == "asm":
             for k, body in kernels(disasm(argv[1], extra, work)).items():
                 if argv[2] in k:

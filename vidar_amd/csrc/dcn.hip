@@ -187,13 +187,12 @@ __global__ __launch_bounds__(256) void dcn_im2col_kernel(                       
 // grid: (ceil(P/256), ceil(C/kCG), N)
 constexpr int kCG = 8;
 // Acc: the accumulate policy of det_acc.h -- det::AccAtomic (fp32 atomics, the default mode), or the two passes of the
-// deterministic mode: det::AccMeasure (which keeps every thread to the end, for its flush), then det::AccFixed.
-// AccMeasure::flush holds a workgroup barrier: with the measure policy no thread may `return` before it.
-template <class Acc, class... AccParam>
+// deterministic mode: det::AccMeasure (which keeps every thread to the end: the contract at its flush), then det::AccFixed.
+template <class Acc>
 __global__ __launch_bounds__(256) void dcn_col2im_kernel(const float* __restrict__ grad_cols, const float* __restrict__ offset,
                                                          const float* __restrict__ mask, float* __restrict__ grad_x, Conv g,
-                                                         AccParam... acc_param) {
-  Acc acc(grad_x, acc_param...);
+                                                         typename Acc::Param param) {
+  Acc acc(grad_x, param);
   const int P = g.Ho * g.Wo, K = g.kh * g.kw;
   const int p = blockIdx.x * 256 + threadIdx.x;
   if constexpr (!Acc::kMeasureOnly) {
@@ -219,7 +218,7 @@ __global__ __launch_bounds__(256) void dcn_col2im_kernel(const float* __restrict
       for_corners(q, g.W, [&](int pix, float w) { acc.add(gim + (size_t)c * plane + pix, w * gv); });
     }
   }
-  if constexpr (Acc::kMeasureOnly) acc.flush();
+  acc.flush();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -588,13 +587,9 @@ int vidar_dcn_col2im_f32(const float* grad_cols, const float* x, const float* of
     const dim3 grid((P + 255) / 256, (C + kCG - 1) / kCG, N);
     const int rc = det_scatter(
         grad_x, nullptr, (size_t)N * C * HW, 0, (uint64_t)N * C * K * P * 4, false, workspace, workspace_bytes, s,
-        [&](uint32_t* word, uint32_t*) {
-          hipLaunchKernelGGL((dcn_col2im_kernel<det::AccMeasure, det::AccMeasure::Param>), grid, dim3(256), 0, s, grad_cols, offset, mask, grad_x, g,
-                             det::AccMeasure::Param{word});
-        },
-        [&](long long* acc, long long*, const uint32_t* word, const uint32_t*, int h) {
-          hipLaunchKernelGGL((dcn_col2im_kernel<det::AccFixed, det::AccFixed::Param>), grid, dim3(256), 0, s, grad_cols, offset, mask, grad_x, g,
-                             det::AccFixed::Param{acc, word, h});
+        [&](auto tag, auto param, auto) {
+          hipLaunchKernelGGL(dcn_col2im_kernel<decltype(tag)>, grid, dim3(256), 0, s, grad_cols, offset, mask, grad_x, g,
+                             param);
         });
     if (rc != 0) return rc;
   } else if (workspace) {
@@ -623,7 +618,7 @@ int vidar_dcn_col2im_f32(const float* grad_cols, const float* x, const float* of
     hipError_t e = hipMemsetAsync(grad_x, 0, sizeof(float) * (size_t)N * C * H * W, s);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(dcn_col2im_kernel<det::AccAtomic>, dim3((P + 255) / 256, (C + kCG - 1) / kCG, N), dim3(256), 0, s, grad_cols,
-                       offset, mask, grad_x, g);
+                       offset, mask, grad_x, g, det::AccAtomic::Param{});
   }
   hipLaunchKernelGGL(W >= 2 ? dcn_col2im_coord_kernel : dcn_col2im_coord_1col_kernel, dim3((P + 255) / 256, K, N), dim3(256), 0,
                      s, grad_cols, x, offset, mask, grad_offset, grad_mask, g);

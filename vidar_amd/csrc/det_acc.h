@@ -103,14 +103,17 @@ DET_HD float finalise(int64_t acc, uint32_t mbits, double delta) {
 namespace det {
 
 // The accumulate policies of a scatter body: `acc.add(p, v)` stands where the body adds v to the output element *p.
-// A policy is built from the float output the body addresses and its Param, which a kernel takes as an argument.
+// All three have one shape, so a kernel is written once, as a template over Acc that takes a `typename Acc::Param` per
+// gradient output:   Acc acc(out, param);  body(..., acc);  acc.flush();     (out: the float output the body addresses)
 
 // fp32 atomic, the default mode: exactly the instruction the bodies used before they took a policy
 struct AccAtomic {
   static constexpr bool kMeasureOnly = false;
+  struct Param {};
   __device__ __forceinline__ AccAtomic() {}
-  __device__ __forceinline__ explicit AccAtomic(const float*) {}
+  __device__ __forceinline__ explicit AccAtomic(const float*, Param = {}) {}
   __device__ __forceinline__ void add(float* p, float v) const { unsafeAtomicAdd(p, v); }
+  __device__ __forceinline__ void flush() const {}
 };
 
 // first pass of the deterministic mode: M = max |v| of everything the body would add
@@ -119,9 +122,13 @@ struct AccMeasure {
   struct Param { uint32_t* word; };
   uint32_t* word;
   uint32_t m = 0;
+  AccMeasure() = default;   // on the host a policy object is only a tag (det_scatter.h)
   __device__ __forceinline__ AccMeasure(const float*, Param p) : word(p.word) {}
   __device__ __forceinline__ void add(float*, float v) { m = max(m, abs_bits(v)); }
-  // every thread of the workgroup calls this once, after the body: per wave, then one atomicMax per workgroup
+  // Per wave, then one atomicMax per workgroup.  THE CONTRACT OF A BODY: flush holds workgroup barriers, so every thread
+  // of a workgroup that runs the body calls it, once per accumulator -- a thread that had returned from the kernel would
+  // deadlock the others.  A body is therefore an inlined function whose early `return`s leave the body, never the
+  // kernel; a kernel that carries its body inline keeps, under this policy, every thread on the way to the flush.
   __device__ __forceinline__ void flush() const {
     __shared__ uint32_t wave_max[16];
     uint32_t v = m;
@@ -147,11 +154,13 @@ struct AccFixed {
   const float* base;
   unsigned long long* acc;
   double inv_delta;
+  AccFixed() = default;
   __device__ __forceinline__ AccFixed(const float* base_, Param p)
       : base(base_), acc((unsigned long long*)p.acc), inv_delta(quantum(*p.word, p.h).inv) {}
   __device__ __forceinline__ void add(float* p, float v) const {
     atomicAdd(acc + (p - base), (unsigned long long)quantise(v, inv_delta));
   }
+  __device__ __forceinline__ void flush() const {}
 };
 
 }  // namespace det

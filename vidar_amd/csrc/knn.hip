@@ -103,9 +103,7 @@ __global__ __launch_bounds__(256) void knn1_finalize_kernel(
 
 // grad_p1[n,i,:] = 2 g (p1 - p2[idx]);  grad_p2[n,idx,:] -= the same (knn_cpu.cpp:93-101)
 // `acc`: the accumulate policy of det_acc.h for grad_p2; the measure pass of the deterministic mode leaves grad_p1 to
-// the fixed-point pass
-// (the measure kernel flushes behind this body with a workgroup barrier: a `return` here must stay a return from this
-// inlined function, never become one from a kernel)
+// the fixed-point pass (the `return`s are held to the contract at its AccMeasure::flush)
 template <class Acc>
 __device__ __forceinline__ void knn1_d3_bwd_body(
     const float* __restrict__ p1, const float* __restrict__ p2, const int64_t* __restrict__ len1,
@@ -139,18 +137,13 @@ __global__ __launch_bounds__(256) void knn1_d3_bwd_kernel(KNN_BWD_IN, float* __r
   det::AccAtomic acc;
   knn1_d3_bwd_body(p1, p2, len1, len2, idx, grad_dist, grad_p1, grad_p2, P1, P2, acc);
 }
-__global__ __launch_bounds__(256) void knn1_d3_bwd_measure_kernel(KNN_BWD_IN, float* __restrict__ grad_p2, int P1, int P2,
-                                                                  uint32_t* __restrict__ word) {
-  det::AccMeasure acc(nullptr, {word});
-  knn1_d3_bwd_body(p1, p2, len1, len2, idx, grad_dist, nullptr, grad_p2, P1, P2, acc);
-  acc.flush();
-}
-__global__ __launch_bounds__(256) void knn1_d3_bwd_fixed_kernel(KNN_BWD_IN, float* __restrict__ grad_p1,
-                                                                float* __restrict__ grad_p2, int P1, int P2,
-                                                                long long* __restrict__ acc64,
-                                                                const uint32_t* __restrict__ word, int h) {
-  det::AccFixed acc(grad_p2, {acc64, word, h});
+template <class Acc>
+__global__ __launch_bounds__(256) void knn1_d3_bwd_det_kernel(KNN_BWD_IN, float* __restrict__ grad_p1,
+                                                              float* __restrict__ grad_p2, int P1, int P2,
+                                                              typename Acc::Param param) {
+  Acc acc(grad_p2, param);
   knn1_d3_bwd_body(p1, p2, len1, len2, idx, grad_dist, grad_p1, grad_p2, P1, P2, acc);
+  acc.flush();
 }
 #undef KNN_BWD_IN
 
@@ -209,13 +202,9 @@ int vidar_knn1_d3_bwd_ws(const float* p1, const float* p2, const int64_t* length
     const dim3 grid((P1 + 255) / 256, N);
     return det_scatter(
         grad_p2, nullptr, (size_t)N * P2 * 3, 0, (uint64_t)N * P1 * 3, N == 0 || P1 == 0, workspace, workspace_bytes, s,
-        [&](uint32_t* word, uint32_t*) {
-          hipLaunchKernelGGL(knn1_d3_bwd_measure_kernel, grid, dim3(256), 0, s, p1, p2, lengths1, lengths2, idx,
-                             grad_dist2, grad_p2, P1, P2, word);
-        },
-        [&](long long* acc, long long*, const uint32_t* word, const uint32_t*, int h) {
-          hipLaunchKernelGGL(knn1_d3_bwd_fixed_kernel, grid, dim3(256), 0, s, p1, p2, lengths1, lengths2, idx,
-                             grad_dist2, grad_p1, grad_p2, P1, P2, acc, word, h);
+        [&](auto tag, auto param, auto) {
+          hipLaunchKernelGGL(knn1_d3_bwd_det_kernel<decltype(tag)>, grid, dim3(256), 0, s, p1, p2, lengths1, lengths2, idx,
+                             grad_dist2, grad_p1, grad_p2, P1, P2, param);
         });
   }
   if (N > 0 && P2 > 0) {

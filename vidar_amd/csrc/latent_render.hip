@@ -251,8 +251,8 @@ __device__ __forceinline__ void lr_prob_fwd(const float* __restrict__ occ, float
 
 // stage 1 backward: grad_prob [bs,Q,Z] -> grad_occ [bs,Q,Z] (pre-zeroed, atomics); lane = (waypoint slot, bin): one
 // atomic instruction covers the contiguous bytes of a tap corner (atomics cost per instruction x line, see msda.hip)
-// (Acc: the accumulate policy of det_acc.h.  The measure kernels flush behind the two backward bodies with a workgroup
-// barrier: their early `return`s leave the inlined body, and must never become returns from a kernel.)
+// (Acc: the accumulate policy of det_acc.h; the early `return`s of the two backward bodies are held to the contract at its
+// AccMeasure::flush.)
 template <int LPW, int ZC, class Acc>
 __device__ __forceinline__ void lr_prob_bwd(const float* __restrict__ occ, const float* __restrict__ grad_prob,
                                             float* __restrict__ grad_occ, int Q, int Zr, const Geo& g, int ncopies,
@@ -445,45 +445,27 @@ __global__ __launch_bounds__(kThreads) void lr_gather_bwd_any_kernel(
   lr_gather_bwd<LPW, 0>(prob, a, feat, msum, grad_feat, grad_prob, grad_a, Q, Z, A, g, ncopies, acc, acc);
 }
 
-// Deterministic mode (det_acc.h): the shape-generic bodies with the measure policy, then with the fixed-point policy,
+// Deterministic mode (det_acc.h): the shape-generic bodies under the measure policy, then under the fixed-point policy,
 // adding straight into the accumulator volumes (no private copies).
-template <int LPW>
-__global__ __launch_bounds__(kThreads) void lr_prob_bwd_measure_kernel(const float* __restrict__ occ,
-                                                                       const float* __restrict__ grad_prob,
-                                                                       float* __restrict__ grad_occ, int Q, int Z, Geo g,
-                                                                       uint32_t* __restrict__ word) {
-  det::AccMeasure acc(nullptr, {word});
+template <int LPW, class Acc>
+__global__ __launch_bounds__(kThreads) void lr_prob_bwd_det_kernel(const float* __restrict__ occ,
+                                                                   const float* __restrict__ grad_prob,
+                                                                   float* __restrict__ grad_occ, int Q, int Z, Geo g,
+                                                                   typename Acc::Param param) {
+  Acc acc(grad_occ, param);
   lr_prob_bwd<LPW, 0>(occ, grad_prob, grad_occ, Q, Z, g, 1, acc);
   acc.flush();
 }
-template <int LPW>
-__global__ __launch_bounds__(kThreads) void lr_prob_bwd_fixed_kernel(const float* __restrict__ occ,
-                                                                     const float* __restrict__ grad_prob,
-                                                                     float* __restrict__ grad_occ, int Q, int Z, Geo g,
-                                                                     long long* __restrict__ acc64,
-                                                                     const uint32_t* __restrict__ word, int h) {
-  det::AccFixed acc(grad_occ, {acc64, word, h});
-  lr_prob_bwd<LPW, 0>(occ, grad_prob, grad_occ, Q, Z, g, 1, acc);
-}
-template <int LPW>
-__global__ __launch_bounds__(kThreads) void lr_gather_bwd_measure_kernel(
+template <int LPW, class Acc>
+__global__ __launch_bounds__(kThreads) void lr_gather_bwd_det_kernel(
     const float* __restrict__ prob, const float* __restrict__ a, const float* __restrict__ feat,
     const float* __restrict__ msum, const float* __restrict__ grad_feat, float* __restrict__ grad_prob,
-    float* __restrict__ grad_a, int Q, int Z, int A, Geo g, uint32_t* __restrict__ word_prob,
-    uint32_t* __restrict__ word_a) {
-  det::AccMeasure acc_prob(nullptr, {word_prob}), acc_a(nullptr, {word_a});
+    float* __restrict__ grad_a, int Q, int Z, int A, Geo g, typename Acc::Param param_prob,
+    typename Acc::Param param_a) {
+  Acc acc_prob(grad_prob, param_prob), acc_a(grad_a, param_a);
   lr_gather_bwd<LPW, 0>(prob, a, feat, msum, grad_feat, grad_prob, grad_a, Q, Z, A, g, 1, acc_prob, acc_a);
   acc_prob.flush();
   acc_a.flush();
-}
-template <int LPW>
-__global__ __launch_bounds__(kThreads) void lr_gather_bwd_fixed_kernel(
-    const float* __restrict__ prob, const float* __restrict__ a, const float* __restrict__ feat,
-    const float* __restrict__ msum, const float* __restrict__ grad_feat, float* __restrict__ grad_prob,
-    float* __restrict__ grad_a, int Q, int Z, int A, Geo g, long long* __restrict__ acc64_prob,
-    long long* __restrict__ acc64_a, const uint32_t* __restrict__ word_prob, const uint32_t* __restrict__ word_a, int h) {
-  det::AccFixed acc_prob(grad_prob, {acc64_prob, word_prob, h}), acc_a(grad_a, {acc64_a, word_a, h});
-  lr_gather_bwd<LPW, 0>(prob, a, feat, msum, grad_feat, grad_prob, grad_a, Q, Z, A, g, 1, acc_prob, acc_a);
 }
 
 inline bool lr_bad(int bs, int H, int W, int Z, int G, int act) {
@@ -546,21 +528,6 @@ int gather_bwd(const float* prob, const float* a, const float* feat, const float
                size_t workspace_bytes, hipStream_t s) {
   const size_t nz = (size_t)bs * H * W * Z, na = (size_t)bs * H * W * A;
   const int Q = H * W;
-  if (det_mode())       // 4 corners of G waypoints per (cell, channel), for either map
-    return det_scatter(
-        grad_prob, grad_a, nz, na, (uint64_t)na * g.G * 4, false, workspace, workspace_bytes, s,
-        [&](uint32_t* wp, uint32_t* wa) {
-          with_lanes(A, [&](auto l) {
-            lr_launch(lr_gather_bwd_measure_kernel<decltype(l)::value>, bs, Q, s, prob, a, feat, msum, grad_feat,
-                      grad_prob, grad_a, Q, Z, A, g, wp, wa);
-          });
-        },
-        [&](long long* ap, long long* aa, const uint32_t* wp, const uint32_t* wa, int h) {
-          with_lanes(A, [&](auto l) {
-            lr_launch(lr_gather_bwd_fixed_kernel<decltype(l)::value>, bs, Q, s, prob, a, feat, msum, grad_feat,
-                      grad_prob, grad_a, Q, Z, A, g, ap, aa, wp, wa, h);
-          });
-        });
   const auto launch = [&](float* sp, float* sa, int ncopies) {
     if (Z == 16 && A == 16)
       lr_launch(lr_gather_bwd_kernel, bs, Q, s, prob, a, feat, msum, grad_feat, sp, sa, Q, g, ncopies);
@@ -570,9 +537,16 @@ int gather_bwd(const float* prob, const float* a, const float* feat, const float
                   g, ncopies);
       });
   };
+  const auto det_launch = [&](auto tag, auto param_prob, auto param_a) {
+    with_lanes(A, [&](auto l) {
+      lr_launch(lr_gather_bwd_det_kernel<decltype(l)::value, decltype(tag)>, bs, Q, s, prob, a, feat, msum, grad_feat,
+                grad_prob, grad_a, Q, Z, A, g, param_prob, param_a);
+    });
+  };
+  const uint64_t adds = (uint64_t)na * g.G * 4;   // 4 corners of G waypoints per (cell, channel), for either map
   if ((nz | na) % 4 == 0)
-    return scatter_with_copies<float4>(grad_prob, grad_a, nz, na, false, workspace, workspace_bytes, s, launch);
-  return scatter_with_copies<float>(grad_prob, grad_a, nz, na, false, workspace, workspace_bytes, s, launch);
+    return scatter_backward<float4>(grad_prob, grad_a, nz, na, adds, false, workspace, workspace_bytes, s, launch, det_launch);
+  return scatter_backward<float>(grad_prob, grad_a, nz, na, adds, false, workspace, workspace_bytes, s, launch, det_launch);
 }
 
 }  // namespace
@@ -581,8 +555,8 @@ extern "C" {
 
 size_t vidar_latent_render_bwd_workspace_bytes(int bs, int H, int W, int Z, int maps) {
   if (bs <= 0 || H <= 0 || W <= 0 || Z <= 0 || maps < 1 || maps > 2) return 0;
-  if (det_mode()) return det_workspace_bytes((size_t)bs * H * W * Z * maps, maps);
-  return scatter_workspace_bytes((size_t)bs * H * W * Z, maps);   // maps: 1 = prob_bwd (grad_occ), 2 = gather_bwd
+  // maps: 1 = prob_bwd (grad_occ), 2 = gather_bwd
+  return scatter_backward_workspace_bytes((size_t)bs * H * W * Z * maps, maps);
 }
 
 int vidar_latent_render_prob_fwd_f32(const float* occ, float* path_prob, int bs, int H, int W, int Z,
@@ -603,28 +577,20 @@ int vidar_latent_render_prob_bwd_f32(const float* occ, const float* grad_path_pr
   hipStream_t s = (hipStream_t)stream;
   Geo g{H, W, grid_num, step, act, 0.f};
   const size_t n = (size_t)bs * H * W * Z;
-  if (det_mode()) {     // 4 corners of the G waypoints and of the cell itself per (cell, bin)
-    const int Q = H * W;
-    return det_scatter(
-        grad_occ, nullptr, n, 0, (uint64_t)n * ((uint64_t)grid_num + 1) * 4, false, workspace, workspace_bytes, s,
-        [&](uint32_t* word, uint32_t*) {
-          with_lanes(Z, [&](auto l) {
-            lr_launch(lr_prob_bwd_measure_kernel<decltype(l)::value>, bs, Q, s, occ, grad_path_prob, grad_occ, Q, Z, g,
-                      word);
-          });
-        },
-        [&](long long* acc, long long*, const uint32_t* word, const uint32_t*, int h) {
-          with_lanes(Z, [&](auto l) {
-            lr_launch(lr_prob_bwd_fixed_kernel<decltype(l)::value>, bs, Q, s, occ, grad_path_prob, grad_occ, Q, Z, g,
-                      acc, word, h);
-          });
-        });
-  }
   const auto launch = [&](float* acc, float*, int ncopies) {
     launch_prob_bwd(occ, grad_path_prob, acc, bs, H, W, Z, g, ncopies, s);
   };
-  if (n % 4 == 0) return scatter_with_copies<float4>(grad_occ, nullptr, n, false, workspace, workspace_bytes, s, launch);
-  return scatter_with_copies<float>(grad_occ, nullptr, n, false, workspace, workspace_bytes, s, launch);
+  const auto det_launch = [&](auto tag, auto param, auto) {
+    with_lanes(Z, [&](auto l) {
+      lr_launch(lr_prob_bwd_det_kernel<decltype(l)::value, decltype(tag)>, bs, H * W, s, occ, grad_path_prob, grad_occ,
+                H * W, Z, g, param);
+    });
+  };
+  // 4 corners of the G waypoints and of the cell itself per (cell, bin)
+  const uint64_t adds = (uint64_t)n * ((uint64_t)grid_num + 1) * 4;
+  if (n % 4 == 0)
+    return scatter_backward<float4>(grad_occ, nullptr, n, 0, adds, false, workspace, workspace_bytes, s, launch, det_launch);
+  return scatter_backward<float>(grad_occ, nullptr, n, 0, adds, false, workspace, workspace_bytes, s, launch, det_launch);
 }
 
 int vidar_latent_render_gather_grouped_fwd_f32(const float* path_prob, const float* lora_a, float* feat, float* msum,

@@ -439,16 +439,18 @@ __device__ __forceinline__ float ld1(const float* __restrict__ p, int64_t o) {
 
 // Acc: the accumulate policy of det_acc.h for grad_value -- det::AccAtomic (fp32 atomics, the default mode), or the two
 // passes of the deterministic mode: det::AccMeasure, which ends before the store phase, then det::AccFixed.
-// AccMeasure::flush holds a workgroup barrier: every thread of a workgroup that runs the item loop must reach it, so no
-// early `return` may be added between the `blk >= nblocks` exit (whole workgroups) and the flush.
+// Between the `blk >= nblocks` exit (whole workgroups) and the flush no early `return` may be added: the contract at
+// AccMeasure::flush.
+// (AccParam: `typename Acc::Param`, as a pack that is empty for AccAtomic -- its empty trailing kernel argument changes the
+// default kernel's register allocation, profiles/kbench_scatter_policy.md)
 template <class Acc, class... AccParam>
 __global__ __launch_bounds__(kThreads) void msda_bwd_kernel(
     const float* __restrict__ value, const int64_t* __restrict__ shapes,
     const int64_t* __restrict__ lsi, const float* __restrict__ loc, const float* __restrict__ attw,
     const float* __restrict__ grad_out, float* __restrict__ grad_value,
     float* __restrict__ grad_loc, float* __restrict__ grad_w, int Nv, int H, int Nq, int L, int P,
-    int64_t n_items, int nblocks, Prep pr, GoMap gm, AccParam... acc_param) {
-  Acc acc(grad_value, acc_param...);
+    int64_t n_items, int nblocks, Prep pr, GoMap gm, AccParam... param) {
+  Acc acc(grad_value, param...);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ Levels lv;
   const int LP = L * P;
@@ -1100,16 +1102,10 @@ static int msda_bwd_launch(const float* value, const int64_t* spatial_shapes,
     return det_scatter(
         grad_value, nullptr, (size_t)B * Nv * H * C, 0, (uint64_t)n_items * L * P * 4 * kCh, n_items == 0, workspace,
         workspace_bytes, s,
-        [&](uint32_t* word, uint32_t*) {
-          hipLaunchKernelGGL((msda_bwd_kernel<det::AccMeasure, det::AccMeasure::Param>), dim3(grid), dim3(kThreads), lds, s, value, spatial_shapes,
-                             level_start_index, sampling_loc, attn_weight, grad_out, grad_value, grad_sampling_loc,
-                             grad_attn_weight, Nv, H, Nq, L, P, n_items, nblocks, pr, gm, det::AccMeasure::Param{word});
-        },
-        [&](long long* acc, long long*, const uint32_t* word, const uint32_t*, int h) {
-          hipLaunchKernelGGL((msda_bwd_kernel<det::AccFixed, det::AccFixed::Param>), dim3(grid), dim3(kThreads), lds, s, value, spatial_shapes,
-                             level_start_index, sampling_loc, attn_weight, grad_out, grad_value, grad_sampling_loc,
-                             grad_attn_weight, Nv, H, Nq, L, P, n_items, nblocks, pr, gm,
-                             det::AccFixed::Param{acc, word, h});
+        [&](auto tag, auto param, auto) {
+          hipLaunchKernelGGL((msda_bwd_kernel<decltype(tag), decltype(param)>), dim3(grid), dim3(kThreads), lds, s, value,
+                             spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, grad_value,
+                             grad_sampling_loc, grad_attn_weight, Nv, H, Nq, L, P, n_items, nblocks, pr, gm, param);
         });
   }
   if (vbytes) {

@@ -369,8 +369,7 @@ struct SampleCoef {   // saved: aux [R, 3]; d dist / d logit = pd * p * (ind - p
 // The adds go into private copies of the volume (scatter_copies.h).  (Leaving the 512-waypoint loop after the run of
 // live waypoints -- the waypoints inside the volume are ONE run of consecutive k, tests/test_ray_early_exit_cpu.py --
 // was measured too: no change, the masked passes cost almost nothing next to the atomics; removed.)
-// (Acc: the accumulate policy of det_acc.h.  The measure kernel flushes behind this body with a workgroup barrier: the
-// early `return`s below leave this inlined function, and must never become returns from a kernel.)
+// (Acc: the accumulate policy of det_acc.h; the early `return`s are held to the contract at its AccMeasure::flush.)
 template <bool K512, bool END_POINT, class Coef, class Acc>
 __device__ __forceinline__ void ray_bwd_body(
     const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
@@ -469,22 +468,15 @@ RAY_KERNEL ray_argmax_any_kernel(RAY_IN, float* __restrict__ pred_dist, float* _
   ray_argmax_body<false>(sigma, origin, pts, tindex, pred_dist, gt_dist, R, v, step, K);
 }
 
-// Deterministic mode (det_acc.h): the same body with the measure policy, then with the fixed-point policy, adding
+// Deterministic mode (det_acc.h): the same body under the measure policy, then under the fixed-point policy, adding
 // straight into the one accumulator volume (no private copies).  Both K forms produce the same contributions.
-template <bool K512, bool END_POINT, class Coef>
-RAY_KERNEL ray_bwd_measure_kernel(RAY_IN, const float* __restrict__ saved, const float* __restrict__ grad,
-                                  float* __restrict__ grad_sigma, int R, VolDims v, float step, int K,
-                                  uint32_t* __restrict__ word) {
-  det::AccMeasure acc(nullptr, {word});
+template <bool K512, bool END_POINT, class Coef, class Acc>
+RAY_KERNEL ray_bwd_det_kernel(RAY_IN, const float* __restrict__ saved, const float* __restrict__ grad,
+                              float* __restrict__ grad_sigma, int R, VolDims v, float step, int K,
+                              typename Acc::Param param) {
+  Acc acc(grad_sigma, param);
   ray_bwd_body<K512, END_POINT, Coef>(sigma, origin, pts, tindex, saved, grad, grad_sigma, R, v, step, 1, K, acc);
   acc.flush();
-}
-template <bool K512, bool END_POINT, class Coef>
-RAY_KERNEL ray_bwd_fixed_kernel(RAY_IN, const float* __restrict__ saved, const float* __restrict__ grad,
-                                float* __restrict__ grad_sigma, int R, VolDims v, float step, int K,
-                                long long* __restrict__ acc64, const uint32_t* __restrict__ word, int h) {
-  det::AccFixed acc(grad_sigma, {acc64, word, h});
-  ray_bwd_body<K512, END_POINT, Coef>(sigma, origin, pts, tindex, saved, grad, grad_sigma, R, v, step, 1, K, acc);
 }
 #undef RAY_KERNEL
 #undef RAY_IN
@@ -507,26 +499,22 @@ inline void rm_launch(K512Kernel k512, AnyKernel any, int R, int K, hipStream_t 
 }
 
 
-// a ray backward in the deterministic mode: at most 8 corners of K (+ the end point) entries per ray
-template <bool END_POINT, class Coef>
-int rm_bwd_det(const float* sigma, const float* origin, const float* pts, const float* tindex, const float* saved,
-               const float* grad, float* grad_sigma, int R, int K, VolDims v, float step, void* workspace,
-               size_t workspace_bytes, hipStream_t s) {
-  const int Kk = rm_k512(K) ? kK : K;
-  return det_scatter(
+// A ray backward: private copies of grad_sigma if the workspace allows (scatter_copies.h), or the deterministic mode's
+// two passes over at most 8 corners of K (+ the end point) entries per ray; R == 0 leaves zeros.
+// `default_launch(acc, nullptr, ncopies)` enqueues the op's own kernel.
+template <bool END_POINT, class Coef, class DefaultLaunch>
+int rm_bwd(const float* sigma, const float* origin, const float* pts, const float* tindex, const float* saved,
+           const float* grad, float* grad_sigma, int R, int K, VolDims v, float step, void* workspace,
+           size_t workspace_bytes, hipStream_t s, DefaultLaunch default_launch) {
+  const bool k512 = rm_k512(K);
+  return scatter_backward(
       grad_sigma, nullptr, rm_cells(v), 0, (uint64_t)R * ((uint64_t)K + END_POINT) * 8, R == 0, workspace,
-      workspace_bytes, s,
-      [&](uint32_t* word, uint32_t*) {
-        const auto k = rm_k512(K) ? ray_bwd_measure_kernel<true, END_POINT, Coef>
-                                  : ray_bwd_measure_kernel<false, END_POINT, Coef>;
+      workspace_bytes, s, default_launch,
+      [&](auto tag, auto param, auto) {
+        using Acc = decltype(tag);
+        const auto k = k512 ? ray_bwd_det_kernel<true, END_POINT, Coef, Acc> : ray_bwd_det_kernel<false, END_POINT, Coef, Acc>;
         hipLaunchKernelGGL(k, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, pts, tindex, saved, grad, grad_sigma, R,
-                           v, step, Kk, word);
-      },
-      [&](long long* acc, long long*, const uint32_t* word, const uint32_t*, int h) {
-        const auto k = rm_k512(K) ? ray_bwd_fixed_kernel<true, END_POINT, Coef>
-                                  : ray_bwd_fixed_kernel<false, END_POINT, Coef>;
-        hipLaunchKernelGGL(k, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, pts, tindex, saved, grad, grad_sigma, R,
-                           v, step, Kk, acc, word, h);
+                           v, step, k512 ? kK : K, param);
       });
 }
 
@@ -536,8 +524,7 @@ extern "C" {
 
 size_t vidar_ray_bwd_workspace_bytes(int F, int Z, int Y, int X) {
   if (F <= 0 || Z <= 0 || Y <= 0 || X <= 0) return 0;
-  if (det_mode()) return det_workspace_bytes(rm_cells(VolDims{F, Z, Y, X}));
-  return scatter_workspace_bytes(rm_cells(VolDims{F, Z, Y, X}), 1);
+  return scatter_backward_workspace_bytes(rm_cells(VolDims{F, Z, Y, X}), 1);
 }
 
 int vidar_ray_max_k(void) { return kKMax; }
@@ -558,7 +545,7 @@ int vidar_ray_ce_fwd_f32(const float* sigma, const float* origin, const float* g
   return vidar_last_error();
 }
 
-// the three backwards: private copies of grad_sigma if the workspace allows (scatter_copies.h); R == 0 leaves zeros
+// the three backwards: rm_bwd with the op's default kernels
 int vidar_ray_ce_bwd_f32(const float* sigma, const float* origin, const float* gt_pts,
                          const float* tindex, const float* lse, const float* grad_ce,
                          float* grad_sigma, int F, int R, int Z, int Y, int X, int K, float step,
@@ -567,11 +554,8 @@ int vidar_ray_ce_bwd_f32(const float* sigma, const float* origin, const float* g
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   VolDims v{F, Z, Y, X};
-  if (det_mode())
-    return rm_bwd_det<true, CeCoef>(sigma, origin, gt_pts, tindex, lse, grad_ce, grad_sigma, R, K, v, step, workspace,
-                                       workspace_bytes, s);
-  return scatter_with_copies(grad_sigma, nullptr, rm_cells(v), R == 0, workspace, workspace_bytes, s,
-                             [&](float* acc, float*, int ncopies) {
+  return rm_bwd<true, CeCoef>(sigma, origin, gt_pts, tindex, lse, grad_ce, grad_sigma, R, K, v, step, workspace,
+                              workspace_bytes, s, [&](float* acc, float*, int ncopies) {
     rm_launch(ray_ce_bwd_kernel, ray_ce_bwd_any_kernel, R, K, s, sigma, origin, gt_pts, tindex, lse, grad_ce, acc, R, v,
               step, ncopies);
   });
@@ -597,11 +581,8 @@ int vidar_ray_gumbel_bwd_f32(const float* sigma, const float* origin, const floa
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   VolDims v{F, Z, Y, X};
-  if (det_mode())
-    return rm_bwd_det<false, SampleCoef>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, K, v, step, workspace,
-                                       workspace_bytes, s);
-  return scatter_with_copies(grad_sigma, nullptr, rm_cells(v), R == 0, workspace, workspace_bytes, s,
-                             [&](float* acc, float*, int ncopies) {
+  return rm_bwd<false, SampleCoef>(sigma, origin, pts, tindex, aux, grad_dist, grad_sigma, R, K, v, step, workspace,
+                                   workspace_bytes, s, [&](float* acc, float*, int ncopies) {
     rm_launch(ray_gumbel_bwd_kernel, ray_gumbel_bwd_any_kernel, R, K, s, sigma, origin, pts, tindex, aux, grad_dist, acc,
               R, v, step, ncopies);
   });
@@ -627,11 +608,8 @@ int vidar_ray_dist_bwd_f32(const float* sigma, const float* origin, const float*
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   VolDims v{F, Z, Y, X};
-  if (det_mode())
-    return rm_bwd_det<true, SampleCoef>(sigma, origin, gt_pts, tindex, aux, grad_dist, grad_sigma, R, K, v, step, workspace,
-                                       workspace_bytes, s);
-  return scatter_with_copies(grad_sigma, nullptr, rm_cells(v), R == 0, workspace, workspace_bytes, s,
-                             [&](float* acc, float*, int ncopies) {
+  return rm_bwd<true, SampleCoef>(sigma, origin, gt_pts, tindex, aux, grad_dist, grad_sigma, R, K, v, step, workspace,
+                                  workspace_bytes, s, [&](float* acc, float*, int ncopies) {
     hipLaunchKernelGGL(ray_dist_bwd_kernel, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, gt_pts, tindex, aux,
                        grad_dist, acc, R, v, step, ncopies, K);
   });
