@@ -582,6 +582,34 @@ int vidar_det_loss_bwd_f32(const float* cls, const float* box, const int32_t* la
                            int B, int Q, int C, int total_g, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Matching step of the nuScenes detection metric, mAP / NDS (csrc/det_eval.hip, pair errors in csrc/det_eval_math.h).  The
+ * reference delegates the metric to the nuScenes devkit (datasets/nuscnes_eval.py:628-676 -> accumulate / calc_ap /
+ * calc_tp); the semantics here are recalled from the devkit, which is not part of the reference tree.
+ * Greedy, confidence-ordered nearest-centre matching for NT distance thresholds at once; one wave owns one (segment,
+ * threshold), segment = (sample, class) = sample * num_classes + class, so nothing is shared, nothing is atomic and the
+ * result is deterministic.
+ *   pred_box [P,9] f32 (x, y, z, three sizes, yaw, vx, vy), grouped by segment and, inside a segment, in PROCESSING ORDER
+ *   (score descending, equal scores with the later input index first); pred_attr [P] i32 attribute ids (NULL: none);
+ *   gt_box [G,9] / gt_attr [G] (id < 0: no attribute) grouped by segment; pred_start / gt_start [NS+1] i32 (device):
+ *   segment s owns rows start[s] .. start[s+1], start[0] = 0 and start[NS] = P resp. G.  dist_ths: NT <= 8 floats on the
+ *   HOST, in metres.
+ * A prediction takes the nearest row of its segment that is not taken yet -- squared centre distance on x, y in fp32,
+ * dx*dx + dy*dy without contraction, the lowest row on ties -- and matches iff that distance is < th*th, strictly; a
+ * prediction whose nearest untaken row is too far is a false positive even if a taken row is nearer.
+ *   match    [NT,P] i32: the matched row of gt_box, or -1        gt_match [NT,G] i32: the matched row of pred_box, or -1
+ *   err      [P,5]  f32, for threshold tp_index (-1: none, err may be NULL): trans_err, vel_err, scale_err, orient_err,
+ *            attr_err of the matched pair (period pi for segments of class barrier_class, 2 pi otherwise; NaN velocity
+ *            -> NaN vel_err; no ground-truth attribute -> NaN attr_err), NaN in all five for an unmatched row.
+ * All three are written completely.  Any segment size (up to 256 annotations of a segment stay in registers, more are
+ * streamed).  Empty extents (NS, NT, or P and G all zero) return 0 without a launch; negative sizes, NT > 8, a tp_index
+ * outside -1 .. NT-1, num_classes < 1 or a missing pointer return VIDAR_ERR_BAD_ARG before any HIP call.
+ * ------------------------------------------------------------------------- */
+int vidar_det_eval_match_f32(const float* pred_box, const int32_t* pred_attr, const int32_t* pred_start,
+                             const float* gt_box, const int32_t* gt_attr, const int32_t* gt_start, const float* dist_ths,
+                             int32_t* match, int32_t* gt_match, float* err, int P, int G, int NS, int NT, int tp_index,
+                             int num_classes, int barrier_class, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Device-side image pipeline (csrc/img_prep.hip, math in csrc/img_prep_math.h): raw uint8 HWC BGR frames -> the fp32
  * [n, 3, Hp, Wp] network input, with the bits of the host pipeline (PhotoMetricDistortionMultiViewImage, CropResizeFlipImage
  * = PIL crop / bicubic resize / flip, NormalizeMultiviewImage, RandomScaleImageMultiViewImage, PadMultiViewImage:

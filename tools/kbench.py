@@ -617,6 +617,72 @@ def bench_det(which):
         report("det_loss_tail", r.pop("loss_fwd_bwd_hip_ms"), **{k: round(v, 4) if isinstance(v, float) else v for k, v in r.items()})
 
 
+def det_eval_operands(seed, samples, preds_per_sample=300, mean_gt=30, device="cpu"):
+    """synthetic detections at validation-split scale: per sample ~mean_gt annotations (Poisson) anywhere within 50 m and
+    preds_per_sample predictions, 60 % of them scattered (sigma 1 m) around an annotation of their class, the rest
+    anywhere; distinct random scores.  -> (pred, gt) lists of per-sample dicts of tensors on `device`"""
+    rng = np.random.default_rng(seed)
+    pred, gt = [], []
+    for _ in range(samples):
+        G = int(rng.poisson(mean_gt))
+        gl = rng.integers(0, 10, G)
+        gb = np.concatenate([rng.uniform(-50, 50, (G, 2)), rng.uniform(-2, 0, (G, 1)), rng.uniform(0.4, 10, (G, 3)),
+                             rng.uniform(-np.pi, np.pi, (G, 1)), rng.normal(0, 2, (G, 2))], 1)
+        P = preds_per_sample
+        pl = rng.integers(0, 10, P)
+        pb = np.concatenate([rng.uniform(-50, 50, (P, 2)), rng.uniform(-2, 0, (P, 1)), rng.uniform(0.4, 10, (P, 3)),
+                             rng.uniform(-np.pi, np.pi, (P, 1)), rng.normal(0, 2, (P, 2))], 1)
+        if G:
+            near = rng.uniform(0, 1, P) < 0.6
+            src = rng.integers(0, G, P)
+            pb[near] = gb[src[near]] + rng.normal(0, 1.0, (int(near.sum()), 9)) * [1, 1, .1, .1, .1, .1, .1, .5, .5]
+            pl[near] = gl[src[near]]
+        pred.append(dict(boxes=pb.astype(np.float32), scores=rng.uniform(0.01, 1, P).astype(np.float32), labels=pl.astype(np.int64)))
+        gt.append(dict(boxes=gb.astype(np.float32), labels=gl.astype(np.int64), num_pts=rng.integers(0, 40, G).astype(np.int64)))
+    to = lambda side: [{k: torch.from_numpy(v).to(device) for k, v in s.items()} for s in side]
+    return (pred, gt) if device == "cpu" else (to(pred), to(gt))
+
+
+def bench_det_eval(which):
+    """the detection metric at validation-split scale on synthetic boxes (6019 samples x 300 predictions, ~30 annotations
+    each): the matcher launch alone by HIP events (median of 5 x 10), the torch plumbing in front of it and the whole
+    DetectionEval.evaluate by wall clock with a device drain (median of 5).  Next to it the loops of the test suite's
+    restatement of the devkit (tests/det_eval_cases.py -- only timed here, nothing is compared) on the host for a 1/50
+    slice of the samples, and that time scaled by 50."""
+    import time
+    from vidar_amd.det_evaluate import DetectionEval
+    dev = torch.device("cuda", 0)
+    S = 6019
+    host_pred, host_gt = det_eval_operands(0, S)
+    to = lambda side: [{k: torch.from_numpy(v).to(dev) for k, v in s.items()} for s in side]
+    pred, gt = to(host_pred), to(host_gt)
+    ev = DetectionEval()
+
+    def wall(fn, n=5):
+        ts = []
+        for _ in range(n + 1):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(); ts.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ts[1:]))
+    k = ev.prepare(pred, gt)
+    P, G = k["pred_box"].shape[0], k["gt_box"].shape[0]
+    kernel_ms = float(np.median([timeit(lambda: ev.run_matcher(k), warm=2, it=10) for _ in range(5)]))
+    prepare_ms, evaluate_ms = wall(lambda: ev.prepare(pred, gt)), wall(lambda: ev.evaluate(pred, gt))
+    result = ev.evaluate(pred, gt)
+    sys.path.insert(0, str(ROOT / "tests"))
+    import det_eval_cases                                       # the host loops, for the time only
+    n = S // 50
+    t0 = time.perf_counter()
+    host = det_eval_cases.evaluate(dict(pred=host_pred[:n], gt=host_gt[:n]))
+    host_s = time.perf_counter() - t0
+    report("det_eval", kernel_ms, 36 * (P + G) + 4 * (4 * P + 4 * G) + 20 * P, samples=S, predictions=P, annotations=G,
+           segments=k["NS"], thresholds=4, prepare_wall_ms=round(prepare_ms, 2), evaluate_wall_ms=round(evaluate_ms, 2),
+           mAP=round(result["mean_ap"], 4), NDS=round(result["nd_score"], 4), host_loops_samples=n,
+           host_loops_s=round(host_s, 2), host_loops_scaled_to_split_s=round(host_s * S / n, 1),
+           host_slice_mAP=round(host["mean_ap"], 4))
+
+
 def bench_deterministic(which):
     """every backward the deterministic mode covers (vidar_amd/deterministic.py) at its BASELINE shape, in both modes:
     mode=0 the fp32-atomic default (with the strategy the step takes), mode=1 the measure + fixed-point (or fixed-order)

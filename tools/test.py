@@ -12,7 +12,11 @@ reference's summary (chamfer distance, L1 and AbsRel ray errors per future frame
 
 A detection recipe (finetune/...) runs the BEVFormer detector in video mode instead: the frames of each synthetic sequence go
 through forward_test one by one (the previous frame's BEV carried along, reset at a scene change) and the decoded boxes of
-every frame are printed -- count, best scores, labels.  NDS / mAP need the nuScenes devkit and are not computed."""
+every frame are printed -- count, best scores, labels.  The boxes of the current (last) frame of every sequence are then
+scored against the sequence's synthetic ground truth (num_pts = 1, no attributes, so attr_err is 1) with
+vidar_amd.det_evaluate -- nuScenes mAP, the five true-positive errors and NDS, computed on the device without the
+devkit: rank 0 gathers the boxes of all ranks, prints the devkit's closing table and writes the result under "metrics"
+in --out, next to the per-frame records ("frames")."""
 import argparse
 import json
 import os
@@ -117,22 +121,26 @@ def main(argv=None):
 
 def video_detection(model, meta, args, dev, rank, world):
     import copy
+    from vidar_amd import evaluate as E
+    from vidar_amd.det_evaluate import DetectionEval, format_summary
     from vidar_amd.synthetic import fpn_features, make_sample
     if args.ann_file or args.submission:
         raise SystemExit("detection recipes evaluate synthetic sequences only (no box annotations in the data reader, no "
                          "submission format); --ann-file / --submission do not apply")
     model.eval()
     T_img = meta["queue_length"] + 1
-    records = []
+    part = []                                        # per sequence: its frame records, the last frame's boxes, its ground truth
     for i in range(rank, args.samples, world):
-        metas = make_sample(50000 + i, queue_length=meta["queue_length"], future_frames=0, rays_per_frame=1,
-                            num_cams=meta["num_cams"], img_hw=meta["img_hw"])[0]
+        metas, _, gt_boxes, gt_labels = make_sample(50000 + i, queue_length=meta["queue_length"], future_frames=0,
+                                                    rays_per_frame=1, num_cams=meta["num_cams"], img_hw=meta["img_hw"],
+                                                    with_boxes=True)
         if args.no_backbone:
             feats = fpn_features(i, T_img, num_cams=meta["num_cams"], shapes=meta["fpn_shapes"], device=dev)
         else:
             g = torch.Generator().manual_seed(50000 + i)
             img = torch.randn(1, T_img, meta["num_cams"], 3, *meta["img_hw"], generator=g).to(dev)
         pose = np.zeros(4)
+        records = []
         for t in range(T_img):
             m = copy.deepcopy(metas[t])
             pose += [*m["can_bus"][:3], m["can_bus"][-1]]               # forward_test expects absolute ego poses
@@ -144,9 +152,25 @@ def video_detection(model, meta, args, dev, rank, world):
                                 top_labels=[int(v) for v in box["labels_3d"][:3]],
                                 top_box=[round(float(v), 3) for v in box["boxes_3d"].tensor[0]] if len(box["boxes_3d"]) else None))
             print(json.dumps(records[-1]), flush=True)
-    if args.out:                                     # this rank's frames
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(json.dumps(records, indent=1))
+        part.append(dict(records=records, boxes=box["boxes_3d"].tensor.numpy(), scores=box["scores_3d"].numpy(),
+                         labels=box["labels_3d"].numpy(), gt_boxes=gt_boxes, gt_labels=gt_labels))
+    part = E.collect_results(part, args.samples)     # rank 0: every sequence, in dataset order
+    if rank == 0:
+        def dv(a, dtype):
+            return torch.as_tensor(a, dtype=dtype, device=dev)
+        pred = [dict(boxes=dv(s["boxes"], torch.float32).reshape(-1, 9), scores=dv(s["scores"], torch.float32),
+                     labels=dv(s["labels"], torch.int64)) for s in part]
+        gt = [dict(boxes=dv(s["gt_boxes"], torch.float32).reshape(-1, 9), labels=dv(s["gt_labels"], torch.int64),
+                   num_pts=torch.ones(len(s["gt_labels"]), dtype=torch.int64, device=dev)) for s in part]
+        metrics = DetectionEval(meta.get("class_names") or DetectionEval().class_names).evaluate(pred, gt)
+        print(format_summary(metrics), flush=True)
+        if args.out:
+            Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.out).write_text(json.dumps(dict(frames=[r for s in part for r in s["records"]], metrics=metrics),
+                                                 indent=1))
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        torch.distributed.barrier()
+        torch.distributed.destroy_process_group()
 
 
 if __name__ == "__main__":
