@@ -610,6 +610,38 @@ int vidar_det_eval_match_f32(const float* pred_box, const int32_t* pred_attr, co
                              int num_classes, int barrier_class, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Ray errors of the forecasting metric, L1 / AbsRel along the ground-truth rays (csrc/ray_eval.hip, per-ray arithmetic
+ * in csrc/ray_eval_math.h): projects/mmdet3d_plugin/bevformer/utils/eval_utils.py:185-225 for S segments at once, a
+ * segment being one (sample, frame) pair.  All arithmetic is fp64 on the fp32 inputs widened first, as the reference's
+ * numpy is, and the nearest neighbour is searched in fp64, as chamferdist does for the reference's fp64 input.
+ *   pred [P,3] f32 / gt [G,3] f32, grouped by segment; pred_start / gt_start [S+1] i32 on the DEVICE: segment s owns rows
+ *   start[s] .. start[s+1], start[0] = 0 and start[S] = P resp. G (values outside are clamped); origin [S,3] f32.
+ *   max_gt: a HOST bound on the longest ground-truth segment; it sizes the grid, tiles = ceil(max_gt / 256), and rays
+ *   of a segment beyond it are not scored.
+ * With (theta, phi, d) = (atan2(x, y), atan2(z, y), sqrt(x*x + y*y + z*z)) of a point minus its segment's origin: a
+ * prediction is kept iff d_hat > 1e-2, a ground-truth ray is counted iff d > 1e-2; every counted ray takes the kept
+ * prediction of its segment with the smallest dtheta*dtheta + dphi*dphi (strict <: the lowest row wins ties; no
+ * wrap-around), moves it onto its own ray, interp = origin + d_hat * unit(gt - origin), and is charged
+ * |clamp(gt) - clamp(interp)| (L1) and that over the clamped ray length (AbsRel), unless clamp(gt) misses the volume or
+ * is <= 0.01 long.  clamp cuts a ray to PC_RANGE = [-70, -70, -4.5, 70, 70, 4.5] (the metric's own range).
+ *   partial [S,tiles,3] f64: (sum of L1, sum of AbsRel, counted rays) of each tile of 256 rays, summed in a fixed order;
+ *            tiles beyond a segment hold zeros.  Their sum over tiles is the segment's (sum L1, sum AbsRel, count):
+ *            l1_error = sum L1 / count.  A segment with counted rays and no kept prediction gives NaN sums (the
+ *            reference raises there).  No atomics: equal inputs give equal bits.
+ *   nn_idx  [G]   i32, may be NULL: the chosen row RELATIVE to the segment's start, -1 for an uncounted ray or a segment
+ *            without a kept prediction
+ *   ray_err [G,2] f64, may be NULL: the ray's two terms, 0 where it contributes nothing
+ *   interp  [G,3] f64, may be NULL: the interpolated point, NaN where nn_idx is -1
+ * The f64 buffers are passed as void*.  workspace: vidar_ray_eval_workspace_bytes(P) bytes of device scratch, 8-byte
+ * aligned.  S == 0 or G == 0 return 0 without a launch; negative sizes, max_gt == 0 with rays to score, a missing
+ * required pointer or a short workspace return VIDAR_ERR_BAD_ARG before any HIP call.
+ * ------------------------------------------------------------------------- */
+int vidar_ray_eval_workspace_bytes(int P, int64_t* bytes);
+int vidar_ray_eval_f64(const float* pred, const int32_t* pred_start, const float* gt, const int32_t* gt_start,
+                       const float* origin, void* partial, int32_t* nn_idx, void* ray_err, void* interp, int P, int G,
+                       int S, int max_gt, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Device-side image pipeline (csrc/img_prep.hip, math in csrc/img_prep_math.h): raw uint8 HWC BGR frames -> the fp32
  * [n, 3, Hp, Wp] network input, with the bits of the host pipeline (PhotoMetricDistortionMultiViewImage, CropResizeFlipImage
  * = PIL crop / bicubic resize / flip, NormalizeMultiviewImage, RandomScaleImageMultiViewImage, PadMultiViewImage:

@@ -683,6 +683,91 @@ def bench_det_eval(which):
            host_slice_mAP=round(host["mean_ap"], 4))
 
 
+def ray_eval_operands(seed, bs=1, frames=4, rays=30000, device="cpu"):
+    """rays of a forecast as dense_heads get_rendered_rays hands them over: [bs, frames * rays] rendered points of the
+    predicted and of the ground-truth depth (the prediction on the ground-truth ray, 0.7 .. 1.3 of its depth), the frame
+    of every ray (2 % take no part: -1) and one origin per (sample, frame)"""
+    rng = np.random.default_rng(seed)
+    N = frames * rays
+    origin = rng.uniform(-2, 2, (bs, frames, 3)) * [1, 1, 0.2]
+    frame = np.tile(np.repeat(np.arange(frames), rays), (bs, 1))
+    o = np.take_along_axis(origin, frame[..., None].repeat(3, -1), 1)
+    end = rng.uniform(-90, 90, (bs, N, 3)) * [1, 1, 0.06]
+    unit = (end - o) / np.linalg.norm(end - o, axis=-1, keepdims=True)
+    depth = np.linalg.norm(end - o, axis=-1, keepdims=True)
+    gt, pred = o + unit * depth, o + unit * depth * rng.uniform(0.7, 1.3, (bs, N, 1))
+    frame = np.where(rng.uniform(size=(bs, N)) < 0.02, -1, frame)
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(device)
+    return t(pred, torch.float32), t(gt, torch.float32), t(frame, torch.int64), t(origin, torch.float32)
+
+
+def bench_ray_eval(which):
+    """the forecasting metric tail of ViDAR.forward_test for 4 segments x 30 000 rays (one sample, current + 3 future
+    frames): the host path as forward_test runs it (boolean selection, chamfer through the KNN kernel, numpy ray errors
+    with the nearest neighbour on the KNN kernel, a float() per figure) against eval_utils.forecast_metrics_device plus
+    its one host read, both by wall clock with a device drain (median of 5 after one warm-up); and the two ray-error
+    launches alone by HIP events.  Writes profiles/kbench_ray_eval.md."""
+    import time
+    from vidar_amd.plugin.utils import e2e_predictor_utils as E
+    from vidar_amd.plugin.utils import eval_utils as U
+    dev = torch.device("cuda", 0)
+    pc_range = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
+    bs, F_, R = 1, 4, 30000
+    pred, gt, frame, origin = ray_eval_operands(0, bs, F_, R, dev)
+
+    def host_tail():
+        out = np.zeros((bs, F_, 3))
+        for b in range(bs):
+            for f in range(F_):
+                m = frame[b] == f
+                p, g = pred[b][m], gt[b][m]
+                cd = float(E.compute_chamfer_distance_inner(p, g, pc_range))
+                l1, ar = U.compute_ray_errors(p.cpu().numpy().astype(np.float64), g.cpu().numpy().astype(np.float64),
+                                              origin[b, f].cpu().numpy().astype(np.float64), p.device)
+                out[b, f] = cd, float(l1), float(ar)
+        return out
+
+    def device_tail():
+        return U.forecast_metrics_device(pred, gt, frame, origin, pc_range).cpu().numpy()[..., :3]
+
+    def wall(fn, n=5):
+        ts = []
+        for _ in range(n + 1):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(); ts.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ts[1:])), ts[1:]
+    device_ms, device_all = wall(device_tail)
+    host_ms, host_all = wall(host_tail)
+    h, d = host_tail(), device_tail()
+    # the ray-error launches alone, on operands already in segment order
+    S, N = bs * F_, frame.shape[1]
+    key, order = torch.sort(torch.where(frame >= 0, frame, torch.full_like(frame, S)).reshape(-1), stable=True)
+    start = torch.searchsorted(key, torch.arange(S + 1, device=dev)).to(torch.int32)
+    sp, sg, so = pred.reshape(-1, 3)[order], gt.reshape(-1, 3)[order], origin.reshape(S, 3)
+    kernel_ms = float(np.median([timeit(lambda: U.ray_errors_device(sp, start, sg, start, so, N), warm=2, it=10)
+                                 for _ in range(5)]))
+    row = dict(segments=S, rays_per_segment=R, ray_error_launches_ms=round(kernel_ms, 3), device_tail_wall_ms=round(device_ms, 2),
+               host_tail_wall_ms=round(host_ms, 2), host_over_device=round(host_ms / device_ms, 1),
+               device_runs_ms=[round(t, 2) for t in device_all], host_runs_ms=[round(t, 2) for t in host_all],
+               max_rel_diff_chamfer=float(np.abs(d[..., 0] / h[..., 0] - 1).max()),
+               max_rel_diff_l1=float(np.abs(d[..., 1] / h[..., 1] - 1).max()),
+               max_rel_diff_absrel=float(np.abs(d[..., 2] / h[..., 2] - 1).max()))
+    report("ray_eval", kernel_ms, **row)
+    (ROOT / "profiles" / "kbench_ray_eval.md").write_text(
+        "# Forecasting metric tail on an MI355X: `python tools/kbench.py ray_eval`\n\n"
+        f"{S} segments (1 sample, current + 3 future frames) x {R} rays, 2 % of the rays dropped; the prediction sits on the\n"
+        "ground-truth ray at 0.7 .. 1.3 of its depth (`tools/kbench.py::ray_eval_operands`).  Wall clock with a device drain,\n"
+        "median of 5 after one warm-up; the two ray-error launches alone by HIP events (median of 5 x 10).\n\n"
+        "```\n" + json.dumps({"device": torch.cuda.get_device_name(0)}) + "\n" + json.dumps(dict(op="ray_eval", **row)) + "\n```\n\n"
+        "| what | result |\n|---|---|\n"
+        f"| host tail of `ViDAR.forward_test` (selection, chamfer, numpy ray errors, a `float()` per figure) | {host_ms:.2f} ms |\n"
+        f"| device tail (`eval_utils.forecast_metrics_device` and its one host read) | {device_ms:.2f} ms |\n"
+        f"| `vidar_ray_eval_f64` (projection + match launches) alone | {kernel_ms:.3f} ms |\n\n"
+        "The `max_rel_diff_*` figures compare the two tails' results on these operands; they are printed to show that both\n"
+        "sides computed the same thing (the host path searches the nearest neighbour in fp32, the device path in fp64).\n")
+
+
 def bench_deterministic(which):
     """every backward the deterministic mode covers (vidar_amd/deterministic.py) at its BASELINE shape, in both modes:
     mode=0 the fp32-atomic default (with the strategy the step takes), mode=1 the measure + fixed-point (or fixed-order)

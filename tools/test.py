@@ -49,7 +49,13 @@ def main(argv=None):
                          "reference's data.test does")
     ap.add_argument("--device-images", action="store_true",
                     help="with --ann-file: ship uint8 frames and run the image pipeline in HIP kernels (same tensor)")
+    ap.add_argument("--device-metrics", action="store_true",
+                    help="score the forecast on the device: one chamfer call, one ray-error call and one host read per "
+                         "batch instead of a dozen round trips per (sample, frame) (same figures; off by default)")
     args = ap.parse_args(argv)
+    if args.device_metrics:
+        from vidar_amd.plugin.utils import eval_utils
+        eval_utils.set_device_metrics(True)
 
     from vidar_amd import checkpoint as C
     from vidar_amd import evaluate as E

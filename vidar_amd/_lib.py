@@ -126,6 +126,8 @@ _ABI = {
     "vidar_det_loss_fwd_f32": "i 8p 2f 5i p z p",
     "vidar_det_loss_bwd_f32": "i 10p 2f 5i p",
     "vidar_det_eval_match_f32": "i 10p 7i p",
+    "vidar_ray_eval_workspace_bytes": "i i p",
+    "vidar_ray_eval_f64": "i 9p 4i p z p",
     "vidar_img_photometric_u8": "i 3p 3i p",
     "vidar_img_photometric_f32": "i 3p 3i p",
     "vidar_img_resample_workspace_bytes": "z 3i",

@@ -131,6 +131,22 @@ class ViDARHeadTemplate(nn.Module):
             pcds.append(per_frame)
         return pcds
 
+    def get_rendered_rays(self, origin, points, tindex, gt_dist, pred_dist, pc_range):
+        """get_rendered_pcds without the boolean selections (no host sync): every ray keeps its place, the selection
+        is the per-ray frame id.  -> dict(pred_pts [bs,N,3], gt_pts [bs,N,3] -- the rendered points of the predicted
+        and of the ground-truth depth --, frame [bs,N] int64: the frame a ray belongs to, -1 for a ray that
+        get_rendered_pcds would drop (its points may hold anything, NaN included), origin [bs,F,3])."""
+        bs, num_frames, _ = origin.shape
+        valid = (tindex >= 0) & (tindex < num_frames) & (gt_dist > 0.)
+        if self.eval_within_grid:
+            valid = valid & e2e_predictor_utils.get_inside_mask(points, pc_range)
+        frame = torch.where(valid, tindex, torch.full_like(tindex, -1.0)).long()
+        o = torch.gather(origin, 1, frame.clamp(min=0).unsqueeze(-1).expand(-1, -1, 3))
+        r = points - o
+        rn = r / torch.sqrt((r ** 2).sum(-1, keepdim=True))
+        return dict(pred_pts=o + rn * pred_dist.unsqueeze(-1), gt_pts=o + rn * gt_dist.unsqueeze(-1), frame=frame,
+                    origin=origin)
+
 
 @HEADS.register_module()
 class ViDARHeadBase(ViDARHeadTemplate):
@@ -236,8 +252,9 @@ class ViDARHeadBase(ViDARHeadTemplate):
 
     @torch.no_grad()
     def get_point_cloud_prediction(self, pred_dict, gt_points, start_idx, tgt_bev_h, tgt_bev_w,
-                                   tgt_pc_range, img_metas=None, batched_origin_points=None):
-        """arg-max decode (:663-752) -> dict(pred_pcds, gt_pcds, origin)."""
+                                   tgt_pc_range, img_metas=None, batched_origin_points=None, as_rays=False):
+        """arg-max decode (:663-752) -> dict(pred_pcds, gt_pcds, origin); as_rays: the dict of get_rendered_rays
+        instead (the device metrics' input: nothing is selected on the host)."""
         bev_preds = pred_dict["next_bev_preds"].float()
         valid_frames = pred_dict["valid_frames"]
         F_, inter_num, bs, token_num, Z = bev_preds.shape
@@ -254,6 +271,8 @@ class ViDARHeadBase(ViDARHeadTemplate):
         scale = (tgt_pc_range[3] - tgt_pc_range[0]) / W
         pred = torch.stack(pred) * scale
         gt = torch.stack(gt) * scale
+        if as_rays:
+            return self.get_rendered_rays(origin_pts, gt_xyz, tindex, gt, pred, tgt_pc_range)
         return dict(
             pred_pcds=self.get_rendered_pcds(origin_pts, gt_xyz, tindex, gt, pred, tgt_pc_range),
             gt_pcds=self.get_rendered_pcds(origin_pts, gt_xyz, tindex, gt, gt, tgt_pc_range),

@@ -119,7 +119,7 @@ class ViDARHeadV1(ViDARHeadBase):
         return keys
 
     def get_point_cloud_prediction(self, pred_dict, gt_points, start_idx, tgt_bev_h, tgt_bev_w,
-                                   tgt_pc_range, img_metas=None, batched_origin_points=None):
+                                   tgt_pc_range, img_metas=None, batched_origin_points=None, as_rays=False):
         pred_dict = dict(pred_dict)
         pred_dict["next_bev_preds"] = pred_dict["next_bev_preds"][:, :, self.pred_history_frame_num, ...].contiguous()
         valid_frames = np.array(pred_dict["valid_frames"])
@@ -129,4 +129,4 @@ class ViDARHeadV1(ViDARHeadBase):
         return super().get_point_cloud_prediction(
             pred_dict=pred_dict, gt_points=gt, start_idx=start_idx, tgt_bev_h=tgt_bev_h,
             tgt_bev_w=tgt_bev_w, tgt_pc_range=tgt_pc_range, img_metas=img_metas,
-            batched_origin_points=origin)
+            batched_origin_points=origin, as_rays=as_rays)

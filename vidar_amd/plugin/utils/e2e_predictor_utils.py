@@ -130,3 +130,17 @@ def compute_chamfer_distance_inner(pred_pcd, gt_pcd, pc_range):
     if pm.sum() == 0 or gm.sum() == 0:
         return 0.0
     return compute_chamfer_distance(pred_pcd[pm], gt_pcd[gm])
+
+
+def chamfer_inner_device(pred, pred_valid, gt, gt_valid, pc_range):
+    """compute_chamfer_distance_inner for S segments at once without a host read: pred [S,N,3] / gt [S,M,3] with bool
+    masks [S,N] / [S,M] of the rows that belong to the segment (the rest is padding of any value).  Both clouds are
+    cropped to pc_range through the masks of the training chamfer loss, whose counts stay on the device.
+    -> [S]: (sum_src / n_src + sum_dst / n_dst) / 2, and 0 where either crop is empty."""
+    from ..losses import chamfer_distance as masked_chamfer
+    pm = pred_valid & get_inside_mask(pred, pc_range)
+    gm = gt_valid & get_inside_mask(gt, pc_range)
+    fwd, bwd, _, _ = masked_chamfer(pred, gt, src_valid=pm, dst_valid=gm, reduction="none")
+    n_src, n_dst = pm.sum(1), gm.sum(1)
+    cd = (fwd.sum(1) / n_src.clamp(min=1) + bwd.sum(1) / n_dst.clamp(min=1)) / 2.0
+    return torch.where((n_src == 0) | (n_dst == 0), torch.zeros_like(cd), cd)

@@ -128,3 +128,96 @@ def compute_ray_errors(pred_pcd, gt_pcd, origin, device, return_interpolated_pcd
     valid = dc > 0.01
     eucl = np.sqrt(((g_pcd[valid] - p_pcd[valid]) ** 2).sum(1))
     return eucl.sum() / count, (eucl / dc[valid]).sum() / count
+
+
+# ---- the same metric on the device (csrc/ray_eval.hip) ------------------------------------------------------------------
+_device_metrics = None      # None: follow VIDAR_DEVICE_METRICS
+
+
+def set_device_metrics(on):
+    """Route ViDAR.forward_test's metric tail (chamfer distance, l1_error, absrel_error) through the device path: one
+    chamfer call, one ray-error call and one host read per batch.  Off by default; `None` returns the decision to the
+    environment variable VIDAR_DEVICE_METRICS.  -> the previous setting"""
+    global _device_metrics
+    prev, _device_metrics = _device_metrics, (None if on is None else bool(on))
+    return prev
+
+
+def device_metrics():
+    if _device_metrics is not None:
+        return _device_metrics
+    import os
+    return os.environ.get("VIDAR_DEVICE_METRICS", "0") not in ("", "0")
+
+
+def ray_errors_device(pred, pred_start, gt, gt_start, origin, max_gt, *, return_per_ray=False):
+    """compute_ray_errors for S segments -- (sample, frame) pairs -- in one call, on the device, in fp64.
+    pred [P,3] / gt [G,3] f32 grouped by segment, pred_start / gt_start [S+1] i32 DEVICE tensors (segment s owns rows
+    start[s] .. start[s+1]; they are never read back), origin [S,3] f32, max_gt: a host bound on the longest ground-truth
+    segment (it sizes the grid only; a cloud's padded length will do).
+    -> [S,3] f64 device tensor (sum of L1, sum of AbsRel, count): l1_error = [:, 0] / [:, 2], absrel_error = [:, 1] / [:, 2].
+    A segment with counted rays and no kept prediction gives NaN (compute_ray_errors raises there).
+    return_per_ray: -> (sums, dict(nn_idx [G] i32 -- the row relative to the segment's start, -1 for an uncounted ray --,
+    ray_err [G,2] f64, interp [G,3] f64 -- compute_ray_errors(..., return_interpolated_pcd=True), NaN where nn_idx is -1 --,
+    partial [S,tiles,3] f64)).  There is no CPU path."""
+    from ..._lib import check, lib, ptr, stream_of
+    tensors = (pred, pred_start, gt, gt_start, origin)
+    if not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
+        raise RuntimeError("ray_errors_device needs device tensors: the product has no CPU path "
+                           "(compute_ray_errors is the host form)")
+    if any(t.device != pred.device for t in tensors):
+        raise RuntimeError("ray_errors_device: all tensors must live on one device")
+    S = origin.shape[0]
+    if (pred.dtype, gt.dtype, origin.dtype) != (torch.float32,) * 3 or (pred_start.dtype, gt_start.dtype) != (torch.int32,) * 2:
+        raise TypeError("ray_errors_device: pred / gt / origin must be float32 and the start tables int32")
+    if pred.dim() != 2 or pred.shape[1] != 3 or gt.dim() != 2 or gt.shape[1] != 3 or tuple(origin.shape) != (S, 3) \
+            or tuple(pred_start.shape) != (S + 1,) or tuple(gt_start.shape) != (S + 1,):
+        raise ValueError("ray_errors_device: pred [P,3], gt [G,3], origin [S,3], pred_start / gt_start [S+1]")
+    pred, gt, origin = pred.contiguous(), gt.contiguous(), origin.contiguous()
+    pred_start, gt_start = pred_start.contiguous(), gt_start.contiguous()
+    P, G, max_gt = pred.shape[0], gt.shape[0], int(max_gt)
+    tiles = (max(max_gt, 0) + 255) // 256
+    f64 = dict(dtype=torch.float64, device=pred.device)
+    partial = torch.zeros(S, tiles, 3, **f64) if S == 0 or G == 0 else torch.empty(S, tiles, 3, **f64)
+    per_ray = None
+    if return_per_ray:
+        per_ray = dict(nn_idx=torch.full((G,), -1, dtype=torch.int32, device=pred.device),
+                       ray_err=torch.zeros(G, 2, **f64), interp=torch.full((G, 3), float("nan"), **f64), partial=partial)
+    import ctypes
+    nbytes = ctypes.c_int64(0)
+    check(lib().vidar_ray_eval_workspace_bytes(P, ctypes.addressof(nbytes)), "vidar_ray_eval_workspace_bytes")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=pred.device) if nbytes.value else None
+    check(lib().vidar_ray_eval_f64(ptr(pred), ptr(pred_start), ptr(gt), ptr(gt_start), ptr(origin), ptr(partial),
+                                   ptr(per_ray and per_ray["nn_idx"]), ptr(per_ray and per_ray["ray_err"]),
+                                   ptr(per_ray and per_ray["interp"]), P, G, S, max_gt, ptr(ws), nbytes.value,
+                                   stream_of(pred)), "vidar_ray_eval_f64")
+    sums = partial.sum(1)
+    return (sums, per_ray) if return_per_ray else sums
+
+
+def forecast_metrics_device(pred, gt, frame, origin, pc_range):
+    """The forecasting metrics of every (sample, frame) segment without a host read.
+    pred / gt [bs,N,3]: the rendered points of the predicted and of the ground-truth depth of every ray, frame [bs,N] int64:
+    the frame a ray belongs to, -1 for a ray that takes no part (its points may hold anything), origin [bs,F,3]
+    (dense_heads get_rendered_rays), pc_range: the model's range, which crops the chamfer distance.
+    -> [bs,F,4] f64 device tensor: chamfer distance (compute_chamfer_distance_inner), l1_error, absrel_error
+    (compute_ray_errors) and the number of rays of the segment."""
+    from . import e2e_predictor_utils
+    bs, N = frame.shape
+    F_ = origin.shape[1]
+    S = bs * F_
+    # chamfer distance inside the model's range: segment (b, f) sees cloud b under the mask frame == f
+    in_seg = (frame.unsqueeze(1) == torch.arange(F_, device=frame.device).view(1, F_, 1)).reshape(S, N)
+    expand = lambda x: x.unsqueeze(1).expand(bs, F_, N, 3).reshape(S, N, 3)
+    cd = e2e_predictor_utils.chamfer_inner_device(expand(pred), in_seg, expand(gt), in_seg, pc_range)
+    # ray errors: rows sorted by segment (the rays that take no part last, owned by no segment), starts found on the device
+    key = torch.where(frame >= 0, torch.arange(bs, device=frame.device).view(bs, 1) * F_ + frame,
+                      torch.full_like(frame, S)).reshape(-1)
+    key, order = torch.sort(key, stable=True)
+    start = torch.searchsorted(key, torch.arange(S + 1, device=key.device)).to(torch.int32)
+    take = lambda x: x.reshape(-1, 3).float()[order]
+    sums = ray_errors_device(take(pred), start, take(gt), start, origin.reshape(S, 3).float(), N)
+    rows = (start[1:] - start[:-1]).to(sums.dtype)
+    # a segment without rays scores 0 (the host path skips it); rays but no counted one is 0 / 0, as on the host
+    err = torch.where(rows.unsqueeze(1) > 0, sums[:, :2] / sums[:, 2:3], torch.zeros_like(sums[:, :2]))
+    return torch.cat([cd.to(sums.dtype).unsqueeze(1), err, rows.unsqueeze(1)], 1).view(bs, F_, 4)
