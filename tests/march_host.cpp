@@ -1,8 +1,8 @@
-// TEST INFRASTRUCTURE.  Compiles vidar_amd/csrc/dvr_march.h (the traversal + integrator every
-// dvr / dvxlr kernel instantiates per lane) with g++ and drives it with scalar loops that mirror
-// what the kernels of dvr_family.hip do around it, so that the traversal logic can be compared
-// with the oracle on a machine without a GPU (tests/test_march_host_cpu.py).  Never used by the
-// product.
+// TEST INFRASTRUCTURE.  Compiles vidar_amd/csrc/dvr_march.h (the traversal, the integrator and the
+// per-ray bodies every dvr / dvxlr kernel instantiates per lane) with g++ and calls those bodies
+// ray by ray, so that the very text the kernels run can be compared with the oracle on a machine
+// without a GPU (tests/test_march_host_cpu.py).  Only the dvxlr finish pass, a wave scan on the
+// device, is mirrored here as a scalar loop.  Never used by the product.
 #include <stdint.h>
 #include <string.h>
 #include <vector>
@@ -30,65 +30,39 @@ int host_dvr_render_forward(const float* sigma, const float* origin, const float
                             const float* tindex, float* pred_dist, float* gt_dist, int N, int M,
                             int T, int TO, int Z, int Y, int X, int train_phase) {
   Vol g{T, TO, Z, Y, X};
-  const size_t vol = (size_t)Z * Y * X;
   for (int n = 0; n < N; ++n)
-    for (int c = 0; c < M; ++c) {
-      float pred = -1.f, gt = -1.f;
-      const RayIn r = load_ray(origin, points, tindex, n, c, M, g);
-      if (r.valid) {
-        NoEmit ne;
-        Integrator<kRounded, kDvrMaxD, NoEmit> a(sigma + ((size_t)n * T + r.ts) * vol, Y, X, ne);
-        const double len = HostTraversal().run<kRounded>(r, g, a);
-        if (a.k > 0) {
-          pred = (float)(a.d0 + a.S);
-          gt = (float)(train_phase ? fmin(len, a.dprev) : len);
-        }
-      }
-      pred_dist[(size_t)n * M + c] = pred;
-      gt_dist[(size_t)n * M + c] = gt;
-    }
+    for (int c = 0; c < M; ++c)
+      seq_forward_ray(sigma, origin, points, tindex, pred_dist, gt_dist, n, c, M, g, train_phase, HostTraversal());
   return 0;
 }
 
-struct HostGrad {
-  double* grad;
-  double S_total, dl_dd;
-  void commit(int, int vid, double, double dt, double P, double) {
-    grad[vid] += (double)(float)(dl_dd * (dt * (P - S_total)));
-  }
+// the kernels add the fp32-rounded term with an fp32 atomic; the harness keeps the sum in double
+struct AddToDouble {
+  void operator()(double* slot, float v) const { *slot += (double)v; }
 };
 
 int host_dvr_render(const float* sigma, const float* origin, const float* points,
                     const float* tindex, float* pred_dist, float* gt_dist, double* grad_sigma,
                     int N, int M, int T, int TO, int Z, int Y, int X, int loss_type) {
   Vol g{T, TO, Z, Y, X};
-  const size_t vol = (size_t)Z * Y * X;
-  memset(grad_sigma, 0, sizeof(double) * N * T * vol);
+  memset(grad_sigma, 0, sizeof(double) * N * T * Z * Y * X);
   for (int n = 0; n < N; ++n)
-    for (int c = 0; c < M; ++c) {
-      float pred = -1.f, gt = -1.f;
-      const RayIn r = load_ray(origin, points, tindex, n, c, M, g);
-      if (r.valid) {
-        const size_t slice = ((size_t)n * T + r.ts) * vol;
-        NoEmit ne;
-        Integrator<kClassic, kDvrMaxD, NoEmit> a(sigma + slice, Y, X, ne);
-        const double len = HostTraversal().run<kClassic>(r, g, a);
-        if (a.k > 0) {
-          const double exp_d = a.d0 + a.S, gt_d = fmin(len, a.dprev);
-          pred = (float)exp_d; gt = (float)gt_d;
-          double dl = 1.0;
-          if (loss_type == 0) dl = (exp_d >= gt_d) ? 1.0 : -1.0;
-          else if (loss_type == 1) dl = exp_d - gt_d;
-          else if (loss_type == 2) dl = (exp_d >= gt_d) ? (1.0 / gt_d) : -(1.0 / gt_d);
-          HostGrad hg{grad_sigma + slice, a.S, dl};
-          Integrator<kClassic, kDvrMaxD, HostGrad> b(sigma + slice, Y, X, hg);
-          HostTraversal().run<kClassic>(r, g, b);
-        }
-      }
-      pred_dist[(size_t)n * M + c] = pred;
-      gt_dist[(size_t)n * M + c] = gt;
-    }
+    for (int c = 0; c < M; ++c)
+      seq_render_ray<AddToDouble>(sigma, origin, points, tindex, pred_dist, gt_dist, grad_sigma, n, c, M, g,
+                                  loss_type, HostTraversal());
   return 0;
+}
+
+// time_slice() and what load_ray() makes of it (it also needs origin[n][ti]); one ray with time index t
+int host_time_slice(float t, int T, int TO, int* ts, int* ray_valid, int* ray_ts) {
+  long ti;
+  const bool ok = time_slice(t, T, ti, *ts);
+  std::vector<float> origin(3 * (size_t)TO, 0.f);
+  const float point[3] = {1.f, 1.f, 1.f};
+  const RayIn r = load_ray(origin.data(), point, &t, 0, 0, 1, Vol{T, TO, 1, 1, 1});
+  *ray_valid = r.valid ? 1 : 0;
+  *ray_ts = r.ts;
+  return ok ? 1 : 0;
 }
 
 // dvxlr.render / render_v2: launch 1 is the shared dvxlr_march_ray(); launch 2 (the finish pass of
@@ -118,8 +92,10 @@ int host_dvxlr_render(const float* sigma, const float* sigma_regul, const float*
       decode_stash(idr[2], cnt, ks, nan_tail);
       const float* reg = nullptr;
       if (sigma_regul && cnt > 0) {
-        const long ti = (long)tindex[row];
-        reg = sigma_regul + ((size_t)n * T + (T == 1 ? 0 : ti)) * vol;
+        long ti;
+        int ts;
+        time_slice(tindex[row], T, ti, ts);      // a ray with samples has a valid time index
+        reg = sigma_regul + ((size_t)n * T + ts) * vol;
       }
       double R = nan_tail ? (double)NAN : 0.0;
       float w_above = 0.f;                     // W_k lives in sample k+1's slot

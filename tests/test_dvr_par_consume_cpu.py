@@ -1,9 +1,12 @@
-"""CPU: the lane-level logic of the step-parallel dvr kernels' consume phase (csrc/dvr_par_kernels.h `par_consume`:
+"""CPU: the lane-level logic of the step-parallel dvr kernels' consume phase (csrc/dvr_par_kernels.h
+`par_consume<kEmitNone | kEmitRows, V2>`, the merged-mode consumer of dvxlr / dvxlr_v2:
 chunks of 63 new steps with the still-open sample of the previous chunk on lane 0, run detection, the rewind
 recurrence of a run of equal voxels iterated to its fixed point, commit flags -> sample index by prefix count, the
 previous committed sample by "highest set bit below me", wave-uniform carries) restated with numpy over 64 "lanes" and
 checked against the sequential integrator semantics of csrc/dvr_march.h (`Integrator::sample` / `commit`: dvxlr.cu:366-377
 merge, W_{k-1} = T_{k-1} (d_k - d_{k-1}), P_k, k_surface) -- sample lists, dt bit for bit, sums to fp64 round-off.
+The kernel's `par_consume` is merged mode only (the modes without the merge run `par_consume_plain`); the restatement
+keeps its `merged=False` reading of the same chunk logic as a second case.
 What must be kept in step with the kernel: the chunk geometry (lane 0 = carry, lanes 1..63 = steps sb .. sb+62), the
 commit rule (last valid lane commits only when the ray ends in this chunk; otherwise a lane commits iff its successor
 is not the same voxel), `__shfl_down` past the last lane returning the lane's own value.  The GPU tests remain the

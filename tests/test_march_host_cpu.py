@@ -127,6 +127,33 @@ def test_dvr_render(host, name, make, loss):
     np.testing.assert_allclose(grad, ref[2], rtol=1e-4, atol=1e-4 * scale)
 
 
+NAN = float("nan")
+# t, T, TO -> time_slice (ok, ts) and load_ray (valid, ts).  A static sigma (T == 1) serves every time index from
+# slice 0 (init / get_grad_sigma call with TO = T = 1 and any ti >= 0); load_ray also needs origin[n][ti]: ti < TO.
+TIME_SLICE = [
+    (-1.0, 2, 2, (False, 0), (False, 0)),
+    (-1.0, 1, 3, (False, 0), (False, 0)),
+    (NAN, 2, 2, (False, 0), (False, 0)),
+    (NAN, 1, 3, (False, 0), (False, 0)),
+    (0.0, 2, 2, (True, 0), (True, 0)),
+    (1.0, 2, 2, (True, 1), (True, 1)),
+    (2.0, 2, 2, (False, 0), (False, 0)),
+    (2.0, 1, 3, (True, 0), (True, 0)),
+    (3.0, 1, 3, (True, 0), (False, 0)),
+    (2.9, 1, 3, (True, 0), (True, 0)),
+]
+
+
+@pytest.mark.parametrize("t,T,TO,want,ray", TIME_SLICE, ids=[f"t{r[0]}-T{r[1]}-TO{r[2]}" for r in TIME_SLICE])
+def test_time_slice(host, t, T, TO, want, ray):
+    """csrc/dvr_march.h time_slice(), the one statement of "which sigma slice does this ray read" behind load_ray, init,
+    get_grad_sigma and the v2 finish pass."""
+    ts, valid, ray_ts = ctypes.c_int(-7), ctypes.c_int(-7), ctypes.c_int(-7)
+    ok = host.host_time_slice(ctypes.c_float(t), T, TO, ctypes.byref(ts), ctypes.byref(valid), ctypes.byref(ray_ts))
+    assert (bool(ok), ts.value) == want
+    assert (bool(valid.value), ray_ts.value) == ray
+
+
 def test_step_parallel_traversal_full_size_frame(tmp_path_factory):
     """One BASELINE frame (30 000 rays from the grid centre) and a jittered-origin multi-frame set through the
     step-parallel traversal (csrc/dvr_par.h) on the host: voxel lists and gt_dist bit-equal to the oracle, and the

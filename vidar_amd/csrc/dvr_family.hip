@@ -100,6 +100,14 @@ inline bool step_parallel(int N, int M, const Vol& g, long auto_max_rays) {
 // wins at every measured size; the one-launch dvxlr.render / render_v2 (padding streamed next to the march) win up to
 // ~90 000 rays and tie with the three-launch lane-per-ray form above (box-to-box spread larger than the difference)
 constexpr long kParAutoForward = 24576, kParAutoRender = 1L << 40, kParAutoDvxlr = 98304;
+// Lane-per-ray launch of `ranked` = kernel<kSortBlock> (256-ray workgroups that rank their rays, pick_ray) once the
+// launch has more than g_sort_min_waves waves, else of `plain` = kernel<kWave>.
+template <class Kernel, class... Args>
+inline void launch_lane_per_ray(Kernel* ranked, Kernel* plain, int N, int M, hipStream_t s_, Args... args) {
+  const bool sort = sort_rays(N, M);
+  const int block = sort ? kSortBlock : kWave;
+  hipLaunchKernelGGL(sort ? ranked : plain, dim3((M + block - 1) / block, N), dim3(block), 0, s_, args...);
+}
 template <int KIND>
 inline void launch_par(const float* sigma, const float* sigma_regul, const float* origin, const float* points,
                        const float* tindex, float* pred_dist, float* gt_dist, float* dd_dsigma, float* indices,
@@ -141,7 +149,7 @@ __global__ __launch_bounds__(kBlock) void dvr_render_kernel(
   const int n = blockIdx.y;
   const int c = pick_ray<kBlock>(origin, points, tindex, n, M, g);
   if (c >= M) return;
-  seq_render_ray(sigma, origin, points, tindex, pred_dist, gt_dist, grad_sigma, n, c, M, g, loss_type);
+  seq_render_ray<AtomicAddF32>(sigma, origin, points, tindex, pred_dist, gt_dist, grad_sigma, n, c, M, g, loss_type);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -191,8 +199,10 @@ __global__ __launch_bounds__(256) void dvxlr_finish_kernel(
     bool nt0;
     decode_stash(idr[2], cnt0, ks0, nt0);
     if (cnt0 > 0) {
-      const long ti = (long)tindex[row];          // a ray with samples has a valid time index
-      reg = sigma_regul + ((size_t)n * g.T + (g.T == 1 ? 0 : ti)) * ((size_t)g.Z * g.Y * g.X);
+      long ti;
+      int ts;
+      time_slice(tindex[row], g.T, ti, ts);       // a ray with samples has a valid time index
+      reg = sigma_regul + ((size_t)n * g.T + ts) * ((size_t)g.Z * g.Y * g.X);
     }
   }
   const int cnt = dvxlr_finish_row<V2>(reg, ddr, idr, rpr, inr, g, lane);
@@ -236,11 +246,9 @@ __global__ __launch_bounds__(256) void dvxlr_scatter_kernel(
   // rays of one frame share their first voxels (the sensor origin): private copies, scatter_copies.h
   grad_sigma += scatter_copy_of_block(ncopies) * copy_stride;
   if (V2) grad_regul += scatter_copy_of_block(ncopies) * copy_stride;
-  const float t = tindex[(size_t)n * M + c];
-  if (t < 0.f || t != t) return;
-  const long ti = (long)t;
-  if (!(g.T == 1 || ti < g.T)) return;
-  const int ts = (g.T == 1) ? 0 : (int)ti;
+  long ti;
+  int ts;
+  if (!time_slice(tindex[(size_t)n * M + c], g.T, ti, ts)) return;
   const size_t vol = (size_t)g.Z * g.Y * g.X;
   float* gs = grad_sigma + ((size_t)n * g.T + ts) * vol;
   float* gr = V2 ? grad_regul + ((size_t)n * g.T + ts) * vol : nullptr;
@@ -274,18 +282,15 @@ __global__ __launch_bounds__(256) void dvr_init_kernel(const float* __restrict__
   const int n = blockIdx.y;
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= M) return;
-  const float t = tindex[(size_t)n * M + c];
-  if (t < 0.f || t != t) return;
-  const long ti = (long)t;
-  if (!(g.T == 1 || ti < g.T)) return;
-  const int ts = (g.T == 1) ? 0 : (int)ti;
+  long ti;
+  int ts;
+  if (!time_slice(tindex[(size_t)n * M + c], g.T, ti, ts)) return;
   const float* p = points + ((size_t)n * M + c) * 3;
   const int vx = (int)p[0], vy = (int)p[1], vz = (int)p[2];
   if (0 <= vx && vx < g.X && 0 <= vy && vy < g.Y && 0 <= vz && vz < g.Z)
     occupancy[((((size_t)n * g.T + ts) * g.Z + vz) * g.Y + vy) * g.X + vx] = 1.f;
 }
 
-inline int hip_ret() { return vidar_last_error(); }
 inline bool bad_dims(int N, int M, int T, int Z, int Y, int X) {
   return N < 0 || M < 0 || T <= 0 || Z <= 0 || Y <= 0 || X <= 0;
 }
@@ -327,17 +332,6 @@ int vidar_dvr_set_traversal(int mode) {
   g_traversal = (mode < -1 || mode > 1) ? -1 : mode;
   return prev;
 }
-#ifdef VIDAR_PAR_TIMING
-int vidar_dbg_par_cycles(unsigned long long* out, int reset) {
-  hipDeviceSynchronize();
-  hipMemcpyFromSymbol(out, HIP_SYMBOL(vidar_march::g_par_cycles), sizeof(unsigned long long) * 8);
-  if (reset) {
-    unsigned long long z[8] = {0};
-    hipMemcpyToSymbol(HIP_SYMBOL(vidar_march::g_par_cycles), z, sizeof(z));
-  }
-  return 0;
-}
-#endif
 int vidar_dvxlr_max_d(void) { return kDvxlrMaxD; }
 
 int vidar_dvr_render_forward_f32(const float* sigma, const float* origin, const float* points,
@@ -351,14 +345,9 @@ int vidar_dvr_render_forward_f32(const float* sigma, const float* origin, const 
   if (step_parallel(N, M, g, kParAutoForward))
     launch_par<kParForward>(sigma, nullptr, origin, points, tindex, pred_dist, gt_dist, nullptr, nullptr, nullptr,
                             nullptr, nullptr, N, M, g, train_phase, (hipStream_t)stream);
-  else if (sort_rays(N, M))
-    hipLaunchKernelGGL(dvr_render_forward_kernel<kSortBlock>, dim3((M + kSortBlock - 1) / kSortBlock, N),
-                       dim3(kSortBlock), 0, (hipStream_t)stream, sigma, origin, points, tindex,
-                       pred_dist, gt_dist, M, g, train_phase);
   else
-    hipLaunchKernelGGL(dvr_render_forward_kernel<kWave>, dim3((M + kWave - 1) / kWave, N), dim3(kWave),
-                       0, (hipStream_t)stream, sigma, origin, points, tindex, pred_dist, gt_dist, M, g,
-                       train_phase);
+    launch_lane_per_ray(dvr_render_forward_kernel<kSortBlock>, dvr_render_forward_kernel<kWave>, N, M,
+                        (hipStream_t)stream, sigma, origin, points, tindex, pred_dist, gt_dist, M, g, train_phase);
   return vidar_last_error();
 }
 
@@ -377,14 +366,9 @@ int vidar_dvr_render_f32(const float* sigma, const float* origin, const float* p
   if (step_parallel(N, M, g, kParAutoRender))
     launch_par<kParRender>(sigma, nullptr, origin, points, tindex, pred_dist, gt_dist, nullptr, nullptr, nullptr,
                            nullptr, grad_sigma, N, M, g, loss_type, (hipStream_t)stream);
-  else if (sort_rays(N, M))
-    hipLaunchKernelGGL(dvr_render_kernel<kSortBlock>, dim3((M + kSortBlock - 1) / kSortBlock, N),
-                       dim3(kSortBlock), 0, (hipStream_t)stream, sigma, origin, points, tindex,
-                       pred_dist, gt_dist, grad_sigma, M, g, loss_type);
   else
-    hipLaunchKernelGGL(dvr_render_kernel<kWave>, dim3((M + kWave - 1) / kWave, N), dim3(kWave), 0,
-                       (hipStream_t)stream, sigma, origin, points, tindex, pred_dist, gt_dist,
-                       grad_sigma, M, g, loss_type);
+    launch_lane_per_ray(dvr_render_kernel<kSortBlock>, dvr_render_kernel<kWave>, N, M, (hipStream_t)stream, sigma,
+                        origin, points, tindex, pred_dist, gt_dist, grad_sigma, M, g, loss_type);
   return vidar_last_error();
 }
 
@@ -434,21 +418,13 @@ static int dvxlr_render_launch(bool v2, const float* sigma, const float* sigma_r
     if (e == hipSuccess) e = hipMemsetAsync(indices, 0, rows * 3 * sizeof(float), s_);
     if (e != hipSuccess) return (int)e;
   }
-  if (sort_rays(N, M))
-    hipLaunchKernelGGL(dvxlr_march_kernel<kSortBlock>, dim3((M + kSortBlock - 1) / kSortBlock, N),
-                       dim3(kSortBlock), 0, s_, sigma, origin, points, tindex, pred_dist, gt_dist,
-                       indices, M, g);
-  else
-    hipLaunchKernelGGL(dvxlr_march_kernel<kWave>, dim3((M + kWave - 1) / kWave, N), dim3(kWave), 0, s_,
-                       sigma, origin, points, tindex, pred_dist, gt_dist, indices, M, g);
-  const dim3 fgrid((M + 3) / 4, N);
+  launch_lane_per_ray(dvxlr_march_kernel<kSortBlock>, dvxlr_march_kernel<kWave>, N, M, s_, sigma, origin, points,
+                      tindex, pred_dist, gt_dist, indices, M, g);
   const bool pad = (g_dvxlr_pad_mode == 0);
-#define VIDAR_FINISH(V2_, PAD_)                                                                      \
-  hipLaunchKernelGGL((dvxlr_finish_kernel<V2_, PAD_>), fgrid, dim3(256), 0, s_, sigma_regul, tindex, \
-                     dd_dsigma, indices, ray_pred, indicator, M, g)
-  if (v2) { if (pad) VIDAR_FINISH(true, true); else VIDAR_FINISH(true, false); }
-  else    { if (pad) VIDAR_FINISH(false, true); else VIDAR_FINISH(false, false); }
-#undef VIDAR_FINISH
+  auto* finish = v2 ? (pad ? dvxlr_finish_kernel<true, true> : dvxlr_finish_kernel<true, false>)
+                    : (pad ? dvxlr_finish_kernel<false, true> : dvxlr_finish_kernel<false, false>);
+  hipLaunchKernelGGL(finish, dim3((M + 3) / 4, N), dim3(256), 0, s_, sigma_regul, tindex, dd_dsigma, indices, ray_pred,
+                     indicator, M, g);
   return vidar_last_error();
 }
 

@@ -1,7 +1,8 @@
-// Ray traversal + online integration shared by every dvr / dvxlr / dvxlr_v2 kernel.
+// Ray traversal + online integration shared by every dvr / dvxlr / dvxlr_v2 kernel, and the per-ray
+// bodies of the three render ops (seq_forward_ray, seq_render_ray, dvxlr_march_ray).
 //
 // Plain C++ on purpose: the kernels of dvr_family.hip instantiate it per lane, and
-// tests/march_host.cpp compiles the very same text with g++ so that the traversal logic can be
+// tests/march_host.cpp compiles the very same text with g++ so that the ray bodies can be
 // checked by the CPU test-suite on a machine without a GPU.  Everything here is IEEE fp64 in the
 // reference's operation order (compile with -ffp-contract=off).
 //
@@ -40,15 +41,23 @@ struct RayIn {
   bool valid;  // false: padded ray (tindex < 0) or tindex out of range
 };
 
+// Which sigma slice does a ray of time index t read?  false: padded ray (t < 0) or NaN, or ti >= T.  A static sigma
+// (T == 1, dvxlr.cu:197) serves EVERY time index from slice 0.  `ti` is the truncated index (0 when false).
+VIDAR_DEV bool time_slice(float t, int T, long& ti, int& ts) {
+  const bool real = !(t < 0.f) && (t == t);
+  const long i = real ? (long)t : 0;
+  const bool ok = real && (T == 1 || i < T);   // reference: device assert
+  ti = ok ? i : 0;
+  ts = (T == 1) ? 0 : (int)ti;
+  return ok;
+}
+
 VIDAR_DEV RayIn load_ray(const float* __restrict__ origin, const float* __restrict__ points,
                          const float* __restrict__ tindex, int n, int c, int M, const Vol& v) {
   RayIn r;
-  const float t = tindex[(size_t)n * M + c];
-  r.valid = !(t < 0.f) && (t == t);
-  long ti = r.valid ? (long)t : 0;
-  if (!(v.T == 1 || ti < v.T) || ti >= v.TO) r.valid = false;  // reference: device assert
-  if (!r.valid) ti = 0;
-  r.ts = (v.T == 1) ? 0 : (int)ti;
+  long ti;
+  r.valid = time_slice(tindex[(size_t)n * M + c], v.T, ti, r.ts);
+  if (ti >= v.TO) { r.valid = false; ti = 0; r.ts = 0; }   // the ray also reads origin[n][ti]
   const float* o = origin + ((size_t)n * v.TO + ti) * 3;
   const float* p = points + ((size_t)n * M + c) * 3;
   r.xo = o[0]; r.yo = o[1]; r.zo = o[2];
@@ -250,8 +259,95 @@ struct SequentialTraversal {
   VIDAR_DEV double run(const RayIn& r, const Vol& g, Sink& sink) const { return march<MODE>(r, g, sink); }
 };
 
-// dvxlr / dvxlr_v2 march of ray c of sample n (launch 1 of dvxlr.render, see dvr_family.hip).  `trav` is the
-// traversal that feeds the integrator: the sequential march, or (host harness only) its step-parallel form.
+// The four numbers of an integrated ray (Integrator: k, d0, S, dprev; ParResult of dvr_par_kernels.h carries the same)
+// -> what the API reports.  A ray without samples reports -1 / -1.  gt is the ray length, clamped to the exit distance
+// of the last sample everywhere but in dvr.render_forward's test phase.
+struct RayDist {
+  double pred = -1.0, gt = -1.0;
+  bool hit = false;
+};
+VIDAR_DEV RayDist ray_dist(int count, double d0, double S, double dprev, double len, bool clamp_gt) {
+  RayDist o;
+  if (count > 0) {
+    o.pred = d0 + S;
+    o.gt = clamp_gt ? fmin(len, dprev) : len;
+    o.hit = true;
+  }
+  return o;
+}
+
+// d loss / d pred_dist of dvr.render's fused loss (dvr.cu:594-623): 0 l1, 1 l2, 2 absrel
+VIDAR_DEV double dvr_loss_slope(int loss_type, double exp_d, double gt_d) {
+  if (loss_type == 0) return (exp_d >= gt_d) ? 1.0 : -1.0;
+  if (loss_type == 1) return exp_d - gt_d;
+  if (loss_type == 2) return (exp_d >= gt_d) ? (1.0 / gt_d) : -(1.0 / gt_d);
+  return 1.0;
+}
+
+// d loss / d sigma[voxel of sample k] of one ray: dl_dd * d pred / d sigma_k, with P_k the prefix of W before k
+VIDAR_DEV double grad_term(double dl_dd, double dt, double P, double S_total) { return dl_dd * (dt * (P - S_total)); }
+
+// Second march of dvr.render: adds every sample's fp32-rounded gradient term into its voxel.  Add()(G* slot, float v)
+// says how: the kernels add into float with a hardware atomic, the host harness into double.
+template <class Add, class G>
+struct GradScatter {
+  G* __restrict__ grad;  // grad_sigma[n][ts] slice
+  double S_total, dl_dd;
+  VIDAR_DEV void commit(int, int vid, double, double dt, double P, double) {
+    const double t = grad_term(dl_dd, dt, P, S_total);
+    if (t != 0.0) Add()(grad + vid, (float)t);
+  }
+};
+
+// The per-ray bodies below are what the lane-per-ray kernels run per lane and the step-parallel kernels run for their
+// irregular rays.  `trav` is the traversal that feeds the integrator: the sequential march, or (host harness only) its
+// step-parallel form.
+
+// dvr.render_forward of ray c of sample n
+template <class Trav = SequentialTraversal>
+VIDAR_DEV void seq_forward_ray(const float* __restrict__ sigma, const float* __restrict__ origin,
+                               const float* __restrict__ points, const float* __restrict__ tindex,
+                               float* __restrict__ pred_dist, float* __restrict__ gt_dist, int n, int c, int M,
+                               const Vol& g, int train_phase, const Trav trav = Trav()) {
+  RayDist o;
+  const RayIn r = load_ray(origin, points, tindex, n, c, M, g);
+  if (r.valid) {
+    NoEmit ne;
+    const size_t vol = (size_t)g.Z * g.Y * g.X;
+    Integrator<kRounded, kDvrMaxD, NoEmit> a(sigma + ((size_t)n * g.T + r.ts) * vol, g.Y, g.X, ne);
+    const double len = trav.template run<kRounded>(r, g, a);
+    o = ray_dist(a.k, a.d0, a.S, a.dprev, len, train_phase != 0);
+  }
+  pred_dist[(size_t)n * M + c] = (float)o.pred;
+  gt_dist[(size_t)n * M + c] = (float)o.gt;
+}
+
+// dvr.render of ray c of sample n: one march for the total, a second one scatters the gradient
+template <class Add, class G, class Trav = SequentialTraversal>
+VIDAR_DEV void seq_render_ray(const float* __restrict__ sigma, const float* __restrict__ origin,
+                              const float* __restrict__ points, const float* __restrict__ tindex,
+                              float* __restrict__ pred_dist, float* __restrict__ gt_dist, G* __restrict__ grad_sigma,
+                              int n, int c, int M, const Vol& g, int loss_type, const Trav trav = Trav()) {
+  RayDist o;
+  const RayIn r = load_ray(origin, points, tindex, n, c, M, g);
+  if (r.valid) {
+    const size_t vol = (size_t)g.Z * g.Y * g.X;
+    const size_t slice = ((size_t)n * g.T + r.ts) * vol;
+    NoEmit ne;
+    Integrator<kClassic, kDvrMaxD, NoEmit> a(sigma + slice, g.Y, g.X, ne);
+    const double len = trav.template run<kClassic>(r, g, a);
+    o = ray_dist(a.k, a.d0, a.S, a.dprev, len, true);
+    if (o.hit) {
+      GradScatter<Add, G> gs{grad_sigma + slice, a.S, dvr_loss_slope(loss_type, o.pred, o.gt)};
+      Integrator<kClassic, kDvrMaxD, GradScatter<Add, G>> b(sigma + slice, g.Y, g.X, gs);
+      trav.template run<kClassic>(r, g, b);
+    }
+  }
+  pred_dist[(size_t)n * M + c] = (float)o.pred;
+  gt_dist[(size_t)n * M + c] = (float)o.gt;
+}
+
+// dvxlr / dvxlr_v2 march of ray c of sample n (launch 1 of dvxlr.render, see dvr_family.hip)
 template <class Trav = SequentialTraversal>
 VIDAR_DEV void dvxlr_march_ray(const float* __restrict__ sigma, const float* __restrict__ origin,
                                const float* __restrict__ points, const float* __restrict__ tindex,
@@ -261,7 +357,8 @@ VIDAR_DEV void dvxlr_march_ray(const float* __restrict__ sigma, const float* __r
   constexpr int L = kDvxlrMaxD;
   const size_t row = (size_t)n * M + c;
   float* idr = indices + row * L * 3;
-  float pred = -1.f, gt = -1.f, stash = 0.f;
+  float stash = 0.f;
+  RayDist o;
   const RayIn r = load_ray(origin, points, tindex, n, c, M, g);
   if (r.valid) {
     RowStager st;
@@ -274,9 +371,8 @@ VIDAR_DEV void dvxlr_march_ray(const float* __restrict__ sigma, const float* __r
     Integrator<kRoundedMerged, kDvxlrMaxD, RowStager> a(sigma + ((size_t)n * g.T + r.ts) * vol, g.Y, g.X,
                                                         st);
     const double len = trav.template run<kRoundedMerged>(r, g, a);
-    if (a.k > 0) {
-      pred = (float)(a.d0 + a.S);
-      gt = (float)fmin(len, a.dprev);
+    o = ray_dist(a.k, a.d0, a.S, a.dprev, len, true);
+    if (o.hit) {
       // the reference's (max_d - d_last) p_out term (dvxlr.cu:412-439) is 0, or NaN when the
       // distances are NaN (zero-length ray): such a ray poisons its whole row
       const double tail = a.dprev - a.dprev;
@@ -284,8 +380,8 @@ VIDAR_DEV void dvxlr_march_ray(const float* __restrict__ sigma, const float* __r
     }
   }
   idr[2] = stash;
-  pred_dist[row] = pred;
-  gt_dist[row] = gt;
+  pred_dist[row] = (float)o.pred;
+  gt_dist[row] = (float)o.gt;
 }
 
 }  // namespace vidar_march

@@ -22,7 +22,7 @@ constexpr int kParRays = 16;        // rays per workgroup -> 48 chain lanes
 constexpr int kParThreads = 256;
 constexpr int kParBudget = 1280;    // staged elements per pass: 2 x 10 KB of LDS -> 7 workgroups per CU
 
-enum ParEmit : int { kEmitNone = 0, kEmitScatter = 2, kEmitRows = 3 };
+enum ParEmit : int { kEmitNone = 0, kEmitRows = 1 };
 
 struct ParHdr {
   double dir[3], tmax[3];
@@ -88,21 +88,45 @@ struct RowsOut {       // dvxlr rows of one ray (kEmitRows)
   float* ind;          // v2: indicator [1026]
   const float* reg;    // v2: sigma_regul slice
   int pad_to;          // zeros / -1 up to here (the early fill starts there)
+
+  // One wave writes the padding (zeros, -1 for the v2 indicator) of samples [from, to): the scalar gap between a live
+  // prefix and the float4 fill of the padding workgroups (wave_fill), which starts at the ray's element bound.
+  template <bool V2>
+  __device__ __forceinline__ void pad(int from, int to, int lane) const {
+    for (int k = from + lane; k < to; k += 64) {
+      dd[k] = 0.f;
+      idx[3 * k] = 0.f; idx[3 * k + 1] = 0.f; idx[3 * k + 2] = 0.f;
+      if (V2) { rp[k] = 0.f; ind[k] = -1.f; }
+    }
+  }
 };
 
-// Lane-per-step integration of one ray by one wave.  steps: S entries of (voxel coordinates, d).  Chunks of 63 new
-// steps; lane 0 carries the still-open sample of the previous chunk (merged mode: the pending run; otherwise the
-// last sample, whose W needs the next sample's distance).
-//   EMIT == kEmitScatter  adds dl_dd * dt_k * (P_k - S_total) to grad[voxel]          (second pass of dvr.render)
+// rows of ray `row` (= n M + c); reg: the ray's sigma_regul slice (v2) or nullptr
+template <bool V2>
+__device__ __forceinline__ RowsOut rows_of(float* __restrict__ dd_dsigma, float* __restrict__ indices,
+                                           float* __restrict__ ray_pred, float* __restrict__ indicator,
+                                           const float* __restrict__ reg, size_t row, int pad_to) {
+  constexpr int L = kDvxlrMaxD;
+  RowsOut ro;
+  ro.dd = dd_dsigma + row * L; ro.idx = indices + row * L * 3;
+  ro.rp = V2 ? ray_pred + row * L : nullptr; ro.ind = V2 ? indicator + row * L : nullptr;
+  ro.reg = reg;
+  ro.pad_to = pad_to;
+  return ro;
+}
+
+// Lane-per-step integration of one ray by one wave in the merged mode (dvxlr / dvxlr_v2: consecutive steps into the
+// same voxel are one sample).  steps: S entries of (voxel coordinates, d).  Chunks of 63 new steps; lane 0 carries the
+// still-open sample of the previous chunk (the pending run).
+//   EMIT == kEmitNone     only the sums (the first pass of a ray with more than one chunk)
 //   EMIT == kEmitRows     writes the final dvxlr rows: dd_dsigma[k] = -dt_k (S_total - P_k), (z, y, x), v2 extras.
 //                         S_total: known (a first kEmitNone pass) when the ray has more than one chunk, else taken
 //                         from this chunk's own scan.
-template <int MODE, int EMIT, bool V2>
+template <int EMIT, bool V2>
 __device__ __forceinline__ ParResult par_consume(const double* __restrict__ md, const short* __restrict__ qb, int S,
                                                  const float* __restrict__ sig, const Vol& g, double true_len,
-                                                 const RowsOut& rows, float* __restrict__ grad, double S_total,
-                                                 double dl_dd, int lane, float pre0, float pre1) {
-  constexpr bool kMerged = (MODE == kRoundedMerged);
+                                                 const RowsOut& rows, double S_total, int lane, float pre0,
+                                                 float pre1) {
   int k_base = 0;
   float c_sg = 0.f;
   double csd_c = 0.0, T_c = 1.0, dl_c = 0.0, d0 = 0.0, P_c = 0.0;
@@ -131,22 +155,19 @@ __device__ __forceinline__ ParResult par_consume(const double* __restrict__ md, 
       lastd = (s > 0) ? md[s - 1] : 0.0;
       udt = fmax(0.0, d - lastd);
     }
-    bool same = false;
-    if (kMerged) {
-      const int vid_up = dpp0_i32<kWaveShr1>(vid);
-      const int valid_up = dpp0_i32<kWaveShr1>((int)valid);
-      same = (lane > 0) && valid && (valid_up != 0) && (vid == vid_up);
-      // udt_s = max(0, d_s - (d_{s-1} - udt_{s-1})) inside a run of equal voxels: a short serial recurrence;
-      // iterate to the fixed point (one sweep per run depth)
-      bool any = __ballot(same) != 0ull;
-      while (any) {
-        const double up = dpp0_f64<kWaveShr1, 0xF>(udt);
-        const double nu = same ? par_dt(d, lastd, true, up) : udt;
-        any = __ballot(__double_as_longlong(nu) != __double_as_longlong(udt)) != 0ull;
-        udt = nu;
-      }
+    const int vid_up = dpp0_i32<kWaveShr1>(vid);
+    const int valid_up = dpp0_i32<kWaveShr1>((int)valid);
+    const bool same = (lane > 0) && valid && (valid_up != 0) && (vid == vid_up);
+    // udt_s = max(0, d_s - (d_{s-1} - udt_{s-1})) inside a run of equal voxels: a short serial recurrence;
+    // iterate to the fixed point (one sweep per run depth)
+    bool any = __ballot(same) != 0ull;
+    while (any) {
+      const double up = dpp0_f64<kWaveShr1, 0xF>(udt);
+      const double nu = same ? par_dt(d, lastd, true, up) : udt;
+      any = __ballot(__double_as_longlong(nu) != __double_as_longlong(udt)) != 0ull;
+      udt = nu;
     }
-    const int same_dn = kMerged ? dpp0_i32<kWaveShl1>((int)same) : 0;
+    const int same_dn = dpp0_i32<kWaveShl1>((int)same);
     const bool commit = valid && ((lane == last_lane) ? done : (same_dn == 0));
     const unsigned long long cm = __ballot(commit);
     const int kl = k_base + __popcll(cm & lt);
@@ -175,12 +196,6 @@ __device__ __forceinline__ ParResult par_consume(const double* __restrict__ md, 
         }
       }
     }
-    if (EMIT == kEmitScatter) {
-      if (commit) {
-        const double gr = dl_dd * (udt * (P - S_total));
-        if (gr != 0.0) unsafeAtomicAdd(grad + vid, (float)gr);
-      }
-    }
     P_c = readlane_f64(P, 63);
     csd_c = readlane_f64(csd, 63);
     if (ncommit != 0) {
@@ -201,13 +216,7 @@ __device__ __forceinline__ ParResult par_consume(const double* __restrict__ md, 
       }
     }
   }
-  if (EMIT == kEmitRows) {        // the gap between the live prefix and the early fill
-    for (int k = k_base + lane; k < rows.pad_to; k += 64) {
-      rows.dd[k] = 0.f;
-      rows.idx[3 * k] = 0.f; rows.idx[3 * k + 1] = 0.f; rows.idx[3 * k + 2] = 0.f;
-      if (V2) { rows.rp[k] = 0.f; rows.ind[k] = -1.f; }
-    }
-  }
+  if (EMIT == kEmitRows) rows.template pad<V2>(k_base, rows.pad_to, lane);   // from the live prefix to the early fill
   ParResult R;
   R.count = k_base;
   R.d0 = d0;
@@ -222,7 +231,7 @@ __device__ __forceinline__ double wave_total_f64(double v) { return readlane_f64
 // Lean lane-per-step integrator of the modes WITHOUT the duplicate merge (dvr.render_forward, dvr.render): every step
 // is a sample, so lane = step, the neighbouring distances come straight from LDS and nothing is carried between
 // chunks except the running optical depth:  W_s = exp(-csd_s) (d_{s+1} - d_s),  pred = d_0 + sum_s W_s.
-//   SCATTER: second pass of dvr.render -- grad[voxel_s] += dl_dd * dt_s * (P_s - S_total), P_s = sum_{j < s} W_j
+//   SCATTER: second pass of dvr.render -- grad[voxel_s] += grad_term(dl_dd, dt_s, P_s, S_total), P_s = sum_{j < s} W_j
 template <bool SCATTER>
 __device__ __forceinline__ ParResult par_consume_plain(const double* __restrict__ md, const short* __restrict__ qb,
                                                        int S, const float* __restrict__ sig, const Vol& g,
@@ -251,7 +260,7 @@ __device__ __forceinline__ ParResult par_consume_plain(const double* __restrict_
       const double incl = wave_scan_f64(w);
       const double P = P_c + (incl - w);                      // exclusive: sum_{j < s} W_j
       if (valid) {
-        const double gr = dl_dd * (dt * (P - S_total));
+        const double gr = grad_term(dl_dd, dt, P, S_total);
         if (gr != 0.0) unsafeAtomicAdd(grad + vid, (float)gr);
       }
       P_c += readlane_f64(incl, 63);
@@ -276,69 +285,10 @@ template <> struct ParMode<kParDvxlr> { static constexpr int mode = kRoundedMerg
 template <> struct ParMode<kParRender> { static constexpr int mode = kClassic; };
 template <> struct ParMode<kParDvxlrV2> { static constexpr int mode = kRoundedMerged; };
 
-// sequential per-ray code (the lane-per-ray kernels' bodies): irregular rays of a step-parallel launch
-__device__ __forceinline__ void seq_forward_ray(const float* __restrict__ sigma, const float* __restrict__ origin,
-                                                const float* __restrict__ points, const float* __restrict__ tindex,
-                                                float* __restrict__ pred_dist, float* __restrict__ gt_dist, int n,
-                                                int c, int M, const Vol& g, int train_phase) {
-  float pred = -1.f, gt = -1.f;
-  const RayIn r = load_ray(origin, points, tindex, n, c, M, g);
-  if (r.valid) {
-    NoEmit ne;
-    const size_t vol = (size_t)g.Z * g.Y * g.X;
-    Integrator<kRounded, kDvrMaxD, NoEmit> integ(sigma + ((size_t)n * g.T + r.ts) * vol, g.Y, g.X, ne);
-    const double len = march<kRounded>(r, g, integ);
-    if (integ.k > 0) {
-      pred = (float)(integ.d0 + integ.S);
-      gt = (float)(train_phase ? fmin(len, integ.dprev) : len);
-    }
-  }
-  pred_dist[(size_t)n * M + c] = pred;
-  gt_dist[(size_t)n * M + c] = gt;
-}
-
-struct GradScatter {
-  float* __restrict__ grad;  // grad_sigma[n][ts] slice
-  double S_total, dl_dd;
-  __device__ __forceinline__ void commit(int, int vid, double, double dt, double P, double) {
-    const double g = dl_dd * (dt * (P - S_total));
-    if (g != 0.0) unsafeAtomicAdd(grad + vid, (float)g);
-  }
+// what GradScatter (dvr_march.h) adds into on the device: fp32 hardware atomics
+struct AtomicAddF32 {
+  __device__ __forceinline__ void operator()(float* slot, float v) const { unsafeAtomicAdd(slot, v); }
 };
-
-__device__ __forceinline__ double dvr_loss_slope(int loss_type, double exp_d, double gt_d) {
-  if (loss_type == 0) return (exp_d >= gt_d) ? 1.0 : -1.0;
-  if (loss_type == 1) return exp_d - gt_d;
-  if (loss_type == 2) return (exp_d >= gt_d) ? (1.0 / gt_d) : -(1.0 / gt_d);
-  return 1.0;
-}
-
-__device__ __forceinline__ void seq_render_ray(const float* __restrict__ sigma, const float* __restrict__ origin,
-                                               const float* __restrict__ points, const float* __restrict__ tindex,
-                                               float* __restrict__ pred_dist, float* __restrict__ gt_dist,
-                                               float* __restrict__ grad_sigma, int n, int c, int M, const Vol& g,
-                                               int loss_type) {
-  float pred = -1.f, gt = -1.f;
-  const RayIn r = load_ray(origin, points, tindex, n, c, M, g);
-  if (r.valid) {
-    const size_t vol = (size_t)g.Z * g.Y * g.X;
-    const size_t slice = ((size_t)n * g.T + r.ts) * vol;
-    NoEmit ne;
-    Integrator<kClassic, kDvrMaxD, NoEmit> a(sigma + slice, g.Y, g.X, ne);
-    const double len = march<kClassic>(r, g, a);
-    if (a.k > 0) {
-      const double exp_d = a.d0 + a.S;
-      const double gt_d = fmin(len, a.dprev);
-      pred = (float)exp_d;
-      gt = (float)gt_d;
-      GradScatter gs{grad_sigma + slice, a.S, dvr_loss_slope(loss_type, exp_d, gt_d)};
-      Integrator<kClassic, kDvrMaxD, GradScatter> b(sigma + slice, g.Y, g.X, gs);
-      march<kClassic>(r, g, b);
-    }
-  }
-  pred_dist[(size_t)n * M + c] = pred;
-  gt_dist[(size_t)n * M + c] = gt;
-}
 
 // Finish pass of one parked dvxlr row by one wave (the body of dvxlr_finish_kernel, dvr_family.hip): reverse wave
 // scan of the parked W -> suffix sums, dd = -dt R, (z, y, x) unpacked, v2 extras.  Used by the two-launch form and,
@@ -398,19 +348,115 @@ __device__ __forceinline__ void wave_fill(float* __restrict__ base, size_t a, si
   if (b4 + lane < b) base[b4 + lane] = val;
 }
 
-#ifdef VIDAR_PAR_TIMING   // experiment only: cycles per phase, summed over workgroups (wave 0)
-__device__ unsigned long long g_par_cycles[8];
-#define PAR_STAMP(i)                                                       \
-  do {                                                                     \
-    if (tid == 0) {                                                        \
-      const unsigned long long now_ = __builtin_readcyclecounter();        \
-      atomicAdd(&g_par_cycles[i], now_ - stamp_);                          \
-      stamp_ = now_;                                                       \
-    }                                                                      \
-  } while (0)
-#else
-#define PAR_STAMP(i) do {} while (0)
-#endif
+// One-launch dvxlr: the FIRST `pad_wgs` workgroups of the grid (about one per CU, dispatched first) only PAD,
+// persistently: each walks blocks of 64 rays and writes the zeros / -1 of their rows from each ray's element bound
+// (the same par_setup as the compute workgroups, so the two never touch the same bytes) to the row end.  95 % of
+// the call's bytes stream at fill rate for the whole launch while the compute workgroups, which share no barrier
+// with them, take the remaining wave slots.  (Measured alternatives: padding from the compute workgroups' idle
+// waves serialises behind their barriers; one padding workgroup per compute workgroup takes half the wave slots;
+// padding workgroups at the end of the grid run after the march -- profiles/r05_kbench_dvr_traversal.log)
+// `bound`: 64 ints of LDS.
+template <int MODE, bool V2>
+__device__ __forceinline__ void par_pad_rows(int* bound, const float* __restrict__ origin,
+                                             const float* __restrict__ points, const float* __restrict__ tindex,
+                                             float* __restrict__ dd_dsigma, float* __restrict__ indices,
+                                             float* __restrict__ ray_pred, float* __restrict__ indicator, int n, int M,
+                                             const Vol& g, int pad_wgs) {
+  constexpr int L = kDvxlrMaxD;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nblk = (M + 63) / 64;
+  for (int blk = (int)blockIdx.x; blk < nblk; blk += pad_wgs) {
+    const int c0f = blk * 64;
+    const int nrows = min(64, M - c0f);
+    if (tid < nrows) {
+      const RayIn rf = load_ray(origin, points, tindex, n, c0f + tid, M, g);
+      const ParRay F = par_setup<MODE>(rf, g);
+      // regular ray: from its element bound.  Padded ray (no samples): the whole row (the compute workgroup only
+      // stores the same 0.0 stash into it).  Valid but irregular ray: nothing -- its row belongs to the compute
+      // workgroup's sequential fallback, which pads it itself.
+      bound[tid] = F.regular ? F.elems : (rf.valid ? L : 0);
+    }
+    __syncthreads();
+    const size_t row0 = (size_t)n * M + c0f;
+    for (int r = wave; r < nrows; r += kParThreads / 64) {      // a wave pads whole rows
+      const size_t e = (size_t)bound[r];
+      const size_t row = row0 + r;
+      wave_fill(dd_dsigma, row * L + e, (row + 1) * L, 0.f, lane);
+      wave_fill(indices, (row * L + e) * 3, (row + 1) * L * 3, 0.f, lane);
+      if (V2) {
+        wave_fill(ray_pred, row * L + e, (row + 1) * L, 0.f, lane);
+        wave_fill(indicator, row * L + e, (row + 1) * L, -1.f, lane);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// Consume phase of one staged ray by one wave: md / qb are its S merged distances / voxel coordinates, `slice` the
+// offset of its sigma[n][ts] volume, `elems` its element bound (where the padding workgroups' fill of its rows starts).
+template <int KIND>
+__device__ __forceinline__ RayDist par_consume_ray(const double* __restrict__ dm, const short* __restrict__ qb, int S,
+                                                   double len, int elems, size_t slice, const float* __restrict__ sigma,
+                                                   const float* __restrict__ sigma_regul, float* __restrict__ dd_dsigma,
+                                                   float* __restrict__ indices, float* __restrict__ ray_pred,
+                                                   float* __restrict__ indicator, float* __restrict__ grad_sigma,
+                                                   size_t row, const Vol& g, int aux, int lane, float pre0,
+                                                   float pre1) {
+  constexpr bool V2 = (KIND == kParDvxlrV2);
+  const float* sig = sigma + slice;
+  if (KIND == kParDvxlr || KIND == kParDvxlrV2) {
+    const float* reg = V2 ? sigma_regul + slice : nullptr;
+    const RowsOut ro = rows_of<V2>(dd_dsigma, indices, ray_pred, indicator, reg, row, elems);
+    double St = 0.0;      // a ray of more than one chunk: the total first
+    if (S > 63) St = par_consume<kEmitNone, false>(dm, qb, S, sig, g, len, RowsOut{}, 0.0, lane, pre0, pre1).S;
+    const ParResult R = par_consume<kEmitRows, V2>(dm, qb, S, sig, g, len, ro, St, lane, pre0, pre1);
+    return ray_dist(R.count, R.d0, R.S, R.dprev, len, true);
+  }
+  const ParResult R = par_consume_plain<false>(dm, qb, S, sig, g, nullptr, 0.0, 0.0, lane, pre0, pre1);
+  const RayDist o = ray_dist(R.count, R.d0, R.S, R.dprev, len, KIND == kParRender || aux != 0);
+  if (KIND == kParRender && o.hit)   // aux: loss_type
+    par_consume_plain<true>(dm, qb, S, sig, g, grad_sigma + slice, R.S, dvr_loss_slope(aux, o.pred, o.gt), lane, pre0,
+                            pre1);
+  return o;
+}
+
+// After the passes: the irregular rays of the workgroup (hdr[].state == 1) take the sequential per-ray code of the
+// lane-per-ray kernels, one lane each; the dvxlr rows they park are then finished by a wave each.
+template <int KIND>
+__device__ __forceinline__ void par_irregular_rays(const ParHdr* hdr, const float* __restrict__ sigma,
+                                                   const float* __restrict__ sigma_regul,
+                                                   const float* __restrict__ origin, const float* __restrict__ points,
+                                                   const float* __restrict__ tindex, float* __restrict__ pred_dist,
+                                                   float* __restrict__ gt_dist, float* __restrict__ dd_dsigma,
+                                                   float* __restrict__ indices, float* __restrict__ ray_pred,
+                                                   float* __restrict__ indicator, float* __restrict__ grad_sigma, int n,
+                                                   int c0, int M, const Vol& g, int aux) {
+  constexpr bool kRows = (KIND == kParDvxlr || KIND == kParDvxlrV2);
+  constexpr bool V2 = (KIND == kParDvxlrV2);
+  constexpr int L = kDvxlrMaxD;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid < kParRays && hdr[tid].state == 1) {
+    const int c = c0 + tid;
+    if (KIND == kParForward) seq_forward_ray(sigma, origin, points, tindex, pred_dist, gt_dist, n, c, M, g, aux);
+    else if (kRows) dvxlr_march_ray(sigma, origin, points, tindex, pred_dist, gt_dist, indices, n, c, M, g);
+    else seq_render_ray<AtomicAddF32>(sigma, origin, points, tindex, pred_dist, gt_dist, grad_sigma, n, c, M, g, aux);
+  }
+  if (!kRows) return;
+  __syncthreads();
+  const size_t vol = (size_t)g.Z * g.Y * g.X;
+  for (int r = wave; r < kParRays; r += kParThreads / 64) {
+    if (hdr[r].state != 1) continue;
+    const size_t row = (size_t)n * M + c0 + r;
+    const float* reg = nullptr;
+    if (V2 && hdr[r].valid) reg = sigma_regul + ((size_t)n * g.T + hdr[r].ts) * vol;
+    // the rest of the row: a valid irregular ray's row is not touched by the padding workgroup; a ray whose bound
+    // check failed (mathematically impossible, kept as a net) was padded from its element bound
+    const int pad_to = !hdr[r].valid ? 0 : (hdr[r].elems > 0 ? hdr[r].elems : L);
+    const RowsOut ro = rows_of<V2>(dd_dsigma, indices, ray_pred, indicator, reg, row, pad_to);
+    const int cnt = dvxlr_finish_row<V2>(reg, ro.dd, ro.idx, ro.rp, ro.ind, g, lane);
+    ro.template pad<V2>(cnt, pad_to, lane);
+  }
+}
 
 // grid (ceil(M / kParRays), N), block kParThreads.  `aux`: train_phase (forward) / loss_type (render).
 template <int KIND>
@@ -423,53 +469,17 @@ __global__ __launch_bounds__(kParThreads) void dvr_par_kernel(
   constexpr int MODE = ParMode<KIND>::mode;
   constexpr bool kRows = (KIND == kParDvxlr || KIND == kParDvxlrV2);
   constexpr bool V2 = (KIND == kParDvxlrV2);
-  constexpr int L = kDvxlrMaxD;
   __shared__ ParStage<MODE == kClassic> st;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = blockIdx.y;
   const size_t vol = (size_t)g.Z * g.Y * g.X;
 
-  // ---- one-launch dvxlr: the FIRST `pad_wgs` workgroups of the grid (about one per CU, dispatched first) only PAD,
-  // persistently: each walks blocks of 64 rays and writes the zeros / -1 of their rows from each ray's element bound
-  // (the same par_setup as the compute workgroups, so the two never touch the same bytes) to the row end.  95 % of
-  // the call's bytes stream at fill rate for the whole launch while the compute workgroups, which share no barrier
-  // with them, take the remaining wave slots.  (Measured alternatives: padding from the compute workgroups' idle
-  // waves serialises behind their barriers; one padding workgroup per compute workgroup takes half the wave slots;
-  // padding workgroups at the end of the grid run after the march -- profiles/r05_kbench_dvr_traversal.log) ----
-  if (kRows && (int)blockIdx.x < pad_wgs) {
-    int* bound = reinterpret_cast<int*>(st.seq);
-    const int nblk = (M + 63) / 64;
-    for (int blk = (int)blockIdx.x; blk < nblk; blk += pad_wgs) {
-      const int c0f = blk * 64;
-      const int nrows = min(64, M - c0f);
-      if (tid < nrows) {
-        const RayIn rf = load_ray(origin, points, tindex, n, c0f + tid, M, g);
-        const ParRay F = par_setup<MODE>(rf, g);
-        // regular ray: from its element bound.  Padded ray (no samples): the whole row (the compute workgroup only
-        // stores the same 0.0 stash into it).  Valid but irregular ray: nothing -- its row belongs to the compute
-        // workgroup's sequential fallback, which pads it itself.
-        bound[tid] = F.regular ? F.elems : (rf.valid ? L : 0);
-      }
-      __syncthreads();
-      const size_t row0 = (size_t)n * M + c0f;
-      for (int r = wave; r < nrows; r += kParThreads / 64) {      // a wave pads whole rows
-        const size_t e = (size_t)bound[r];
-        const size_t row = row0 + r;
-        wave_fill(dd_dsigma, row * L + e, (row + 1) * L, 0.f, lane);
-        wave_fill(indices, (row * L + e) * 3, (row + 1) * L * 3, 0.f, lane);
-        if (V2) {
-          wave_fill(ray_pred, row * L + e, (row + 1) * L, 0.f, lane);
-          wave_fill(indicator, row * L + e, (row + 1) * L, -1.f, lane);
-        }
-      }
-      __syncthreads();
-    }
+  if (kRows && (int)blockIdx.x < pad_wgs) {      // one-launch dvxlr: the first workgroups of the grid only pad
+    par_pad_rows<MODE, V2>(reinterpret_cast<int*>(st.seq), origin, points, tindex, dd_dsigma, indices, ray_pred,
+                           indicator, n, M, g, pad_wgs);
     return;
   }
   const int c0 = ((int)blockIdx.x - (kRows ? pad_wgs : 0)) * kParRays;
-#ifdef VIDAR_PAR_TIMING
-  unsigned long long stamp_ = __builtin_readcyclecounter();
-#endif
 
   // ---- setup: lane (ray, axis); every lane evaluates the whole ray (its own axis stays in registers) ----
   const int cr = tid / 3, ca = tid - 3 * cr;
@@ -499,7 +509,6 @@ __global__ __launch_bounds__(kParThreads) void dvr_par_kernel(
   }
   if (tid == 0) st.first = 0;
   __syncthreads();
-  PAR_STAMP(0);
 
   // this lane's own axis as scalars (a run-time index into P.ax[] would push the struct into scratch)
   const int size_a = (ca == 0) ? g.X : (ca == 1 ? g.Y : g.Z);
@@ -536,7 +545,6 @@ __global__ __launch_bounds__(kParThreads) void dvr_par_kernel(
       for (int i = 0; i < my_m; ++i) { out[i] = t; t += my_tdelta; }
     }
     __syncthreads();
-    PAR_STAMP(1);
 
     // ---- rank: every element finds its merged position ----
     for (int r = first + wave; r < end; r += kParThreads / 64) {
@@ -564,7 +572,6 @@ __global__ __launch_bounds__(kParThreads) void dvr_par_kernel(
       }
     }
     __syncthreads();
-    PAR_STAMP(2);
 
     // ---- step count, bound check, chain 2: rounded-path voxel coordinates per step ----
     if (mine) {
@@ -604,7 +611,6 @@ __global__ __launch_bounds__(kParThreads) void dvr_par_kernel(
       }
     }
     __syncthreads();
-    PAR_STAMP(3);
 
     // ---- consume: wave per ray, lane per step.  First the density gathers of the first two chunks of all (up to 4)
     // rays of this wave are put in flight together ----
@@ -635,87 +641,25 @@ __global__ __launch_bounds__(kParThreads) void dvr_par_kernel(
       if (h.state != 0) continue;
       const float pre0 = kk == 0 ? pre[0][0] : (kk == 1 ? pre[1][0] : (kk == 2 ? pre[2][0] : pre[3][0]));
       const float pre1 = kk == 0 ? pre[0][1] : (kk == 1 ? pre[1][1] : (kk == 2 ? pre[2][1] : pre[3][1]));
-      const int c = c0 + r;
-      const size_t row = (size_t)n * M + c;
-      const float* sig = sigma + ((size_t)n * g.T + h.ts) * vol;
+      const size_t row = (size_t)n * M + c0 + r;
       const double* dm = st.md + h.off;
       const short* qb = (MODE == kClassic) ? reinterpret_cast<const short*>(st.vox + h.off)
                                            : reinterpret_cast<const short*>(st.seq + h.off);
-      const double len = h.len;
-      const int S = h.S;
-      float pred = -1.f, gt = -1.f;
-      RowsOut none{};
-      if (KIND == kParForward) {
-        const ParResult R = par_consume_plain<false>(dm, qb, S, sig, g, nullptr, 0.0, 0.0, lane, pre0, pre1);
-        if (R.count > 0) {
-          pred = (float)(R.d0 + R.S);
-          gt = (float)(aux ? fmin(len, R.dprev) : len);
-        }
-      } else if (kRows) {
-        RowsOut ro;
-        ro.dd = dd_dsigma + row * L; ro.idx = indices + row * L * 3;
-        ro.rp = V2 ? ray_pred + row * L : nullptr; ro.ind = V2 ? indicator + row * L : nullptr;
-        ro.reg = V2 ? sigma_regul + ((size_t)n * g.T + h.ts) * vol : nullptr;
-        ro.pad_to = h.elems;
-        double St = 0.0;
-        if (S > 63)
-          St = par_consume<MODE, kEmitNone, false>(dm, qb, S, sig, g, len, none, nullptr, 0.0, 0.0, lane, pre0, pre1).S;
-        const ParResult R = par_consume<MODE, kEmitRows, V2>(dm, qb, S, sig, g, len, ro, nullptr, St, 0.0, lane, pre0,
-                                                              pre1);
-        if (R.count > 0) {
-          pred = (float)(R.d0 + R.S);
-          gt = (float)fmin(len, R.dprev);
-        }
-      } else {
-        const ParResult R = par_consume_plain<false>(dm, qb, S, sig, g, nullptr, 0.0, 0.0, lane, pre0, pre1);
-        if (R.count > 0) {
-          const double exp_d = R.d0 + R.S;
-          const double gt_d = fmin(len, R.dprev);
-          pred = (float)exp_d;
-          gt = (float)gt_d;
-          float* grad = grad_sigma + ((size_t)n * g.T + h.ts) * vol;
-          par_consume_plain<true>(dm, qb, S, sig, g, grad, R.S, dvr_loss_slope(aux, exp_d, gt_d), lane, pre0, pre1);
-        }
-      }
+      const RayDist o = par_consume_ray<KIND>(dm, qb, h.S, h.len, h.elems, ((size_t)n * g.T + h.ts) * vol, sigma,
+                                              sigma_regul, dd_dsigma, indices, ray_pred, indicator, grad_sigma, row, g,
+                                              aux, lane, pre0, pre1);
       if (lane == 0) {
-        pred_dist[row] = pred;
-        gt_dist[row] = gt;
+        pred_dist[row] = (float)o.pred;
+        gt_dist[row] = (float)o.gt;
         h.state = 2;
       }
     }
     __syncthreads();
-    PAR_STAMP(4);
     if (tid == 0) st.first = end;
     __syncthreads();
   }
-  // ---- sequential fallback: one lane per irregular ray ----
-  if (tid < kParRays && st.hdr[tid].state == 1) {
-    const int c = c0 + tid;
-    if (KIND == kParForward) seq_forward_ray(sigma, origin, points, tindex, pred_dist, gt_dist, n, c, M, g, aux);
-    else if (kRows) dvxlr_march_ray(sigma, origin, points, tindex, pred_dist, gt_dist, indices, n, c, M, g);
-    else seq_render_ray(sigma, origin, points, tindex, pred_dist, gt_dist, grad_sigma, n, c, M, g, aux);
-  }
-  if (kRows) {                        // ... whose parked rows are finished by a wave each (their padding is in place)
-    __syncthreads();
-    for (int r = wave; r < kParRays; r += kParThreads / 64) {
-      if (st.hdr[r].state != 1) continue;
-      const size_t row = (size_t)n * M + c0 + r;
-      const float* reg = nullptr;
-      if (V2 && st.hdr[r].valid) reg = sigma_regul + ((size_t)n * g.T + st.hdr[r].ts) * vol;
-      const int cnt = dvxlr_finish_row<V2>(reg, dd_dsigma + row * L, indices + row * L * 3,
-                                           V2 ? ray_pred + row * L : nullptr, V2 ? indicator + row * L : nullptr, g,
-                                           lane);
-      // the rest of the row: a valid irregular ray's row is not touched by the padding workgroup; a ray whose bound
-      // check failed (mathematically impossible, kept as a net) was padded from its element bound
-      const int pad_to = !st.hdr[r].valid ? 0 : (st.hdr[r].elems > 0 ? st.hdr[r].elems : L);
-      for (int k = cnt + lane; k < pad_to; k += 64) {
-        dd_dsigma[row * L + k] = 0.f;
-        float* id = indices + (row * L + k) * 3;
-        id[0] = 0.f; id[1] = 0.f; id[2] = 0.f;
-        if (V2) { ray_pred[row * L + k] = 0.f; indicator[row * L + k] = -1.f; }
-      }
-    }
-  }
+  par_irregular_rays<KIND>(st.hdr, sigma, sigma_regul, origin, points, tindex, pred_dist, gt_dist, dd_dsigma, indices,
+                           ray_pred, indicator, grad_sigma, n, c0, M, g, aux);
 }
 
 }  // namespace vidar_march
