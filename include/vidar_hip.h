@@ -582,6 +582,39 @@ int vidar_det_loss_bwd_f32(const float* cls, const float* box, const int32_t* la
                            int B, int Q, int C, int total_g, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Hungarian assignment of the detection loss tail on the device (csrc/det_assign.hip, per-problem body in
+ * csrc/det_assign_math.h): scipy.optimize.linear_sum_assignment for ALL NL * B (layer, sample) cost blocks of a step in
+ * one launch, one workgroup per problem, no host read.  Shortest augmenting paths with dual variables; rows are the
+ * shorter side min(Q, G_b); duals and path costs are fp64 on the fp32 costs widened (fp32 duals lose the optimum at
+ * 900 x 512).
+ *   cost [NL, Q*total_g] f32 as vidar_det_match_cost_f32 writes it (sample b's [Q, G_b] row-major block of a layer's row
+ *   at Q*gt_start[b]); gt_start [B+1] i32 on the DEVICE -- the kernel reads G_b there, the host passes total_g only.
+ *   matched [NL,B,Q] i32: index inside the sample's ground truth, -1 = background; written completely (G_b == 0, Q > G_b
+ *   and Q < G_b alike).  status [NL*B] i32, written completely:
+ *     0 solved;
+ *     1 the block holds NaN or -inf (SciPy: "matrix contains invalid numeric entries"), found by a pre-pass;
+ *     2 every perfect matching of the short side needs a +inf entry (SciPy: "cost matrix is infeasible"; +inf entries that
+ *       can be avoided are legal);
+ *     3 the sample's gt_start range is not inside 0 .. total_g.
+ *   A problem with a non-zero status has -1 in all of its matched row; the other problems of the launch are unaffected.
+ * Ties: equal minima of a search step resolve to the LOWEST COLUMN INDEX, so the result does not depend on lane count,
+ * wave count or arrival order.  Where the optimum is unique the assignment equals SciPy's; on exact ties only the total is.
+ * Extent: the solver state stays in LDS, which holds a long side max(Q, G_b) <= 2048 and a short side min(Q, G_b) <= 1024.
+ * The host knows total_g >= G_b only, so the rule is stated on it: max(Q, total_g) <= 2048 and min(Q, total_g) <= 1024.
+ * vidar_det_assign_workspace_bytes reports *bytes = -1 (and returns 0) for an unsupported extent -- the caller keeps its
+ * host path -- and otherwise the scratch the launch needs (a transposed copy of the cost; 4-byte aligned, caller-owned).
+ * Deterministic: no atomics, nothing shared between workgroups; same inputs, same bytes, whatever slot a problem has.
+ * Every loop of the kernel is bounded by the problem's size: no input makes it spin.
+ * NL == 0 or B == 0 returns 0 without a launch.  total_g == 0 (cost and workspace may be NULL) and Q == 0 (matched may be
+ * NULL) still launch: THE LAUNCH fills matched with -1 and status with 0, the caller does not.
+ * VIDAR_ERR_BAD_ARG before any HIP call: negative sizes, NL*B beyond 2^31-1, a missing pointer, a workspace that is too
+ * small or misaligned, an unsupported extent.
+ * ------------------------------------------------------------------------- */
+int vidar_det_assign_workspace_bytes(int NL, int B, int Q, int total_g, int64_t* bytes);
+int vidar_det_assign_f32(const float* cost, const int32_t* gt_start, int32_t* matched, int32_t* status, int NL, int B,
+                         int Q, int total_g, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Matching step of the nuScenes detection metric, mAP / NDS (csrc/det_eval.hip, pair errors in csrc/det_eval_math.h).  The
  * reference delegates the metric to the nuScenes devkit (datasets/nuscnes_eval.py:628-676 -> accumulate / calc_ap /
  * calc_tp); the semantics here are recalled from the devkit, which is not part of the reference tree.

@@ -575,12 +575,15 @@ def det_operands(seed, NL, B, Q, C, counts, device):
 def bench_det(which):
     """the detection loss tail of one fine-tune step (NL 6, B 1, Q 900, C 10): fused HIP kernels against the plain PyTorch
     composition of the same arithmetic, same process.  Device time per piece by HIP events (median of 5 x 50), and the
-    whole tail -- cost, host assignment, losses forward + backward -- by wall clock with a device drain (median of 30)."""
+    whole tail -- cost, assignment, losses forward + backward -- by wall clock with a device drain (median of 30), with
+    the assignment on the host (the default) and on the device (csrc/det_assign.hip).  The assignment alone: the host path
+    (pinned copy, wait, SciPy over the 6 problems, upload) by wall clock with a device drain, the device launch by HIP
+    events; the assignments of the two are compared before anything is timed."""
     import time
     from vidar_amd.plugin.dense_heads import det_ops as D
     dev = torch.device("cuda", 0)
     NL, B, Q, C = 6, 1, 900, 10
-    for G in (37, 150):
+    for G in (37, 150, 512):
         counts = [G]
         cls, box, gt_norm, gt_label, gt_start, cw = det_operands(G, NL, B, Q, C, counts, dev)
         cls.requires_grad_(True); box.requires_grad_(True)
@@ -593,10 +596,14 @@ def bench_det(which):
             s = fn(cls, box, labels, matched, gt_norm, gt_start, cw, 0.25, 2.0)
             torch.autograd.grad(s, [cls, box], gsum)
 
-        def tail(fused):
+        cost0 = D.match_cost(cls, box, gt_norm, gt_label, gt_start, G, *args)
+        m_dev, st_dev = D.assign_device(cost0, NL, B, Q, gt_start, G)
+        assert torch.equal(m_dev, matched) and not bool(st_dev.any()), "device and host assignments differ"
+
+        def tail(fused, device_assign=False):
             cost = (D.match_cost(cls, box, gt_norm, gt_label, gt_start, G, *args) if fused
                     else D.match_cost_torch(cls.detach(), box.detach(), gt_norm, gt_label, counts, *args))
-            m = D.hungarian(cost, NL, Q, counts)
+            m = D.assign_device(cost, NL, B, Q, gt_start, G)[0] if device_assign else D.hungarian(cost, NL, Q, counts)
             lab = D.labels_from_matched(m, gt_label, gt_start, C)
             s = (D.DetLossFunction.apply if fused else D.det_loss_sums_torch)(cls, box, lab, m, gt_norm, gt_start, cw, 0.25, 2.0)
             torch.autograd.grad(s, [cls, box], gsum)
@@ -607,13 +614,21 @@ def bench_det(which):
                  cost_torch_ms=med(lambda: D.match_cost_torch(cls.detach(), box.detach(), gt_norm, gt_label, counts, *args)),
                  loss_fwd_bwd_hip_ms=med(lambda: loss_pair(D.DetLossFunction.apply)),
                  loss_fwd_bwd_torch_ms=med(lambda: loss_pair(D.det_loss_sums_torch)))
-        for name, fused in (("tail_wall_hip_ms", True), ("tail_wall_torch_ms", False)):
+        r["assign_device_ms"] = float(np.median([timeit(lambda: D.assign_device(cost0, NL, B, Q, gt_start, G), warm=3, it=20)
+                                                 for _ in range(5)]))
+
+        def wall(f):
             ts = []
             for i in range(35):
                 torch.cuda.synchronize(); t0 = time.perf_counter()
-                tail(fused)
+                f()
                 torch.cuda.synchronize(); ts.append((time.perf_counter() - t0) * 1e3)
-            r[name] = float(np.median(ts[5:]))
+            return float(np.median(ts[5:]))
+        r["assign_host_wall_ms"] = wall(lambda: D.hungarian(cost0, NL, Q, counts))
+        r["assign_device_wall_ms"] = wall(lambda: D.assign_device(cost0, NL, B, Q, gt_start, G))
+        r["tail_wall_hip_ms"] = wall(lambda: tail(True))
+        r["tail_wall_hip_device_assign_ms"] = wall(lambda: tail(True, True))
+        r["tail_wall_torch_ms"] = wall(lambda: tail(False))
         report("det_loss_tail", r.pop("loss_fwd_bwd_hip_ms"), **{k: round(v, 4) if isinstance(v, float) else v for k, v in r.items()})
 
 

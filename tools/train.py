@@ -43,6 +43,9 @@ def main():
     ap.add_argument("--device-images", action="store_true",
                     help="with --ann-file: the workers only decode and draw the augmentation, the image pipeline "
                          "(photometric, crop / resize / flip, normalise, pad) runs in HIP kernels with the host path's bits")
+    ap.add_argument("--device-assign", action="store_true",
+                    help="detection fine-tuning: Hungarian assignment on the device (csrc/det_assign.hip), no host read in "
+                         "the loss tail; its status is checked where the loss is read for the log line")
     args = ap.parse_args()
 
     from vidar_amd import checkpoint as C
@@ -148,9 +151,16 @@ def main():
         batches = _Epochs()
     else:
         batches = [sample(i) for i in range(args.samples)]
+    on_log = None
+    if args.device_assign:
+        if not detection:
+            raise SystemExit("--device-assign belongs to the detection fine-tuning recipes")
+        from vidar_amd.plugin.dense_heads import det_ops
+        det_ops.set_assign("device")
+        on_log = lambda: det_ops.check_assign_status(model.pts_bbox_head.last_assign_status)  # noqa: E731
     n = T.fit(ddp, opt, batches, args.iters, scheduler=sched, max_norm=clip,
               log_every=10, log_path=work / "log.jsonl", ckpt_path=work / "latest.pth",
-              ckpt_every=max(1, args.iters // 2), rank=rank, start_iter=it0)
+              ckpt_every=max(1, args.iters // 2), rank=rank, start_iter=it0, on_log=on_log)
     if rank == 0:
         print(f"finished {n} iterations; log: {work / 'log.jsonl'}; checkpoint: {work / 'latest.pth'}")
 

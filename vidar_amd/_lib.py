@@ -125,6 +125,8 @@ _ABI = {
     "vidar_det_loss_workspace_bytes": "z 3i",
     "vidar_det_loss_fwd_f32": "i 8p 2f 5i p z p",
     "vidar_det_loss_bwd_f32": "i 10p 2f 5i p",
+    "vidar_det_assign_workspace_bytes": "i 4i p",
+    "vidar_det_assign_f32": "i 4p 4i p z p",
     "vidar_det_eval_match_f32": "i 10p 7i p",
     "vidar_ray_eval_workspace_bytes": "i i p",
     "vidar_ray_eval_f64": "i 9p 4i p z p",

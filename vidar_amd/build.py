@@ -37,6 +37,9 @@ PER_FILE: dict[str, list[str]] = {
     "img_prep.hip": ["-ffp-contract=off"],
     # the same for the fp64 ray errors against the reference's numpy (csrc/ray_eval_math.h)
     "ray_eval.hip": ["-ffp-contract=off"],
+    # and for the fp64 duals of the assignment: the host program of the tests must take the same decisions
+    # (csrc/det_assign_math.h)
+    "det_assign.hip": ["-ffp-contract=off"],
 }
 
 

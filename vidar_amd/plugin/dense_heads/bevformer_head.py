@@ -6,6 +6,8 @@ loss_cls / loss_bbox / loss_iou / train_cfg['assigner'], bg_cls_weight 0 for a s
 What changed is the execution plan of the loss, not the math.  On CUDA tensors `loss` packs the ground truth of the batch
 once, builds the Hungarian cost matrices of all decoder layers and samples with one kernel, reads them with ONE host
 copy, and evaluates focal + L1 losses of all layers with one kernel each way (dense_heads/det_ops.py, csrc/det_loss.hip).
+With det_ops.set_assign("device") / VIDAR_DET_ASSIGN=device (off by default) the assignment runs on the device too
+(csrc/det_assign.hip) and that host copy goes: `last_assign_status` keeps the launch's status for whoever reads the loss.
 With VIDAR_DET_LOSS=torch, or on CPU tensors, the reference's own structure runs: loss_single per decoder layer,
 HungarianAssigner3D.assign per (layer, sample) with its blocking copy, FocalLoss and L1Loss modules."""
 from __future__ import annotations
@@ -67,6 +69,7 @@ class BEVFormerHead(nn.Module):
         if loss_cls.get("class_weight") is not None:
             raise NotImplementedError("BEVFormerHead: loss_cls.class_weight")
         self.assigner = None
+        self.last_assign_status = None      # device assignment: status tensor of the most recent loss (det_ops.assign_device)
         if train_cfg:
             assert "assigner" in train_cfg, "assigner should be provided when train_cfg is set."
             assigner = train_cfg["assigner"]
@@ -241,7 +244,9 @@ class BEVFormerHead(nn.Module):
         cost = det_ops.match_cost(all_cls_scores, all_bbox_preds, gt_norm, gt_label, gt_start, total, self.assigner.cls_cost.alpha,
                                   float(self.assigner.cls_cost.gamma), float(self.assigner.cls_cost.weight),
                                   float(self.assigner.reg_cost.weight))
-        matched = det_ops.hungarian(cost, NL, Q, counts)
+        # 'host' (default): det_ops.hungarian, the step's one host read.  'device': csrc/det_assign.hip, no read; the
+        # status of the launch stays on the device until someone asks (det_ops.check_assign_status)
+        matched, self.last_assign_status = det_ops.assign(cost, NL, B, Q, gt_start, counts)
         labels = det_ops.labels_from_matched(matched, gt_label, gt_start, self.num_classes)
         sums = det_ops.det_loss_sums(all_cls_scores, all_bbox_preds, labels, matched, gt_norm, gt_start, self.code_weights,
                                      alpha, gamma)

@@ -3,7 +3,9 @@
 Two implementations of the SAME arithmetic:
   * fused (CUDA tensors, default): csrc/det_loss.hip through ctypes -- `match_cost` is one launch, `hungarian` makes ONE
     pinned non-blocking copy + one event wait for the NL * B cost matrices of a step, `DetLossFunction` is one launch each
-    way; the reductions are deterministic (same inputs, same bits);
+    way; the reductions are deterministic (same inputs, same bits); under `set_assign("device")` / VIDAR_DET_ASSIGN=device
+    (off by default) `assign_device` solves all NL * B problems in one launch of csrc/det_assign.hip and no host read is
+    left in the tail;
   * torch (`*_torch`, CPU tensors, or CUDA with VIDAR_DET_LOSS=torch): the plain composition -- the CPU path of the
     feature, the A/B partner for timing and the second opinion of the GPU tests.
 Ground truth is packed over the batch: gt_box_norm [total_g, 10] (normalize_bbox applied), gt_label [total_g],
@@ -115,6 +117,83 @@ def hungarian(cost, NL, Q, gt_counts):
         host = cost
     matched = solve(host.numpy(), NL, Q, gt_counts)
     return to_device_async(matched, cost.device, torch.int32)
+
+
+# ---- the assignment on the device (csrc/det_assign.hip), off by default ------------------------------------------------
+_ASSIGN_MODES = ("host", "device")
+_ASSIGN = {"mode": None, "warned": False}
+STATUS_MESSAGES = {1: "matrix contains invalid numeric entries", 2: "cost matrix is infeasible",
+                   3: "gt_start does not describe the packed ground truth"}
+
+
+def set_assign(mode):
+    """'host' (scipy behind one cost copy, `hungarian`) or 'device' (`assign_device`, no host read); None hands the choice
+    back to the environment variable VIDAR_DET_ASSIGN (same two values, default 'host')"""
+    if mode is not None and mode not in _ASSIGN_MODES:
+        raise ValueError(f"set_assign({mode!r}): expected 'host' or 'device'")
+    _ASSIGN["mode"] = mode
+
+
+def assign_mode():
+    mode = _ASSIGN["mode"] or os.environ.get("VIDAR_DET_ASSIGN", "host")
+    if mode not in _ASSIGN_MODES:
+        raise ValueError(f"VIDAR_DET_ASSIGN={mode!r}: expected 'host' or 'device'")
+    return mode
+
+
+def assign_supported(NL, B, Q, total_g):
+    """workspace bytes of vidar_det_assign_f32, or None when the extent is beyond the solver's LDS state (host arithmetic)"""
+    import ctypes
+    from ..._lib import lib, check
+    n = ctypes.c_int64(0)
+    check(lib().vidar_det_assign_workspace_bytes(NL, B, Q, int(total_g), ctypes.addressof(n)), "det_assign_workspace_bytes")
+    return None if n.value < 0 else n.value
+
+
+def assign_device(cost, NL, B, Q, gt_start_dev, total_g):
+    """vidar_det_assign_f32: device cost [NL, Q * total_g] -> (matched [NL, B, Q] int32, status [NL * B] int32), both on
+    the device and written completely by the launch (total_g == 0 included).  No host read, no event wait; runs on torch's
+    current stream.  status: 0 solved, else see STATUS_MESSAGES / `check_assign_status`."""
+    from ..._lib import lib, check, ptr, stream_of
+    if not cost.is_cuda:
+        raise RuntimeError("det_ops.assign_device runs on the GPU only (`solve` is the host path)")
+    nbytes = assign_supported(NL, B, Q, total_g)
+    if nbytes is None:
+        raise ValueError(f"det_ops.assign_device: Q {Q} x total_g {total_g} is beyond the supported extent")
+    cost = cost.detach().float().contiguous()
+    assert cost.numel() == NL * Q * total_g and gt_start_dev.dtype == torch.int32 and gt_start_dev.numel() >= B + 1
+    matched = torch.empty((NL, B, Q), device=cost.device, dtype=torch.int32)
+    status = torch.empty((NL * B,), device=cost.device, dtype=torch.int32)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=cost.device) if nbytes else None
+    check(lib().vidar_det_assign_f32(ptr(cost) if cost.numel() else None, ptr(gt_start_dev), ptr(matched) if Q else None,
+                                     ptr(status), NL, B, Q, int(total_g), ptr(ws), nbytes, stream_of(cost)), "det_assign")
+    return matched, status
+
+
+def assign(cost, NL, B, Q, gt_start_dev, gt_counts):
+    """the assignment of a step under the switch -> (matched, status or None).  'device' falls back to the host path, with
+    one warning per process, for an extent the kernel does not hold."""
+    total_g = int(sum(gt_counts))
+    if assign_mode() == "device" and cost.is_cuda:
+        if assign_supported(NL, B, Q, total_g) is not None:
+            return assign_device(cost, NL, B, Q, gt_start_dev, total_g)
+        if not _ASSIGN["warned"]:
+            import warnings
+            _ASSIGN["warned"] = True
+            warnings.warn(f"device assignment: {Q} queries x {total_g} boxes is beyond the supported extent; "
+                          "this and every such step is assigned on the host", RuntimeWarning, stacklevel=2)
+    return hungarian(cost, NL, Q, gt_counts), None
+
+
+def check_assign_status(status):
+    """read a status tensor of `assign_device` (ONE host read: call it where the loss is read anyway, not per step) and
+    raise what scipy.optimize.linear_sum_assignment would have raised for the first problem that was refused"""
+    if status is None:
+        return
+    codes = status.detach().cpu().tolist()
+    for p, code in enumerate(codes):
+        if code:
+            raise ValueError(f"{STATUS_MESSAGES.get(code, f'status {code}')} (assignment problem {p} of {len(codes)})")
 
 
 def labels_from_matched(matched, gt_label, gt_start_dev, num_classes):

@@ -258,13 +258,14 @@ class CosineWithWarmup:
 
 
 def fit(model, optimizer, batches, iters, scheduler=None, max_norm=35.0, log_every=50, log_path=None,
-        ckpt_path=None, ckpt_every=0, rank=0, start_iter=0, freeze_gemm_tuning_after=20):
+        ckpt_path=None, ckpt_every=0, rank=0, start_iter=0, freeze_gemm_tuning_after=20, on_log=None):
     """Thin training loop (the reference delegates this to mmcv's EpochBasedRunner + hooks, which are
     out of scope): `batches` is any iterable of forward_train kwargs; JSON-lines log of the loss
     terms and samples/s; optional periodic checkpoints in the mmcv dictionary layout.  After
     `freeze_gemm_tuning_after` iterations TunableOp stops tuning new GEMM shapes (gemm_tuning.freeze):
     a rank that met a new padded SpatialCrossAttention length later would otherwise tune for seconds
-    while the other ranks wait at the gradient all-reduce."""
+    while the other ranks wait at the gradient all-reduce.  `on_log()` runs where the loss is read for a log line (the host
+    waits for the device there anyway): the place for checks that need a host read, never once per step."""
     import json
     import time
     from .checkpoint import save_checkpoint
@@ -285,6 +286,8 @@ def fit(model, optimizer, batches, iters, scheduler=None, max_norm=35.0, log_eve
                            samples_per_s_per_rank=(it - start_iter) / (time.perf_counter() - t0),
                            **{k: float(v) for k, v in parts.items()})
                 log.write(json.dumps(rec) + "\n"); log.flush()
+                if on_log is not None:
+                    on_log()
             if ckpt_path and ckpt_every and it % ckpt_every == 0 and rank == 0:
                 save_checkpoint(model, ckpt_path, optimizer, meta=dict(iter=it, epoch=0))
             if it >= iters:
