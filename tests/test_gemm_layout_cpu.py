@@ -1,8 +1,8 @@
 """CPU: the thread -> LDS image -> MFMA fragment -> accumulator -> output mapping of csrc/gemm_mfma.hip, restated with
 numpy index arithmetic and checked against A @ B for all four operand layouts and both arithmetic modes.
 
-What is restated (and must be kept in step with the kernel): the staging maps of `load_kmajor` / `load_mnmajor` /
-`store_kmajor` / `store_mnmajor` (which element a thread holds and where it lands in the image), the image geometry
+What is restated (and must be kept in step with the kernel): the staging maps of `load<PREC, LAY>` / `stage<PREC, LAY>`
+for both layouts (which element a thread holds and where it lands in the image), the image geometry
 `Geo<PREC>` (K-major row stride 36 dwords in fp32 mode; 16 dwords with XOR-swizzled 16-byte chunks in bf16 mode;
 136-dword unit rows), `frag()` (units 8s + 4h + {0..3} of a row), the operand
 roles of `v_mfma_f32_32x32x16_bf16` / `v_mfma_f32_32x32x2_f32` (A[i = lane & 31][k = lane >> 5 ...], B[k][j = lane & 31]) and

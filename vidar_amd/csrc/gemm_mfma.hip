@@ -2,7 +2,10 @@
 //
 //   C[z] = epilogue( A[z] (M x K)  *  B[z] (K x N) )        fp32 in HBM on both sides, fp32 accumulate
 //
-// Two arithmetic modes share every line of the tile machinery:
+// Two arithmetic modes share every line of the tile machinery, and every piece of it is written once: a thread's
+// coordinates (Lane), the staging path of an operand by layout (voff / load / stage, stage_pair for both operands), the
+// k-step on the LDS images (mma_step), the epilogue's arithmetic (finish) and its window descriptors (window_rsrc).
+// The modes:
 //   VIDAR_GEMM_F32    v_mfma_f32_32x32x2_f32 : exact fp32 products, one rounding per product (the arithmetic of
 //                     the rocBLAS / hipBLASLt kernels it replaces), 1/16 of the bf16 matrix rate
 //   VIDAR_GEMM_BF16X3 every operand is split while it is staged, x = hi + lo with hi = bf16(x), lo = bf16(x - hi),
@@ -44,6 +47,8 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "vidar_hip.h"
 #include "vidar_common.h"
@@ -96,37 +101,56 @@ struct GemmArgs {
   float* rowsum_ws;     // [Z][M] partial rows (inside the caller's workspace)
 };
 
+// a thread's place in the 2 x 2 waves of a tile: its wave owns rows wm .. wm + 63 and columns wn .. wn + 63 of the tile,
+// the lane is row / column l31 of a 32 x 32 MFMA tile and k half h
+struct Lane {
+  int wm, wn, l31, h;
+  __device__ __forceinline__ Lane(int tid, int wave) : wm((wave >> 1) * 64), wn((wave & 1) * 64), l31(tid & 31), h((tid & 63) >> 5) {}
+  __device__ __forceinline__ explicit Lane(int tid) : Lane(tid, tid >> 6) {}
+  // byte offset of the lane's first accumulator element (row wm + 4h, column wn + l31) in a window of leading dimension ld
+  __device__ __forceinline__ uint32_t voff(uint32_t ld) const { return (uint32_t)(((wm + 4 * h) * ld + wn + l31) * 4); }
+};
+
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][2]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+}
+
 // ---- staging: 16 floats per operand per thread ------------------------------------------------------------------------
-template <int PREC>
 struct Staged {               // the registers a thread holds between its global loads and its LDS writes
   static constexpr int CH = 2;                                // chunks of 8 floats: 16 floats per operand per thread
   f32x4 v[CH][2];
 };
 
-// K-major operand: element (row, k) at P[row * ld + k].  The lanes of a wave instruction run along k first: LPR = BK/4 = 8
-// lanes x 16 bytes cover the whole k-step of one row (one 128-byte line), 8 rows per instruction, so every request is a
-// full contiguous piece (one lane per row, or a pair of
-// lanes 64 bytes apart, made each dwordx4 touch 32 lines in 16-byte pieces: the kernel was bound by the texture
-// addresser, not by MFMA or HBM).  float4 number i of a thread: row 32*wave + i*(64/LPR) + lane/LPR, k (lane%LPR)*4.
-template <int PREC>
-struct KMap {
-  static constexpr int LPR = 8;                                 // lanes per row: 8 x 16 B = the 128-byte k-step of a row
-  static constexpr int RPI = 64 / LPR;                          // rows per instruction
-  static constexpr int NI = 32 / RPI;                           // instructions (float4 per thread)
-};
+// K-major operand: element (row, k) at P[row * ld + k].  The lanes of a wave instruction run along k first: KM_LPR =
+// BK/4 = 8 lanes x 16 bytes cover the whole k-step of one row (one 128-byte line), 8 rows per instruction, so every
+// request is made of whole 128-byte lines.  (The earlier map, one lane per row, made each dwordx4 touch 32 lines in
+// 16-byte pieces: the kernel was bound by the texture addresser, not by MFMA or HBM.)
+// float4 number i of a thread: row 32*wave + i*KM_RPI + lane/KM_LPR, k (lane%KM_LPR)*4.
+constexpr int KM_LPR = 8;                                       // lanes per row: 8 x 16 B = the 128-byte k-step of a row
+constexpr int KM_RPI = 64 / KM_LPR;                             // rows per instruction
+constexpr int KM_NI = 32 / KM_RPI;                              // instructions (float4 per thread)
 
 // Addressing of both loaders: buffer loads through a descriptor whose base is the workgroup's (uniform) tile origin at
 // the first k of its range, ONE 32-bit per-thread byte offset computed before the loop (voffset) and the uniform advance
 // of the k loop in a scalar register (soffset): no vector address arithmetic inside the loop.  The descriptor is built
 // from readfirstlane'd halves of the pointer so that the compiler can see it is uniform (no waterfall loops).
 // The host checks that the offsets fit 31 bits.
-typedef uint32_t raw4 __attribute__((__vector_size__(4 * sizeof(uint32_t))));
-
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* p, int64_t bytes = 0x7fffffff) {
   const uint64_t a = (uint64_t)p;
   const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
   const int32_t n = __builtin_amdgcn_readfirstlane((int32_t)(bytes > 0x7fffffff ? 0x7fffffff : bytes));
   return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), 0, n, 0x00020000);
+}
+// the window of a row-major matrix from `base` to the matrix' last element, rows_left x cols_left elements away (both
+// >= 1); an operand that is not there gets a zero-length descriptor (every load through it returns 0)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t window_rsrc(const float* base, int64_t ld, int rows_left, int cols_left,
+                                                              bool present = true) {
+  return make_rsrc(base, present ? ((int64_t)(rows_left - 1) * ld + cols_left) * 4 : 0);
 }
 __device__ __forceinline__ f32x4 ld16(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
@@ -135,50 +159,49 @@ __device__ __forceinline__ float ld4(__amdgpu_buffer_rsrc_t r, uint32_t voff, ui
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
 
-template <int PREC>
-__device__ __forceinline__ uint32_t voff_kmajor(int64_t ld, int tid) {
-  using M = KMap<PREC>;
-  const int lane = tid & 63, wave = tid >> 6;
-  return (uint32_t)(((32 * wave + lane / M::LPR) * (uint32_t)ld + (lane % M::LPR) * 4) * 4);
-}
-
-// descriptor base = P + row0 * ld + kbeg, ending at the matrix' last element ; krel = k0 - kbeg.
-// No per-lane bounds checks: rows past the matrix only feed output rows that are never stored (and read as 0 past the
-// descriptor's end); a k-step that reaches past K reads the start of the next row, so its lanes are masked -- `tail` is
-// workgroup-uniform and true for at most the last k-step of a product whose K is not a multiple of the k-step.
-template <int PREC>
-__device__ __forceinline__ void load_kmajor(Staged<PREC>& s, __amdgpu_buffer_rsrc_t rs, int64_t ld, int krel, int k0, int kend,
-                                            bool tail, int tid, uint32_t voff) {
-  using M = KMap<PREC>;
-#pragma unroll
-  for (int i = 0; i < M::NI; ++i)
-    s.v[i >> 1][i & 1] = ld16(rs, voff, (uint32_t)((i * M::RPI * (uint32_t)ld + krel) * 4));
-  if (tail) {
-    const int k = k0 + ((tid & 63) % M::LPR) * 4;
-#pragma unroll
-    for (int i = 0; i < M::NI; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s.v[i >> 1][i & 1][j] = (k + j < kend) ? s.v[i >> 1][i & 1][j] : 0.0f;
-  }
-}
-
+// The staging path of an operand, selected by its layout: voff (the thread's byte offset), load (global -> registers),
+// stage (registers -> LDS image).
 // MN-major operand: element (k, col) at P[k * ld + col].  bf16 mode: item = tid + 256c, column quad item&31, k pair
 // item>>5 (two rows of four columns).  fp32 mode: items tid + 256 i, i = 0..3: column quad item&31, k = item>>5.
-template <int PREC>
-__device__ __forceinline__ uint32_t voff_mnmajor(int64_t ld, int tid) {
+template <int PREC, int LAY>
+__device__ __forceinline__ uint32_t voff(int64_t ld, int tid) {
+  if (LAY == LAY_K) {
+    const int lane = tid & 63, wave = tid >> 6;
+    return (uint32_t)(((32 * wave + lane / KM_LPR) * (uint32_t)ld + (lane % KM_LPR) * 4) * 4);
+  }
   const int kr = (PREC == PREC_BF16X3) ? (tid >> 5) * 2 : (tid >> 5);
   return (uint32_t)((kr * (uint32_t)ld + (tid & 31) * 4) * 4);
 }
 
-// descriptor base = P + kbeg * ld + col0, ending at the matrix' last element ; krel = k0 - kbeg.  Rows k >= K lie past the
+// the k-step at k0 = kbeg + krel of a product whose k range ends at kend.
+// K-major: descriptor base = P + row0 * ld + kbeg, ending at the matrix' last element.  No per-lane bounds checks: rows
+// past the matrix only feed output rows that are never stored (and read as 0 past the descriptor's end); a k-step that
+// reaches past kend reads the start of the next row, so its lanes are masked -- `tail` is workgroup-uniform and true
+// for at most the last k-step of a product whose K is not a multiple of the k-step.
+// MN-major: descriptor base = P + kbeg * ld + col0, ending at the matrix' last element.  Rows k >= K lie past the
 // descriptor's end and read as 0 (the k tail needs no mask); columns past the matrix only feed outputs that are never stored.
-template <int PREC>
-__device__ __forceinline__ void load_mnmajor(Staged<PREC>& s, __amdgpu_buffer_rsrc_t rs, int64_t ld, int krel, uint32_t voff) {
+template <int PREC, int LAY>
+__device__ __forceinline__ void load(Staged& s, __amdgpu_buffer_rsrc_t rs, int64_t ld, int krel, int k0, int kend, int tid,
+                                     uint32_t vo) {
+  if (LAY == LAY_K) {
 #pragma unroll
-  for (int i = 0; i < Staged<PREC>::CH * 2; ++i) {
-    // uniform k of this load relative to the thread's own row: bf16 mode 16*(i>>1) + (i&1), fp32 mode 8*i
-    const int ku = (PREC == PREC_BF16X3) ? 16 * (i >> 1) + (i & 1) : 8 * i;       // i = 0..3 in both modes
-    s.v[i >> 1][i & 1] = ld16(rs, voff, (uint32_t)(krel + ku) * (uint32_t)ld * 4u);
+    for (int i = 0; i < KM_NI; ++i)
+      s.v[i >> 1][i & 1] = ld16(rs, vo, (uint32_t)((i * KM_RPI * (uint32_t)ld + krel) * 4));
+    const bool tail = k0 + BK > kend;
+    if (tail) {
+      const int k = k0 + ((tid & 63) % KM_LPR) * 4;
+#pragma unroll
+      for (int i = 0; i < KM_NI; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s.v[i >> 1][i & 1][j] = (k + j < kend) ? s.v[i >> 1][i & 1][j] : 0.0f;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < Staged::CH * 2; ++i) {
+      // uniform k of this load relative to the thread's own row: bf16 mode 16*(i>>1) + (i&1), fp32 mode 8*i
+      const int ku = (PREC == PREC_BF16X3) ? 16 * (i >> 1) + (i & 1) : 8 * i;       // i = 0..3 in both modes
+      s.v[i >> 1][i & 1] = ld16(rs, vo, (uint32_t)(krel + ku) * (uint32_t)ld * 4u);
+    }
   }
 }
 
@@ -193,31 +216,27 @@ __device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t&
 }
 
 // LDS writes.  `img` = the operand's image (bf16 mode: hi at img, lo at img + IMG_DWORDS).
-template <int PREC>
-__device__ __forceinline__ void store_kmajor(const Staged<PREC>& s, uint32_t* img, int tid) {
-  using M = KMap<PREC>;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int r0 = 32 * wave + lane / M::LPR, kq = lane % M::LPR;
+template <int PREC, int LAY>
+__device__ __forceinline__ void stage(const Staged& s, uint32_t* img, int tid) {
+  if (LAY == LAY_K) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const int r0 = 32 * wave + lane / KM_LPR, kq = lane % KM_LPR;
 #pragma unroll
-  for (int i = 0; i < M::NI; ++i) {
-    const int r = r0 + i * M::RPI;
-    const f32x4 v = s.v[i >> 1][i & 1];
-    if (PREC == PREC_BF16X3) {             // four k -> two units (k pairs) of hi and of lo
-      uint32_t h0, l0, h1, l1;
-      split2(v[0], v[1], h0, l0);
-      split2(v[2], v[3], h1, l1);
-      const int pos = r * Geo<PREC>::KM_STRIDE + ((((kq >> 1) ^ ((r >> 2) & 3)) << 2) | ((kq & 1) << 1));
-      *(u32x2*)(img + pos) = u32x2{h0, h1};
-      *(u32x2*)(img + Geo<PREC>::IMG_DWORDS + pos) = u32x2{l0, l1};
-    } else {                               // (stored as dwords, the type every fragment read uses)
-      *(u32x4*)(img + r * Geo<PREC>::KM_STRIDE + 4 * kq) = __builtin_bit_cast(u32x4, v);
+    for (int i = 0; i < KM_NI; ++i) {
+      const int r = r0 + i * KM_RPI;
+      const f32x4 v = s.v[i >> 1][i & 1];
+      if (PREC == PREC_BF16X3) {             // four k -> two units (k pairs) of hi and of lo
+        uint32_t h0, l0, h1, l1;
+        split2(v[0], v[1], h0, l0);
+        split2(v[2], v[3], h1, l1);
+        const int pos = r * Geo<PREC>::KM_STRIDE + ((((kq >> 1) ^ ((r >> 2) & 3)) << 2) | ((kq & 1) << 1));
+        *(u32x2*)(img + pos) = u32x2{h0, h1};
+        *(u32x2*)(img + Geo<PREC>::IMG_DWORDS + pos) = u32x2{l0, l1};
+      } else {                               // (stored as dwords, the type every fragment read uses)
+        *(u32x4*)(img + r * Geo<PREC>::KM_STRIDE + 4 * kq) = __builtin_bit_cast(u32x4, v);
+      }
     }
-  }
-}
-
-template <int PREC>
-__device__ __forceinline__ void store_mnmajor(const Staged<PREC>& s, uint32_t* img, int tid) {
-  if (PREC == PREC_BF16X3) {
+  } else if (PREC == PREC_BF16X3) {
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       const int item = tid + 256 * c;
@@ -239,6 +258,11 @@ __device__ __forceinline__ void store_mnmajor(const Staged<PREC>& s, uint32_t* i
       *(u32x4*)(img + (item >> 5) * MN_STRIDE + (item & 31) * 4) = __builtin_bit_cast(u32x4, s.v[i >> 1][i & 1]);
     }
   }
+}
+template <int PREC, int ALAY, int BLAY>
+__device__ __forceinline__ void stage_pair(const Staged& sa, const Staged& sb, uint32_t* imgA, uint32_t* imgB, int tid) {
+  stage<PREC, ALAY>(sa, imgA, tid);
+  stage<PREC, BLAY>(sb, imgB, tid);
 }
 
 // a lane's fragment of row `row` (0..127 inside the tile) for sub-step s: units 8s + 4h + {0..3}
@@ -285,25 +309,21 @@ __device__ __forceinline__ Tile decode_tile(const GemmArgs& g, int t) {
   T.kend = min(g.K, T.kbeg + g.k_chunk);
   const float* A = g.A + (int64_t)T.batch * g.sA;
   const float* B = g.B + (int64_t)T.batch * g.sB;
-  // descriptors: from the tile's first element to the operand's last one (bytes)
-  const int64_t kleft = g.K - T.kbeg;
-  T.rsA = ALAY == LAY_K ? make_rsrc(A + (int64_t)T.m0 * g.lda + T.kbeg, ((int64_t)(g.M - 1 - T.m0) * g.lda + kleft) * 4)
-                        : make_rsrc(A + (int64_t)T.kbeg * g.lda + T.m0, ((kleft - 1) * g.lda + (g.M - T.m0)) * 4);
-  T.rsB = BLAY == LAY_K ? make_rsrc(B + (int64_t)T.n0 * g.ldb + T.kbeg, ((int64_t)(g.N - 1 - T.n0) * g.ldb + kleft) * 4)
-                        : make_rsrc(B + (int64_t)T.kbeg * g.ldb + T.n0, ((kleft - 1) * g.ldb + (g.N - T.n0)) * 4);
+  // descriptors: from the tile's first element to the operand's last one
+  const int kleft = g.K - T.kbeg;
+  T.rsA = ALAY == LAY_K ? window_rsrc(A + (int64_t)T.m0 * g.lda + T.kbeg, g.lda, g.M - T.m0, kleft)
+                        : window_rsrc(A + (int64_t)T.kbeg * g.lda + T.m0, g.lda, kleft, g.M - T.m0);
+  T.rsB = BLAY == LAY_K ? window_rsrc(B + (int64_t)T.n0 * g.ldb + T.kbeg, g.ldb, g.N - T.n0, kleft)
+                        : window_rsrc(B + (int64_t)T.kbeg * g.ldb + T.n0, g.ldb, kleft, g.N - T.n0);
   return T;
 }
 
 // global loads of the k-step starting at k0 of tile T into the staging registers
 template <int PREC, int ALAY, int BLAY>
-__device__ __forceinline__ void fetch(Staged<PREC>& sa, Staged<PREC>& sb, const GemmArgs& g, const Tile& T, int k0, int tid,
-                                      uint32_t voa, uint32_t vob) {
-  const int krel = k0 - T.kbeg;
-  const bool tail = k0 + BK > T.kend;
-  if (ALAY == LAY_K) load_kmajor<PREC>(sa, T.rsA, g.lda, krel, k0, T.kend, tail, tid, voa);
-  else load_mnmajor<PREC>(sa, T.rsA, g.lda, krel, voa);
-  if (BLAY == LAY_K) load_kmajor<PREC>(sb, T.rsB, g.ldb, krel, k0, T.kend, tail, tid, vob);
-  else load_mnmajor<PREC>(sb, T.rsB, g.ldb, krel, vob);
+__device__ __forceinline__ void fetch(Staged& sa, Staged& sb, const GemmArgs& g, const Tile& T, int k0, int tid, uint32_t voa,
+                                      uint32_t vob) {
+  load<PREC, ALAY>(sa, T.rsA, g.lda, k0 - T.kbeg, k0, T.kend, tid, voa);
+  load<PREC, BLAY>(sb, T.rsB, g.ldb, k0 - T.kbeg, k0, T.kend, tid, vob);
 }
 
 // sum over the staged k of a thread's A values, per row of its row quad (MN-major staging: every float4 of a thread is
@@ -312,68 +332,78 @@ __device__ __forceinline__ void fetch(Staged<PREC>& sa, Staged<PREC>& sb, const 
 // so the components of rows >= M hold garbage (possibly Inf / NaN).  Every row is its own vector component and the
 // store's `cur.m0 + tid < g.M` guard drops those components: that guard is load-bearing
 // (tests/test_gemm_gpu.py::test_rowsum_with_ragged_rows).  Buffer loads need dword alignment only (no 16-byte rule).
-template <int PREC>
-__device__ __forceinline__ void add_rowsum(f32x4& rs, const Staged<PREC>& sa) {
+__device__ __forceinline__ void add_rowsum(f32x4& rs, const Staged& sa) {
 #pragma unroll
-  for (int i = 0; i < Staged<PREC>::CH * 2; ++i) rs += sa.v[i >> 1][i & 1];
+  for (int i = 0; i < Staged::CH * 2; ++i) rs += sa.v[i >> 1][i & 1];
+}
+
+// one k-step of a wave's 64 x 64 part of the tile on the operand images: per sub-step s the fragment reads, then the MFMAs
+template <int PREC, int ALAY, int BLAY>
+__device__ __forceinline__ void mma_step(f32x16 (&acc)[2][2], const uint32_t* imgA, const uint32_t* imgB, const Lane& c) {
+  constexpr int IMGS = (PREC == PREC_BF16X3) ? 2 : 1;
+  constexpr int IMG_DWORDS = Geo<PREC>::IMG_DWORDS;
+#pragma unroll
+  for (int s = 0; s < Geo<PREC>::NS; ++s) {
+    u32x4 fa[2][IMGS], fb[2][IMGS];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int p = 0; p < IMGS; ++p) {
+        fa[i][p] = frag<PREC, ALAY>(imgA + p * IMG_DWORDS, c.wm + 32 * i + c.l31, s, c.h);
+        fb[i][p] = frag<PREC, BLAY>(imgB + p * IMG_DWORDS, c.wn + 32 * i + c.l31, s, c.h);
+      }
+    if (PREC == PREC_BF16X3) {
+      // term-major order: the four accumulators of the wave take turns, so the three dependent MFMAs of one
+      // accumulator (lo*hi, hi*lo, hi*hi) are four issues apart instead of back to back
+#pragma unroll
+      for (int term = 0; term < 3; ++term)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const bf16x8 a = __builtin_bit_cast(bf16x8, fa[i][term == 0 ? IMGS - 1 : 0]);
+            const bf16x8 b = __builtin_bit_cast(bf16x8, fb[j][term == 1 ? IMGS - 1 : 0]);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[i][j], 0, 0, 0);
+          }
+    } else {
+      // (`__builtin_bit_cast(float, vec[u])` on a vector ELEMENT folds every u to element 0 on ROCm 7.2: cast the vector)
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const f32x4 bf = __builtin_bit_cast(f32x4, fb[j][0]), af = __builtin_bit_cast(f32x4, fa[i][0]);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[u], bf[u], acc[i][j], 0, 0, 0);
+          }
+    }
+  }
 }
 
 // the k loop of one tile, k-steps [T.kbeg, kstop).  On entry the staging registers hold (or are about to receive) the
 // tile's first k-step; a step requests its successor while that lies inside the TILE (k0 + BK < T.kend), so with
 // kstop < T.kend the loop leaves the staging registers holding the first k-step it did not run.
 template <int PREC, int ALAY, int BLAY>
-__device__ __forceinline__ void mainloop(f32x16 (&acc)[2][2], Staged<PREC>& sa, Staged<PREC>& sb, const GemmArgs& g,
-                                         const Tile& T, int kstop, uint32_t* imgA, uint32_t* imgB, int tid, uint32_t voa,
-                                         uint32_t vob, f32x4& rowsum, bool want_rowsum) {
-  constexpr int IMGS = (PREC == PREC_BF16X3) ? 2 : 1;
-  constexpr int IMG_DWORDS = Geo<PREC>::IMG_DWORDS;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-  const int l31 = lane & 31, h = lane >> 5;
+__device__ __forceinline__ void mainloop(f32x16 (&acc)[2][2], Staged& sa, Staged& sb, const GemmArgs& g, const Tile& T,
+                                         int kstop, uint32_t* imgA, uint32_t* imgB, int tid, uint32_t voa, uint32_t vob,
+                                         f32x4& rowsum, bool want_rowsum) {
+  const Lane c(tid);
   for (int k0 = T.kbeg; k0 < kstop; k0 += BK) {
-    if (ALAY == LAY_MN && want_rowsum) add_rowsum<PREC>(rowsum, sa);
-    if (ALAY == LAY_K) store_kmajor<PREC>(sa, imgA, tid); else store_mnmajor<PREC>(sa, imgA, tid);
-    if (BLAY == LAY_K) store_kmajor<PREC>(sb, imgB, tid); else store_mnmajor<PREC>(sb, imgB, tid);
+    if (ALAY == LAY_MN && want_rowsum) add_rowsum(rowsum, sa);
+    stage_pair<PREC, ALAY, BLAY>(sa, sb, imgA, imgB, tid);
     __syncthreads();
     if (k0 + BK < T.kend) fetch<PREC, ALAY, BLAY>(sa, sb, g, T, k0 + BK, tid, voa, vob);   // in flight under the MFMAs below
-#pragma unroll
-    for (int s = 0; s < Geo<PREC>::NS; ++s) {
-      u32x4 fa[2][IMGS], fb[2][IMGS];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int p = 0; p < IMGS; ++p) {
-          fa[i][p] = frag<PREC, ALAY>(imgA + p * IMG_DWORDS, wm + 32 * i + l31, s, h);
-          fb[i][p] = frag<PREC, BLAY>(imgB + p * IMG_DWORDS, wn + 32 * i + l31, s, h);
-        }
-      if (PREC == PREC_BF16X3) {
-        // term-major order: the four accumulators of the wave take turns, so the three dependent MFMAs of one
-        // accumulator (lo*hi, hi*lo, hi*hi) are four issues apart instead of back to back
-#pragma unroll
-        for (int term = 0; term < 3; ++term)
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-              const bf16x8 a = __builtin_bit_cast(bf16x8, fa[i][term == 0 ? IMGS - 1 : 0]);
-              const bf16x8 b = __builtin_bit_cast(bf16x8, fb[j][term == 1 ? IMGS - 1 : 0]);
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[i][j], 0, 0, 0);
-            }
-      } else {
-        // (`__builtin_bit_cast(float, vec[u])` on a vector ELEMENT folds every u to element 0 on ROCm 7.2: cast the vector)
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-              const f32x4 bf = __builtin_bit_cast(f32x4, fb[j][0]), af = __builtin_bit_cast(f32x4, fa[i][0]);
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[u], bf[u], acc[i][j], 0, 0, 0);
-            }
-      }
-    }
+    mma_step<PREC, ALAY, BLAY>(acc, imgA, imgB, c);
     __syncthreads();
   }
+}
+
+// y = relu?( acc * scale + shift + residual ): THE arithmetic of every epilogue of this file (-ffp-contract=off: each
+// operation rounds on its own, so the three users give the same bits).  A missing operand is sc = 1 / sh = 0 / rs = 0.
+__device__ __forceinline__ float finish(float acc, float sc, float sh, float rs, int relu) {
+  float y = acc * sc + sh + rs;
+  if (relu && !(y > 0.0f)) y = 0.0f;
+  return y;
 }
 
 // epilogue of one tile: accumulator register r of MFMA tile (i, j) is row m = m0 + wm + 32i + (r&3) + 8(r>>2) + 4h, column
@@ -384,9 +414,7 @@ __device__ __forceinline__ void mainloop(f32x16 (&acc)[2][2], Staged<PREC>& sa, 
 // by an explicit row predicate; the column test n < N is made once per column tile.
 template <bool RAGGED_M>
 __device__ __forceinline__ void epilogue_impl(const f32x16 (&acc)[2][2], const GemmArgs& g, const Tile& T, int tid) {
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-  const int l31 = lane & 31, h = lane >> 5;
+  const Lane c(tid);
   const int m0 = T.m0, n0 = T.n0;
   float* C; int64_t ldc;
   if (g.slabs) { C = g.C + (int64_t)T.z * g.M * g.N; ldc = g.N; }
@@ -394,20 +422,20 @@ __device__ __forceinline__ void epilogue_impl(const f32x16 (&acc)[2][2], const G
   const bool epi = !g.slabs;
   const bool by_n = epi && g.vec_axis == 0, by_m = epi && g.vec_axis == 1;
   const int rows_left = g.M - m0, cols_left = g.N - n0;                      // >= 1
-  const int mleft = rows_left - wm - 4 * h;                                  // rows of this lane's part of the tile inside M
-  const __amdgpu_buffer_rsrc_t rsC = make_rsrc(C + (int64_t)m0 * ldc + n0, ((int64_t)(rows_left - 1) * ldc + cols_left) * 4);
-  const uint32_t voC = (uint32_t)(((wm + 4 * h) * (uint32_t)ldc + wn + l31) * 4);
+  const int mleft = rows_left - c.wm - 4 * c.h;                              // rows of this lane's part of the tile inside M
+  const __amdgpu_buffer_rsrc_t rsC = window_rsrc(C + (int64_t)m0 * ldc + n0, ldc, rows_left, cols_left);
+  const uint32_t voC = c.voff((uint32_t)ldc);
   const bool has_res = epi && g.residual != nullptr;
   const float* Rp = has_res ? g.residual + (int64_t)T.batch * g.sR + (int64_t)m0 * g.ldr + n0 : C;
-  const __amdgpu_buffer_rsrc_t rsR = make_rsrc(Rp, has_res ? ((int64_t)(rows_left - 1) * g.ldr + cols_left) * 4 : 0);
-  const uint32_t voR = (uint32_t)(((wm + 4 * h) * (uint32_t)g.ldr + wn + l31) * 4);
+  const __amdgpu_buffer_rsrc_t rsR = window_rsrc(Rp, g.ldr, rows_left, cols_left, has_res);
+  const uint32_t voR = c.voff((uint32_t)g.ldr);
   const bool m_scale = by_m && g.scale != nullptr, m_shift = by_m && g.shift != nullptr;
   const __amdgpu_buffer_rsrc_t rsS = make_rsrc(m_scale ? g.scale + m0 : C, m_scale ? (int64_t)rows_left * 4 : 0);
   const __amdgpu_buffer_rsrc_t rsH = make_rsrc(m_shift ? g.shift + m0 : C, m_shift ? (int64_t)rows_left * 4 : 0);
-  const uint32_t voM = (uint32_t)((wm + 4 * h) * 4);
+  const uint32_t voM = (uint32_t)((c.wm + 4 * c.h) * 4);
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int n = n0 + wn + 32 * j + l31;
+    const int n = n0 + c.wn + 32 * j + c.l31;
     if (n >= g.N) continue;
     float sn = 1.0f, bn = 0.0f;
     if (by_n && g.scale) sn = g.scale[n];
@@ -428,10 +456,7 @@ __device__ __forceinline__ void epilogue_impl(const f32x16 (&acc)[2][2], const G
         for (int r = 0; r < 8; ++r) {
           const int row = 32 * i + (r & 3) + 8 * ((r0 + r) >> 2);
           float y = acc[i][j][r0 + r];
-          if (epi) {
-            y = y * sc[r] + sh[r] + rs[r];
-            if (g.relu && !(y > 0.0f)) y = 0.0f;
-          }
+          if (epi) y = finish(y, sc[r], sh[r], rs[r], g.relu);
           // rows >= M (only a tile of the last tile row has any: RAGGED_M): an explicit predicate on top of the
           // descriptor's range check (the row part of the offset is a scalar offset, which the hardware only checks
           // through the gfx9 rule num_records - soffset).  Full tiles keep the bare store burst -- the predicate's
@@ -490,10 +515,9 @@ __device__ __forceinline__ float table_value(const GemmArgs& g, const Tile& T, i
 
 // the step's operands and the tile's table value: staging registers -> LDS
 template <int ALAY, int BLAY>
-__device__ __forceinline__ void last_step_stage(const Staged<PREC_F32>& sa, const Staged<PREC_F32>& sb, uint32_t* imgA,
-                                                uint32_t* imgB, float* tab, float tabv, int tid) {
-  if (ALAY == LAY_K) store_kmajor<PREC_F32>(sa, imgA, tid); else store_mnmajor<PREC_F32>(sa, imgA, tid);
-  if (BLAY == LAY_K) store_kmajor<PREC_F32>(sb, imgB, tid); else store_mnmajor<PREC_F32>(sb, imgB, tid);
+__device__ __forceinline__ void last_step_stage(const Staged& sa, const Staged& sb, uint32_t* imgA, uint32_t* imgB,
+                                                float* tab, float tabv, int tid) {
+  stage_pair<PREC_F32, ALAY, BLAY>(sa, sb, imgA, imgB, tid);
   tab[tid] = tabv;
   __syncthreads();
 }
@@ -507,25 +531,21 @@ __device__ __forceinline__ void last_step_piped(f32x16 (&acc)[2][2], const GemmA
   // thread id makes them this function's own, recomputed per tile
   int tid = tid0;
   asm volatile("" : "+v"(tid));
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-  const int l31 = lane & 31, h = lane >> 5;
+  const Lane c(tid);
   // descriptors of the tile's own 128 x 128 window of C and of the residual
-  const __amdgpu_buffer_rsrc_t rsC = make_rsrc(g.C + (int64_t)T.batch * g.sC + (int64_t)T.m0 * g.ldc + T.n0,
-                                               ((int64_t)(BM - 1) * g.ldc + BN) * 4);
+  const __amdgpu_buffer_rsrc_t rsC =
+      window_rsrc(g.C + (int64_t)T.batch * g.sC + (int64_t)T.m0 * g.ldc + T.n0, g.ldc, BM, BN);
   const uint32_t ldc = (uint32_t)g.ldc, ldr = (uint32_t)g.ldr;
-  const uint32_t voC = (uint32_t)(((wm + 4 * h) * ldc + wn + l31) * 4);
+  const uint32_t voC = c.voff(ldc);
   const bool has_res = g.residual != nullptr;
-  const __amdgpu_buffer_rsrc_t rsR =
-      make_rsrc(has_res ? g.residual + (int64_t)T.batch * g.sR + (int64_t)T.m0 * g.ldr + T.n0 : g.C,
-                has_res ? ((int64_t)(BM - 1) * g.ldr + BN) * 4 : 0);
-  const uint32_t voR = (uint32_t)(((wm + 4 * h) * ldr + wn + l31) * 4), voRz = has_res ? voR : 0u;
+  const __amdgpu_buffer_rsrc_t rsR = window_rsrc(
+      has_res ? g.residual + (int64_t)T.batch * g.sR + (int64_t)T.m0 * g.ldr + T.n0 : g.C, g.ldr, BM, BN, has_res);
+  const uint32_t voRz = has_res ? c.voff(ldr) : 0u;
   // without a residual every load must miss the zero-length descriptor and return 0: the range check subtracts the
   // scalar offset from the length first, so the scalar offset has to be 0 then
   const uint32_t rb = has_res ? 4u : 0u;
-  const float* tsc = tab + wm + 4 * h;
+  const float* tsc = tab + c.wm + 4 * c.h;
   const float* tsh = tsc + BM;
-  const bool relu = g.relu != 0;
   float rs[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) rs[r] = ld4(rsR, voRz, (uint32_t)((((r & 3) + 8 * (r >> 2)) * ldr) * rb));
@@ -543,8 +563,8 @@ __device__ __forceinline__ void last_step_piped(f32x16 (&acc)[2][2], const GemmA
     for (int s = 0; s < 4; ++s) {
       f32x4 af = {0.f, 0.f, 0.f, 0.f}, bf = af;
       if (sub < 4) {
-        af = __builtin_bit_cast(f32x4, frag<PREC, ALAY>(imgA, wm + 32 * i + l31, s, h));
-        bf = __builtin_bit_cast(f32x4, frag<PREC, BLAY>(imgB, wn + 32 * j + l31, s, h));
+        af = __builtin_bit_cast(f32x4, frag<PREC, ALAY>(imgA, c.wm + 32 * i + c.l31, s, c.h));
+        bf = __builtin_bit_cast(f32x4, frag<PREC, BLAY>(imgB, c.wn + 32 * j + c.l31, s, c.h));
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -552,8 +572,7 @@ __device__ __forceinline__ void last_step_piped(f32x16 (&acc)[2][2], const GemmA
         if (sub > 0) {
           const int r = 4 * s + u;
           const int prow = 32 * pi + 8 * s + u;                 // uniform part of the row inside the wave's tile
-          float y = acc[pi][pj][r] * tsc[prow] + tsh[prow] + rs[r];
-          if (relu && !(y > 0.0f)) y = 0.0f;
+          const float y = finish(acc[pi][pj][r], tsc[prow], tsh[prow], rs[r], g.relu);
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, y), rsC, voC, (uint32_t)((prow * ldc + 32 * pj) * 4), 0);
           if (sub < 4) rs[r] = ld4(rsR, voRz, (uint32_t)(((32 * i + 8 * s + u) * ldr + 32 * j) * rb));
         }
@@ -577,21 +596,15 @@ __global__ __launch_bounds__(THREADS, 3) void gemm_mfma_kernel(GemmArgs g) {
   uint32_t* imgA = lds;
   uint32_t* imgB = lds + IMGS * Geo<PREC>::IMG_DWORDS;
   const int tid = threadIdx.x;
-  const uint32_t voa = ALAY == LAY_K ? voff_kmajor<PREC>(g.lda, tid) : voff_mnmajor<PREC>(g.lda, tid);
-  const uint32_t vob = BLAY == LAY_K ? voff_kmajor<PREC>(g.ldb, tid) : voff_mnmajor<PREC>(g.ldb, tid);
-  Staged<PREC> sa, sb;
+  const uint32_t voa = voff<PREC, ALAY>(g.lda, tid), vob = voff<PREC, BLAY>(g.ldb, tid);
+  Staged sa, sb;
   int t = blockIdx.x;
   if (t >= g.total) return;
   Tile cur = decode_tile<PREC, ALAY, BLAY>(g, t);
   if (cur.kbeg < cur.kend) fetch<PREC, ALAY, BLAY>(sa, sb, g, cur, cur.kbeg, tid, voa, vob);
   for (int parity = 0;; parity ^= 1) {
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    zero_acc(acc);
     f32x4 rowsum = {0.f, 0.f, 0.f, 0.f};
     const bool want_rowsum = ALAY == LAY_MN && g.a_rowsum != nullptr && cur.n0 == 0;     // workgroup-uniform
     const int tn = t + (int)gridDim.x;
@@ -693,9 +706,8 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_mfma_ws_kernel(GemmArgs g)
   if (wave >= 4) {
     // ------------------------------------------------ producers ------------------------------------------------
     const int ptid = tid - 256;
-    const uint32_t voa = ALAY == LAY_K ? voff_kmajor<PREC>(g.lda, ptid) : voff_mnmajor<PREC>(g.lda, ptid);
-    const uint32_t vob = BLAY == LAY_K ? voff_kmajor<PREC>(g.ldb, ptid) : voff_mnmajor<PREC>(g.ldb, ptid);
-    Staged<PREC> sa0, sb0, sa1, sb1;
+    const uint32_t voa = voff<PREC, ALAY>(g.lda, ptid), vob = voff<PREC, BLAY>(g.ldb, ptid);
+    Staged sa0, sb0, sa1, sb1;
     Cursor<PREC, ALAY, BLAY> rd;                       // next k-step to REQUEST
     rd.start(g, (int)blockIdx.x);
     // how many k-steps this workgroup owns in total (= barriers both roles execute)
@@ -704,80 +716,36 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_mfma_ws_kernel(GemmArgs g)
       const Tile T = decode_tile<PREC, ALAY, BLAY>(g, t);
       steps += (T.kend > T.kbeg) ? (T.kend - T.kbeg + BK - 1) / BK : 0;
     }
-    if (rd.valid(g)) { fetch<PREC, ALAY, BLAY>(sa0, sb0, g, rd.T, rd.k0, ptid, voa, vob); rd.advance(g); }
-    if (rd.valid(g)) { fetch<PREC, ALAY, BLAY>(sa1, sb1, g, rd.T, rd.k0, ptid, voa, vob); rd.advance(g); }
+    const auto request = [&](Staged& sa, Staged& sb) {
+      if (rd.valid(g)) { fetch<PREC, ALAY, BLAY>(sa, sb, g, rd.T, rd.k0, ptid, voa, vob); rd.advance(g); }
+    };
+    // a register set goes to its stage of the ring and is requested again, two k-steps ahead
+    const auto produce = [&](Staged& sa, Staged& sb, int slot) {
+      uint32_t* imgA = lds + slot * STAGE_DWORDS;
+      stage_pair<PREC, ALAY, BLAY>(sa, sb, imgA, imgA + IMGS * IMG_DWORDS, ptid);
+      request(sa, sb);
+      lds_barrier();
+    };
+    request(sa0, sb0);
+    request(sa1, sb1);
     for (int gs = 0; gs < steps; gs += 2) {
-      {
-        uint32_t* imgA = lds;
-        uint32_t* imgB = lds + IMGS * IMG_DWORDS;
-        if (ALAY == LAY_K) store_kmajor<PREC>(sa0, imgA, ptid); else store_mnmajor<PREC>(sa0, imgA, ptid);
-        if (BLAY == LAY_K) store_kmajor<PREC>(sb0, imgB, ptid); else store_mnmajor<PREC>(sb0, imgB, ptid);
-        if (rd.valid(g)) { fetch<PREC, ALAY, BLAY>(sa0, sb0, g, rd.T, rd.k0, ptid, voa, vob); rd.advance(g); }
-        lds_barrier();
-      }
-      if (gs + 1 < steps) {
-        uint32_t* imgA = lds + STAGE_DWORDS;
-        uint32_t* imgB = lds + STAGE_DWORDS + IMGS * IMG_DWORDS;
-        if (ALAY == LAY_K) store_kmajor<PREC>(sa1, imgA, ptid); else store_mnmajor<PREC>(sa1, imgA, ptid);
-        if (BLAY == LAY_K) store_kmajor<PREC>(sb1, imgB, ptid); else store_mnmajor<PREC>(sb1, imgB, ptid);
-        if (rd.valid(g)) { fetch<PREC, ALAY, BLAY>(sa1, sb1, g, rd.T, rd.k0, ptid, voa, vob); rd.advance(g); }
-        lds_barrier();
-      }
+      produce(sa0, sb0, 0);
+      if (gs + 1 < steps) produce(sa1, sb1, 1);
     }
     return;
   }
 
   // ---------------------------------------------------- consumers ----------------------------------------------------
-  const int lane = tid & 63;
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-  const int l31 = lane & 31, h = lane >> 5;
+  const Lane c(tid, wave);
   int gs = 0;                                            // flat k-step counter: stage = gs & 1
   for (int t = (int)blockIdx.x; t < g.total; t += (int)gridDim.x) {
     const Tile T = decode_tile<PREC, ALAY, BLAY>(g, t);
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    zero_acc(acc);
     for (int k0 = T.kbeg; k0 < T.kend; k0 += BK, ++gs) {
       lds_barrier();
       const uint32_t* imgA = lds + (gs & 1) * STAGE_DWORDS;
-      const uint32_t* imgB = imgA + IMGS * IMG_DWORDS;
-#pragma unroll
-      for (int s = 0; s < Geo<PREC>::NS; ++s) {
-        u32x4 fa[2][IMGS], fb[2][IMGS];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int p = 0; p < IMGS; ++p) {
-            fa[i][p] = frag<PREC, ALAY>(imgA + p * IMG_DWORDS, wm + 32 * i + l31, s, h);
-            fb[i][p] = frag<PREC, BLAY>(imgB + p * IMG_DWORDS, wn + 32 * i + l31, s, h);
-          }
-        if (PREC == PREC_BF16X3) {
-#pragma unroll
-          for (int term = 0; term < 3; ++term)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-              for (int j = 0; j < 2; ++j) {
-                const bf16x8 a = __builtin_bit_cast(bf16x8, fa[i][term == 0 ? IMGS - 1 : 0]);
-                const bf16x8 b = __builtin_bit_cast(bf16x8, fb[j][term == 1 ? IMGS - 1 : 0]);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[i][j], 0, 0, 0);
-              }
-        } else {
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-              for (int j = 0; j < 2; ++j) {
-                const f32x4 bf = __builtin_bit_cast(f32x4, fb[j][0]), af = __builtin_bit_cast(f32x4, fa[i][0]);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[u], bf[u], acc[i][j], 0, 0, 0);
-              }
-        }
-      }
+      mma_step<PREC, ALAY, BLAY>(acc, imgA, imgA + IMGS * IMG_DWORDS, c);
     }
     epilogue(acc, g, T, tid);
   }
@@ -821,21 +789,12 @@ __global__ __launch_bounds__(256) void gemm_slab_reduce_kernel(const float* __re
         const int64_t idx = 4 * q + e;
         const int m = (int)(idx / g.N), n = (int)(idx - (int64_t)m * g.N);
         const int vi = g.vec_axis == 1 ? m : n;
-        float y = sum[e] * (g.scale ? g.scale[vi] : 1.0f) + (g.shift ? g.shift[vi] : 0.0f);
-        if (g.residual) y += g.residual[(int64_t)m * g.ldr + n];
-        g.C[(int64_t)m * g.ldc + n] = (g.relu && !(y > 0.0f)) ? 0.0f : y;
+        g.C[(int64_t)m * g.ldc + n] = finish(sum[e], g.scale ? g.scale[vi] : 1.0f, g.shift ? g.shift[vi] : 0.0f,
+                                             g.residual ? g.residual[(int64_t)m * g.ldr + n] : 0.0f, g.relu);
       }
     }
     __syncthreads();
   }
-}
-
-template <int PREC>
-void launch_ws(const GemmArgs& g, int a_layout, int b_layout, dim3 grid, hipStream_t st) {
-  if (a_layout == LAY_K && b_layout == LAY_K) hipLaunchKernelGGL((gemm_mfma_ws_kernel<PREC, LAY_K, LAY_K>), grid, dim3(WS_THREADS), 0, st, g);
-  else if (a_layout == LAY_K) hipLaunchKernelGGL((gemm_mfma_ws_kernel<PREC, LAY_K, LAY_MN>), grid, dim3(WS_THREADS), 0, st, g);
-  else if (b_layout == LAY_K) hipLaunchKernelGGL((gemm_mfma_ws_kernel<PREC, LAY_MN, LAY_K>), grid, dim3(WS_THREADS), 0, st, g);
-  else hipLaunchKernelGGL((gemm_mfma_ws_kernel<PREC, LAY_MN, LAY_MN>), grid, dim3(WS_THREADS), 0, st, g);
 }
 
 // 0 (default): every wave does every job (round 4); 1 / 2: wave-specialised producer / consumer workgroups, one /
@@ -844,12 +803,23 @@ void launch_ws(const GemmArgs& g, int a_layout, int b_layout, dim3 grid, hipStre
 // per-k-step LDS + split work that both forms share, not by the overlap structure.  Kept as the A/B it is.
 int g_gemm_variant = 0;
 
+template <class F>
+void with_layouts(int a_layout, int b_layout, F f) {
+  using K = std::integral_constant<int, LAY_K>;
+  using MN = std::integral_constant<int, LAY_MN>;
+  if (a_layout == LAY_K && b_layout == LAY_K) f(K{}, K{});
+  else if (a_layout == LAY_K) f(K{}, MN{});
+  else if (b_layout == LAY_K) f(MN{}, K{});
+  else f(MN{}, MN{});
+}
+
 template <int PREC>
-void launch(const GemmArgs& g, int a_layout, int b_layout, dim3 grid, hipStream_t st) {
-  if (a_layout == LAY_K && b_layout == LAY_K) hipLaunchKernelGGL((gemm_mfma_kernel<PREC, LAY_K, LAY_K>), grid, dim3(THREADS), 0, st, g);
-  else if (a_layout == LAY_K) hipLaunchKernelGGL((gemm_mfma_kernel<PREC, LAY_K, LAY_MN>), grid, dim3(THREADS), 0, st, g);
-  else if (b_layout == LAY_K) hipLaunchKernelGGL((gemm_mfma_kernel<PREC, LAY_MN, LAY_K>), grid, dim3(THREADS), 0, st, g);
-  else hipLaunchKernelGGL((gemm_mfma_kernel<PREC, LAY_MN, LAY_MN>), grid, dim3(THREADS), 0, st, g);
+void launch(const GemmArgs& g, int a_layout, int b_layout, bool ws, int grid, hipStream_t st) {
+  with_layouts(a_layout, b_layout, [&](auto a, auto b) {
+    constexpr int ALAY = decltype(a)::value, BLAY = decltype(b)::value;
+    if (ws) hipLaunchKernelGGL((gemm_mfma_ws_kernel<PREC, ALAY, BLAY>), dim3(grid), dim3(WS_THREADS), 0, st, g);
+    else hipLaunchKernelGGL((gemm_mfma_kernel<PREC, ALAY, BLAY>), dim3(grid), dim3(THREADS), 0, st, g);
+  });
 }
 
 int num_cus() {                       // of the CURRENT device (cached per device id)
@@ -865,14 +835,26 @@ int num_cus() {                       // of the CURRENT device (cached per devic
 }
 
 // how many k-splits a reduced product gets: enough workgroups for ~2 per CU, k chunks of at least 4 k-steps
-int pick_splits(int M, int N, int K, int batch, int bk) {
+int pick_splits(int M, int N, int K, int batch) {
   const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN) * batch;
   int s = (512 + tiles - 1) / tiles;
-  const int max_s = (K + 4 * bk - 1) / (4 * bk);
+  const int max_s = (K + 4 * BK - 1) / (4 * BK);
   if (s > max_s) s = max_s;
   if (s < 1) s = 1;
   if (s > 256) s = 256;
   return s;
+}
+
+// Z = batch * splits slabs of [M, N], plus Z partial rows of [M] behind them when the row sums of A ride along
+size_t slab_workspace_bytes(int Z, int M, int N, bool rowsum) {
+  return (size_t)Z * ((size_t)M * N + (rowsum ? M : 0)) * sizeof(float);
+}
+
+// one residency of the chip at `per_cu` workgroups per CU: a multiple of 8, so that t & 7 stays the workgroup's XCD for
+// every tile it walks
+int resident_grid(int total, int per_cu) {
+  const int resident = num_cus() * per_cu / 8 * 8;
+  return total > resident ? resident : total;
 }
 
 }  // namespace
@@ -887,18 +869,16 @@ int vidar_gemm_set_variant(int variant) {
 
 int vidar_gemm_splits(int M, int N, int K, int batch, int precision, int reduce) {
   if (!reduce) return 1;
-  return pick_splits(M, N, K, batch, BK);
+  return pick_splits(M, N, K, batch);
 }
 
 size_t vidar_gemm_workspace_bytes(int M, int N, int K, int batch, int precision, int reduce) {
   if (!reduce) return 0;
-  const int s = vidar_gemm_splits(M, N, K, batch, precision, reduce);
-  // reduce == 1: the product alone -- Z = batch * splits slabs of [M, N], none when there is a single slab (it is
-  // written straight to C);  reduce == 2: the product WITH the row sums of A (a_rowsum) -- the slabs plus Z partial
-  // rows of [M], also for a single slab
-  const size_t Z = (size_t)batch * s;
-  if (reduce == 1) return Z > 1 ? Z * (size_t)M * N * sizeof(float) : 0;
-  return Z * ((size_t)M * N + M) * sizeof(float);
+  // reduce == 1: the product alone -- none when there is a single slab (it is written straight to C);
+  // reduce == 2: the product WITH the row sums of A (a_rowsum) -- the partial rows too, also for a single slab
+  const int Z = batch * pick_splits(M, N, K, batch);
+  if (reduce == 1) return Z > 1 ? slab_workspace_bytes(Z, M, N, false) : 0;
+  return slab_workspace_bytes(Z, M, N, true);
 }
 
 int vidar_gemm_f32(const float* A, int64_t lda, int a_layout, const float* B, int64_t ldb, int b_layout, float* C,
@@ -920,7 +900,6 @@ int vidar_gemm_f32(const float* A, int64_t lda, int a_layout, const float* B, in
   if ((a_layout == LAY_MN && (int64_t)K * lda >= (1LL << 29)) || (b_layout == LAY_MN && (int64_t)K * ldb >= (1LL << 29)))
     return VIDAR_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const int bk = BK;
   GemmArgs g;
   g.A = A; g.B = B; g.C = C;
   g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.sA = strideA; g.sB = strideB; g.sC = strideC;
@@ -929,8 +908,8 @@ int vidar_gemm_f32(const float* A, int64_t lda, int a_layout, const float* B, in
   g.relu = relu;
   g.tiles_m = (M + BM - 1) / BM; g.tiles_n = (N + BN - 1) / BN;
   g.m_fastest = M < N;
-  g.splits = reduce ? pick_splits(M, N, K, batch, bk) : 1;
-  g.k_chunk = ((K + g.splits - 1) / g.splits + bk - 1) / bk * bk;
+  g.splits = reduce ? pick_splits(M, N, K, batch) : 1;
+  g.k_chunk = ((K + g.splits - 1) / g.splits + BK - 1) / BK * BK;
   const int Z = batch * g.splits;
   g.slabs = (reduce && (Z > 1 || a_rowsum != nullptr)) ? 1 : 0;
   g.a_rowsum = a_rowsum;
@@ -940,30 +919,19 @@ int vidar_gemm_f32(const float* A, int64_t lda, int a_layout, const float* B, in
   // a reduced product writes slabs and the reduction kernel applies the epilogue on [M, N] of ONE output: batch and
   // residual strides have no meaning there
   if (reduce && (strideC != 0 || strideR != 0) && batch > 1) return VIDAR_ERR_BAD_ARG;
-  GemmArgs k = g;
   if (g.slabs) {
-    const size_t need = (size_t)Z * ((size_t)M * N + (a_rowsum ? M : 0)) * sizeof(float);
-    if (workspace == nullptr || workspace_bytes < need) return VIDAR_ERR_BAD_ARG;
-    k.C = (float*)workspace;
+    if (workspace == nullptr || workspace_bytes < slab_workspace_bytes(Z, M, N, a_rowsum != nullptr)) return VIDAR_ERR_BAD_ARG;
     g.rowsum_ws = a_rowsum ? (float*)workspace + (size_t)Z * M * N : nullptr;
-    k.rowsum_ws = g.rowsum_ws;
   }
-  k.total = g.tiles_m * g.tiles_n * Z;
-  // one residency of the chip: 3 workgroups per CU (launch bounds: 3 waves per SIMD), a multiple of 8 so that t & 7
-  // stays the workgroup's XCD for every tile it walks.  (Measured against one workgroup per tile and against fetching
-  // the next tile after the epilogue: within noise of each other on MI355X, profiles/r04_kbench_gemm_*.)
-  if (g_gemm_variant >= 1 && a_rowsum == nullptr) {
-    // one (two) 512-thread workgroup(s) per CU (a multiple of 8 keeps t & 7 = the XCD for every tile a workgroup walks)
-    const int resident = num_cus() * g_gemm_variant / 8 * 8;
-    dim3 grid(k.total > resident ? resident : k.total);
-    if (precision == PREC_BF16X3) launch_ws<PREC_BF16X3>(k, a_layout, b_layout, grid, st);
-    else launch_ws<PREC_F32>(k, a_layout, b_layout, grid, st);
-  } else {
-    const int resident = num_cus() * 3 / 8 * 8;
-    dim3 grid(k.total > resident ? resident : k.total);
-    if (precision == PREC_BF16X3) launch<PREC_BF16X3>(k, a_layout, b_layout, grid, st);
-    else launch<PREC_F32>(k, a_layout, b_layout, grid, st);
-  }
+  // the default kernel: 3 workgroups per CU (launch bounds: 3 waves per SIMD).  (Measured against one workgroup per tile
+  // and against fetching the next tile after the epilogue: within noise of each other on MI355X,
+  // profiles/r04_kbench_gemm_*.)  Wave-specialised: one (two) 512-thread workgroup(s) per CU.
+  const bool ws = g_gemm_variant >= 1 && a_rowsum == nullptr;
+  const int grid = resident_grid(g.total, ws ? g_gemm_variant : 3);
+  GemmArgs tiles = g;                                    // the product's tiles go to the slabs, the reduction to C
+  if (g.slabs) tiles.C = (float*)workspace;
+  if (precision == PREC_BF16X3) launch<PREC_BF16X3>(tiles, a_layout, b_layout, ws, grid, st);
+  else launch<PREC_F32>(tiles, a_layout, b_layout, ws, grid, st);
   if (g.slabs) {
     const int64_t total = (int64_t)M * N;
     int blocks = (int)((total / 4 + 1 + 63) / 64);

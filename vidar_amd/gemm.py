@@ -92,13 +92,12 @@ def operand_ok(t, layout, contraction) -> bool:
 def _operand(t, layout, contraction, what):
     """`t` as the kernel can read it: itself when operand_ok, otherwise a contiguous copy (a transposed / expanded view
     used to be an error here)"""
-    _f32c(t, what) if t.stride(-1) == 1 else None
-    if operand_ok(t, layout, contraction):
-        return t
     if not t.is_cuda:
         raise RuntimeError(f"vidar_gemm: {what} must be a CUDA tensor (no CPU path)")
     if t.dtype != torch.float32:
         raise TypeError(f"vidar_gemm: {what} must be float32, got {t.dtype}")
+    if operand_ok(t, layout, contraction):
+        return t
     c = t.contiguous()
     if not operand_ok(c, layout, contraction):
         raise ValueError(f"vidar_gemm: {what} {tuple(t.shape)} exceeds the kernel's addressing range "
