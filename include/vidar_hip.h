@@ -170,6 +170,31 @@ int vidar_knn1_d3_bwd_ws(const float* p1, const float* p2, const int64_t* length
                          float* grad_p1, float* grad_p2, int N, int P1, int P2, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* knn_points_idx / knn_points_backward for 1 <= D <= 8, 1 <= K <= 32 (the reference's V2 range, knn.cu:261-264;
+ * csrc/knn_generic.hip).  p1 [N,P1,D], p2 [N,P2,D] f32; idx [N,P1,K] i64, dist2 [N,P1,K] f32: for every row below
+ * lengths1 the min(K, lengths2) points of p2[n, :lengths2[n]] that are smallest in (dist2, index), ascending; rows past
+ * lengths1 and slots past lengths2 are zero.  dist2 = sum over d of (p1[d] - p2[d])^2 in the order d = 0, 1, .., every
+ * product and sum rounded on its own (knn_cpu.cpp:36-40): the same bytes as the reference's CPU build.
+ *   chunks: p2 is cut into that many ranges across workgroups; 0 = the library chooses from N, P1, P2, K and the CU
+ *     count.  The result does not depend on it (the (dist2, index) order is total).
+ *   workspace: *bytes of vidar_knn_workspace_bytes = 8 * N * P1 * chunks_used * K (the partial lists; never P1 * P2),
+ *     chunks_used = min(chunks, max(P2, 1)).  The query returns VIDAR_ERR_BAD_ARG and *bytes = -1 for a (D, K) outside
+ *     the range or extents the kernels' 32-bit indices cannot hold (P1 * D or P2 * D above INT32_MAX; N or chunks
+ *     above 65535); it makes no call that needs a GPU.
+ *   An extent of 0 (N, P1, P2 or K) returns 0 before any HIP call and writes nothing: with nothing to search every
+ *     output is zero, and the caller provides that (chamferdist._C allocates zeros).  For every other call idx / dist2
+ *     and grad_p1 / grad_p2 are written completely.
+ * vidar_knn_bwd_f32: grad_p1[n,i,d] = sum over k < min(K, lengths2) of c = (2 g[n,i,k]) (p1[n,i,d] - p2[n,idx[n,i,k],d])
+ * in the order k = 0, 1, .. (a plain store: the reference's bytes); grad_p2[n,idx,d] -= c with fp32 atomics on a zeroed
+ * grad_p2 (knn_cpu.cpp:88-103).  An idx outside [0, P2) contributes nothing.  The deterministic mode does not change it. */
+int vidar_knn_workspace_bytes(int N, int P1, int P2, int D, int K, int chunks, int64_t* bytes, int64_t* chunks_used);
+int vidar_knn_fwd_f32(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2,
+                      int64_t* idx, float* dist2, void* workspace, size_t workspace_bytes,
+                      int N, int P1, int P2, int D, int K, int chunks, void* stream);
+int vidar_knn_bwd_f32(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2,
+                      const int64_t* idx, const float* grad_dist2, float* grad_p1, float* grad_p2,
+                      int N, int P1, int P2, int D, int K, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Multi-scale deformable attention.  Replaces mmcv._ext.ms_deform_attn_{forward,backward}
  * (mmcv-full 1.4.0, third party) as called from

@@ -1,6 +1,7 @@
 """Per-kernel timing of the HIP ops at BASELINE sizes (HIP events on torch's current stream, which
 is the stream every op launches on).  Prints one JSON line per op: ms, algorithmic GB/s."""
 import json
+import os
 import sys
 from pathlib import Path
 
@@ -125,6 +126,56 @@ def bench_knn(which):
         ms = timeit(lambda: knn_points(a, b))
         report(f"knn1_d3 {P1}x{P2}", ms, 12 * (P1 + P2) + 12 * P1, Gpairs_s=round(P1 * P2 / ms / 1e6, 1),
                fp32_TFLOPs=round(P1 * P2 * 8 / ms / 1e9, 2))
+    bench_knn_generic(rng)
+
+
+def bench_knn_generic(rng):
+    """every other (D, K): the kernels of csrc/knn_generic.hip next to the torch program they replace (the parent's
+    path, VIDAR_KNN_GENERIC=torch), alternating in one run: time, Gpairs/s and peak temporary bytes of both (torch's
+    allocator statistics: the peak above what was allocated before the call, less the two outputs)"""
+    from vidar_amd.third_lib.chamferdist import _C
+
+    def peak_temp(fn, out_bytes):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        return torch.cuda.max_memory_allocated() - before - out_bytes
+
+    for P1, P2 in ((30000, 30000), (10000, 30000)):
+        for D, K in ((3, 2), (3, 4), (3, 8), (3, 32), (8, 4), (2, 1)):
+            a = torch.from_numpy(rng.uniform(-50, 50, (1, P1, D)).astype(np.float32)).cuda()
+            b = torch.from_numpy(rng.uniform(-50, 50, (1, P2, D)).astype(np.float32)).cuda()
+            l1 = torch.tensor([P1], device="cuda"); l2 = torch.tensor([P2], device="cuda")
+            fwd = lambda: _C.knn_points_idx(a, b, l1, l2, K, -1)
+            idx, dist = fwd()
+            gd = torch.from_numpy(rng.standard_normal((1, P1, K)).astype(np.float32)).cuda()
+            cases = [("fwd", fwd, 12 * P1 * K, P1 * P2)]
+            if K == 8:
+                cases.append(("bwd", lambda: _C.knn_points_backward(a, b, l1, l2, idx, gd), 4 * D * (P1 + P2), P1 * K))
+            for what, fn, out_bytes, pairs in cases:
+                res = {}
+                for path in ("kernel", "torch", "kernel", "torch"):           # alternating; the better of two windows each
+                    if path == "torch":
+                        os.environ["VIDAR_KNN_GENERIC"] = "torch"
+                    try:
+                        ms = timeit(fn, warm=1, it=3) if path == "torch" else timeit(fn)
+                        res[path] = (min(ms, res[path][0]) if path in res else ms, peak_temp(fn, out_bytes))
+                    finally:
+                        os.environ.pop("VIDAR_KNN_GENERIC", None)
+                if what == "fwd":                                             # the two paths give the same bytes
+                    os.environ["VIDAR_KNN_GENERIC"] = "torch"
+                    try:
+                        ti, td = fn()
+                    finally:
+                        os.environ.pop("VIDAR_KNN_GENERIC", None)
+                    assert torch.equal(ti, idx) and torch.equal(td, dist), (D, K, P1, P2)
+                (kms, ktemp), (tms, ttemp) = res["kernel"], res["torch"]
+                report(f"knn_generic {what} D={D} K={K} {P1}x{P2}", kms, None, torch_ms=round(tms, 3),
+                       speedup=round(tms / kms, 1), Gpairs_s=round(pairs / kms / 1e6, 2),
+                       torch_Gpairs_s=round(pairs / tms / 1e6, 2), temp_MB=round(ktemp / 1e6, 2),
+                       torch_temp_MB=round(ttemp / 1e6, 2))
 
 
 def bench_msda_coherent(which):

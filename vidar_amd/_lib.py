@@ -71,6 +71,9 @@ _ABI = {
     "vidar_knn1_d3_bwd": "i 8p 3i p",
     "vidar_knn1_d3_bwd_workspace_bytes": "i 2i p",
     "vidar_knn1_d3_bwd_ws": "i 8p 3i p z p",
+    "vidar_knn_workspace_bytes": "i 6i 2p",
+    "vidar_knn_fwd_f32": "i 7p z 6i p",
+    "vidar_knn_bwd_f32": "i 8p 5i p",
     "vidar_msda_fwd_f32": "i 6p 7i p",
     "vidar_msda_bwd_workspace_bytes": "z 6i",
     "vidar_msda_set_item_order": "i i",

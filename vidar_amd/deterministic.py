@@ -39,7 +39,7 @@ _COVERAGE = {
     "dvr.render": (NOT_COVERED, "vidar_dvr_render_f32 (grad_sigma)"),
     "dvxlr.get_grad_sigma": (NOT_COVERED, "vidar_dvxlr_get_grad_sigma_f32"),
     "dvxlr_v2.get_grad_sigma": (NOT_COVERED, "vidar_dvxlr2_get_grad_sigma_f32"),
-    "knn generic backward": (NOT_COVERED, "chamferdist._C._generic_knn_backward (scatter_add_)"),
+    "knn generic backward": (NOT_COVERED, "vidar_knn_bwd_f32 (grad_p2); chamferdist._C._generic_knn_backward (scatter_add_) for D > 8 or K > 32"),
     "gemm": (ALREADY, "vidar_gemm_f32: split-K slabs summed in a fixed order"),
     "det_loss": (ALREADY, "vidar_det_loss_{fwd,bwd}_f32"),
     "forward kernels, gathers": (ALREADY, "every forward; grad_sampling_loc / grad_attn_weight; knn grad_p1"),

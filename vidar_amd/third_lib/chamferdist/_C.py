@@ -1,15 +1,22 @@
 """`chamferdist._C` -- same callables as the reference's pybind module
-(third_lib/chamfer_dist/chamferdist/chamferdist/ext.cpp:5-11).  The hot case K=1, D=3 runs the
-gfx950 HIP kernel behind vidar_knn1_d3_{fwd,bwd}; other (D, K) are not on ViDAR's path
-(every call site uses K=1 on xyz clouds: chamfer.py:77-93): the reference dispatches them to templated kernels
-(knn.cu:266-295), here they run as a chunked torch program ON THE DEVICE of the inputs (`_generic_*` below: same
-results as knn_cpu.cpp:7-58 / :64-106 -- ascending distances, ties to the lower index, zero rows past `lengths1`,
-zero slots past `lengths2`), not a host fallback: CPU tensors are refused exactly like in the hot case."""
+(third_lib/chamfer_dist/chamferdist/chamferdist/ext.cpp:5-11), on gfx950 HIP kernels:
+  * K = 1, D = 3 (every call site of ViDAR: chamfer.py:77-93) runs vidar_knn1_d3_{fwd,bwd} (csrc/knn.hip);
+  * every other (D, K) with 1 <= D <= 8 and 1 <= K <= 32 -- the range of the reference's templated kernels
+    (knn.cu:261-295) -- runs vidar_knn_{fwd,bwd}_f32 (csrc/knn_generic.hip): per-lane sorted top-K lists in registers,
+    no distance matrix, a workspace proportional to N * P1 * chunks * K;
+  * outside that range (D > 8 or K > 32), or with VIDAR_KNN_GENERIC=torch (an A/B switch for tools/kbench.py), a
+    chunked torch program ON THE DEVICE of the inputs (`_generic_*` below), not a host fallback: CPU tensors are
+    refused exactly like in the hot case.
+All three give the results of knn_cpu.cpp:7-58 / :64-106 -- fp32 distances with separately rounded products,
+ascending, ties to the lower index, zero rows past `lengths1`, zero slots past `lengths2` -- indices and distances bit
+for bit."""
 from __future__ import annotations
 
-import torch
-
 import ctypes
+import os
+import warnings
+
+import torch
 
 from ..._lib import lib, check, ptr, stream_of, TIMER
 from ... import deterministic
@@ -17,7 +24,7 @@ from ... import deterministic
 
 def knn_check_version(version: int, D: int, K: int) -> bool:
     """KnnCheckVersion (knn.cu:269-280): which of the reference's four kernels accepts (D, K).  Every accepted
-    combination computes the same result here (one HIP kernel for D = 3, K = 1; the device program below otherwise)."""
+    combination computes the same result here (see the module docstring for which kernel runs)."""
     if version == 0:
         return True
     if version == 1:
@@ -99,34 +106,73 @@ def _generic_knn_backward(p1, p2, l1, l2, idxs, grad_dists):
     return g1, g2
 
 
-def knn_points_idx(p1, p2, lengths1, lengths2, K: int = 1, version: int = -1):
-    """-> (idx int64 [N,P1,K], dists f32 [N,P1,K]) ; squared L2, ties -> lowest index."""
+def _kernel_workspace(N, P1, P2, D, K, chunks=0):
+    """(bytes, chunks_used) of vidar_knn_fwd_f32, or None where (D, K) or the extents are outside the kernels' range"""
+    nbytes, used = ctypes.c_int64(0), ctypes.c_int64(0)
+    rc = lib().vidar_knn_workspace_bytes(N, P1, P2, D, K, chunks, ctypes.addressof(nbytes), ctypes.addressof(used))
+    return None if rc != 0 or nbytes.value < 0 else (nbytes.value, used.value)
+
+
+def _use_torch_program():
+    return os.environ.get("VIDAR_KNN_GENERIC", "") == "torch"
+
+
+def knn_points_idx(p1, p2, lengths1, lengths2, K: int = 1, version: int = -1, chunks: int = 0):
+    """-> (idx int64 [N,P1,K], dists f32 [N,P1,K]) ; squared L2, ties -> lowest index.  `chunks` (not in the reference's
+    signature): the split of p2 the generic kernel takes, 0 = its own choice; the result does not depend on it."""
+    K = int(K)
+    if version >= 0 and not knn_check_version(version, p1.shape[-1], K):
+        # the reference prints a warning and goes on with ChooseVersion(D, K) (knn.cu:331-339); every version computes
+        # the same result here
+        warnings.warn(f"Requested KNN version {version} is not compatible with D = {p1.shape[-1]}; K = {K}. "
+                      f"Falling back to the default version", UserWarning, stacklevel=2)
     p1, p2, l1, l2 = _prep(p1, p2, lengths1, lengths2)
-    if version >= 0 and not knn_check_version(version, p1.shape[2], K):
-        raise RuntimeError("Invalid version")                   # AT_ASSERTM(KnnCheckVersion(version, D, K), ...) knn.cu:318
-    if K != 1 or p1.shape[2] != 3:
-        return _generic_knn_idx(p1, p2, l1.to(p1.device), l2.to(p1.device), int(K))
-    N, P1, _ = p1.shape
+    N, P1, D = p1.shape
     P2 = p2.shape[1]
-    idx = torch.empty((N, P1, 1), dtype=torch.int64, device=p1.device)
-    dist = torch.empty((N, P1, 1), dtype=torch.float32, device=p1.device)
-    ws = torch.empty((max(N * P1, 1),), dtype=torch.int64, device=p1.device)
-    with TIMER.span("knn1_d3_fwd", 12 * (N * P1 + N * P2) + 12 * N * P1):
-      check(lib().vidar_knn1_d3_fwd(ptr(p1), ptr(p2), ptr(l1), ptr(l2), ptr(idx), ptr(dist), ptr(ws),
-                                  N, P1, P2, stream_of(p1)), "knn_points_idx")
+    if K == 1 and D == 3:
+        idx = torch.empty((N, P1, 1), dtype=torch.int64, device=p1.device)
+        dist = torch.empty((N, P1, 1), dtype=torch.float32, device=p1.device)
+        ws = torch.empty((max(N * P1, 1),), dtype=torch.int64, device=p1.device)
+        with TIMER.span("knn1_d3_fwd", 12 * (N * P1 + N * P2) + 12 * N * P1):
+          check(lib().vidar_knn1_d3_fwd(ptr(p1), ptr(p2), ptr(l1), ptr(l2), ptr(idx), ptr(dist), ptr(ws),
+                                      N, P1, P2, stream_of(p1)), "knn_points_idx")
+        return idx, dist
+    need = None if _use_torch_program() else _kernel_workspace(N, P1, P2, D, K, chunks)
+    if need is None:
+        return _generic_knn_idx(p1, p2, l1.to(p1.device), l2.to(p1.device), K)
+    if N == 0 or P1 == 0 or P2 == 0:              # nothing to search: the zero fill is the whole result
+        return (torch.zeros((N, P1, K), dtype=torch.int64, device=p1.device),
+                torch.zeros((N, P1, K), dtype=torch.float32, device=p1.device))
+    l1, l2 = l1.to(p1.device), l2.to(p1.device)
+    idx = torch.empty((N, P1, K), dtype=torch.int64, device=p1.device)
+    dist = torch.empty((N, P1, K), dtype=torch.float32, device=p1.device)
+    ws = torch.empty(need[0], dtype=torch.uint8, device=p1.device)
+    with TIMER.span("knn_fwd", 4 * D * (N * P1 + N * P2) + 12 * N * P1 * K):
+        check(lib().vidar_knn_fwd_f32(ptr(p1), ptr(p2), ptr(l1), ptr(l2), ptr(idx), ptr(dist), ptr(ws), need[0],
+                                      N, P1, P2, D, K, chunks, stream_of(p1)), "knn_points_idx")
     return idx, dist
 
 
 def knn_points_backward(p1, p2, lengths1, lengths2, idxs, grad_dists):
-    """-> (grad_p1 [N,P1,3], grad_p2 [N,P2,3])   (knn_cpu.cpp:64-106)"""
+    """-> (grad_p1 [N,P1,D], grad_p2 [N,P2,D])   (knn_cpu.cpp:64-106)"""
     if idxs.shape[-1] != 1 or p1.shape[-1] != 3:
         deterministic.require("knn generic backward")             # before anything touches the GPU
     p1, p2, l1, l2 = _prep(p1, p2, lengths1, lengths2)
-    if idxs.shape[-1] != 1 or p1.shape[2] != 3:
-        return _generic_knn_backward(p1, p2, l1.to(p1.device), l2.to(p1.device), idxs.contiguous(),
-                                     grad_dists.contiguous().float())
-    N, P1, _ = p1.shape
+    N, P1, D = p1.shape
     P2 = p2.shape[1]
+    K = idxs.shape[-1]
+    if K != 1 or D != 3:
+        idxs, grad_dists = idxs.contiguous(), grad_dists.contiguous().float()
+        l1, l2 = l1.to(p1.device), l2.to(p1.device)
+        if _use_torch_program() or _kernel_workspace(N, P1, P2, D, K) is None:
+            return _generic_knn_backward(p1, p2, l1, l2, idxs, grad_dists)
+        if N == 0 or P1 == 0 or P2 == 0:
+            return torch.zeros_like(p1), torch.zeros_like(p2)
+        g1 = torch.empty_like(p1)
+        g2 = torch.empty_like(p2)
+        check(lib().vidar_knn_bwd_f32(ptr(p1), ptr(p2), ptr(l1), ptr(l2), ptr(idxs), ptr(grad_dists), ptr(g1), ptr(g2),
+                                      N, P1, P2, D, K, stream_of(p1)), "knn_points_backward")
+        return g1, g2
     g1 = torch.empty_like(p1)
     g2 = torch.empty_like(p2)
     ws, wsn = None, 0
