@@ -16,7 +16,17 @@ every frame are printed -- count, best scores, labels.  The boxes of the current
 scored against the sequence's synthetic ground truth (num_pts = 1, no attributes, so attr_err is 1) with
 vidar_amd.det_evaluate -- nuScenes mAP, the five true-positive errors and NDS, computed on the device without the
 devkit: rank 0 gathers the boxes of all ranks, prints the devkit's closing table and writes the result under "metrics"
-in --out, next to the per-frame records ("frames")."""
+in --out, next to the per-frame records ("frames").
+
+With --ann-file a detection recipe runs video mode over the frames of a validation info pkl instead, in dataset order
+(vidar_amd.data.DetectionSequenceDataset in test mode; every rank takes a contiguous shard, so its frames stay in scene
+order), and scores the boxes of EVERY frame against the file's own annotations (det_evaluate.ground_truth_from_infos: all
+annotated boxes with their lidar + radar point counts, no attributes), both sides in the ego frame of their sample;
+--results-json PATH also writes the boxes in the nuScenes detection submission layout (global frame), --eval-stride N keeps
+every N-th SCENE whole.
+
+    python tools/test.py finetune/vidar_1_8_nusc_1future --checkpoint work_dirs/fine-tune/latest.pth \
+        --ann-file data/nuscenes/nuscenes_infos_temporal_val.pkl --samples 0 --results-json work_dirs/results_nusc.json"""
 import argparse
 import json
 import os
@@ -45,8 +55,13 @@ def main(argv=None):
     ap.add_argument("--ann-file", help="validation info pkl (data/nuscenes/nuscenes_infos_temporal_val.pkl)")
     ap.add_argument("--data-root", default="")
     ap.add_argument("--eval-stride", type=int, default=None,
-                    help="evaluate every N-th usable val index (quick subset); default: the whole split, as the "
+                    help="evaluate every N-th usable val index (quick subset; a detection recipe: every N-th scene, whole, "
+                         "so that the temporal input stays what the model expects); default: the whole split, as the "
                          "reference's data.test does")
+    ap.add_argument("--results-json", help="detection recipes with --ann-file: also write the decoded boxes in the nuScenes "
+                                           "detection submission layout (global frame) to this file")
+    ap.add_argument("--cams", type=int, help="cameras per frame of the info file when it is not the recipe's (plumbing "
+                                             "runs on reduced files; nuScenes: 6)")
     ap.add_argument("--device-images", action="store_true",
                     help="with --ann-file: ship uint8 frames and run the image pipeline in HIP kernels (same tensor)")
     ap.add_argument("--device-metrics", action="store_true",
@@ -70,6 +85,9 @@ def main(argv=None):
     dev = torch.device("cuda", local)
     kw = dict(bev_h=args.bev[0], bev_w=args.bev[1]) if args.bev else {}
     meta = get_config(args.config, with_backbone=not args.no_backbone, **kw)
+    if args.cams:
+        from vidar_amd.configs import set_num_cams
+        set_num_cams(meta["model"], args.cams)
     if args.submission:
         meta["model"]["_submission"] = True
         meta["model"]["_submission_path"] = args.submission
@@ -130,10 +148,14 @@ def video_detection(model, meta, args, dev, rank, world):
     from vidar_amd import evaluate as E
     from vidar_amd.det_evaluate import DetectionEval, format_summary
     from vidar_amd.synthetic import fpn_features, make_sample
-    if args.ann_file or args.submission:
-        raise SystemExit("detection recipes evaluate synthetic sequences only (no box annotations in the data reader, no "
-                         "submission format); --ann-file / --submission do not apply")
+    if args.submission:
+        raise SystemExit("--submission writes the forecasting depth files and does not apply to a detection recipe; its "
+                         "boxes go to --results-json (with --ann-file)")
+    if args.results_json and not args.ann_file:
+        raise SystemExit("--results-json needs --ann-file: the submission layout names the samples of an info file")
     model.eval()
+    if args.ann_file:
+        return info_detection(model, meta, args, dev, rank, world)
     T_img = meta["queue_length"] + 1
     part = []                                        # per sequence: its frame records, the last frame's boxes, its ground truth
     for i in range(rank, args.samples, world):
@@ -174,6 +196,72 @@ def video_detection(model, meta, args, dev, rank, world):
             Path(args.out).parent.mkdir(parents=True, exist_ok=True)
             Path(args.out).write_text(json.dumps(dict(frames=[r for s in part for r in s["records"]], metrics=metrics),
                                                  indent=1))
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        torch.distributed.barrier()
+        torch.distributed.destroy_process_group()
+
+
+def whole_scene_subset(infos, stride):
+    """indices of the frames of every `stride`-th scene (scenes in order of first appearance)"""
+    scenes = list(dict.fromkeys(info["scene_token"] for info in infos))
+    keep = set(scenes[::stride or 1])
+    return [i for i, info in enumerate(infos) if info["scene_token"] in keep]
+
+
+@torch.no_grad()
+def info_detection(model, meta, args, dev, rank, world):
+    """video mode over the frames of an info pkl, scored against its own annotations"""
+    from vidar_amd.configs import dataset_kwargs
+    from vidar_amd.data import DetectionSequenceDataset, DistributedSampler
+    from vidar_amd.data.device_prep import DeviceImagePrep
+    from vidar_amd.data.loader import collate, finish_batch
+    from vidar_amd.det_evaluate import (DetectionEval, boxes_to_ego, format_summary, ground_truth_from_infos,
+                                        write_results_json)
+    ds = DetectionSequenceDataset(args.ann_file, data_root=args.data_root, device_images=args.device_images,
+                                  **dataset_kwargs(meta, test_mode=True))
+    frames = whole_scene_subset([ds.infos[i] for i in ds.usable_index], args.eval_stride)
+    if args.samples > 0:                                         # as on the forecasting route: --samples 0 = the whole file
+        frames = frames[:args.samples]
+    prep = DeviceImagePrep() if args.device_images else None
+    part = []
+    for pos in DistributedSampler(frames, world, rank):           # contiguous shard: this rank's frames in scene order
+        s_ = ds[frames[pos]]
+        img = finish_batch(collate([s_]), dev, prep)["img"] if args.device_images else s_["img"][None].to(dev)
+        m = s_["img_metas"]
+        box = model(return_loss=False, img_metas=[[m]], img=[img])[0]["pts_bbox"]
+        rec = dict(sample=m["sample_idx"], scene=m["scene_token"], boxes=len(box["boxes_3d"]),
+                   top_scores=[round(float(v), 4) for v in box["scores_3d"][:3]],
+                   top_labels=[int(v) for v in box["labels_3d"][:3]])
+        print(json.dumps(rec), flush=True)
+        part.append(dict(pos=pos, record=rec, boxes=box["boxes_3d"].tensor.numpy(), scores=box["scores_3d"].numpy(),
+                         labels=box["labels_3d"].numpy()))
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and world > 1:
+        parts = [None] * world
+        torch.distributed.all_gather_object(parts, part)
+        part = [s for p in parts for s in p]                     # rank order = dataset order; the tail repeats the head
+    part = part[:len(frames)]
+    if rank == 0:
+        assert [s["pos"] for s in part] == list(range(len(frames)))
+        infos = [ds.infos[ds.usable_index[i]] for i in frames]
+        class_names = meta.get("class_names") or DetectionEval().class_names
+        lidar = [dict(boxes=torch.as_tensor(s["boxes"], dtype=torch.float32, device=dev).reshape(-1, 9),
+                      scores=torch.as_tensor(s["scores"], dtype=torch.float32, device=dev),
+                      labels=torch.as_tensor(s["labels"], dtype=torch.int64, device=dev)) for s in part]
+        # bottom face -> gravity centre, LiDAR frame -> ego frame of each box's sample: one batched transform
+        counts = [len(p["labels"]) for p in lidar]
+        b = torch.cat([p["boxes"] for p in lidar])
+        b = torch.cat([b[:, :2], (b[:, 2] + b[:, 5] * 0.5)[:, None], b[:, 3:]], 1)
+        per_box = lambda key: np.repeat(np.asarray([info[key] for info in infos], np.float64), counts, axis=0)
+        ego = boxes_to_ego(b, per_box("lidar2ego_rotation"), per_box("lidar2ego_translation")).split(counts)
+        pred = [dict(p, boxes=e) for p, e in zip(lidar, ego)]
+        metrics = DetectionEval(class_names).evaluate(pred, ground_truth_from_infos(infos, class_names, dev))
+        print(format_summary(metrics, gt_attrs=False), flush=True)
+        if args.results_json:
+            write_results_json(args.results_json, [info["token"] for info in infos], lidar, infos, class_names)
+            print(f"results: {args.results_json}", flush=True)
+        if args.out:
+            Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.out).write_text(json.dumps(dict(frames=[s["record"] for s in part], metrics=metrics), indent=1))
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

@@ -7,8 +7,9 @@
 
 CONFIG is one of the in-repo names (vidar_amd.configs.VARIANTS) or a path to a released mmcv-style
 config file, which loads unchanged.  Data: the synthetic generator (every rank draws its own samples), or with
---ann-file an info pkl read by vidar_amd.data (multi-sweep lidar, image augmentation, DistributedGroupSampler).  DDP over RCCL, AdamW + cosine/warm-up, grad-clip 35, JSON-lines
-log, mmcv-layout checkpoints, --resume-from."""
+--ann-file an info pkl read by vidar_amd.data (multi-sweep lidar, image augmentation, DistributedGroupSampler; a
+finetune/ recipe reads the box annotations of the same file through DetectionSequenceDataset).  DDP over RCCL, AdamW +
+cosine/warm-up, grad-clip 35, JSON-lines log, mmcv-layout checkpoints, --resume-from."""
 import argparse
 import ast
 import os
@@ -23,7 +24,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("config")
     ap.add_argument("--iters", type=int, default=100)
@@ -43,14 +44,17 @@ def main():
     ap.add_argument("--device-images", action="store_true",
                     help="with --ann-file: the workers only decode and draw the augmentation, the image pipeline "
                          "(photometric, crop / resize / flip, normalise, pad) runs in HIP kernels with the host path's bits")
+    ap.add_argument("--bev", type=int, nargs=2, help="train a named recipe at a reduced BEV (plumbing runs)")
+    ap.add_argument("--cams", type=int, help="cameras per frame of the info file when it is not the recipe's (plumbing "
+                                             "runs on reduced files; nuScenes: 6)")
     ap.add_argument("--device-assign", action="store_true",
                     help="detection fine-tuning: Hungarian assignment on the device (csrc/det_assign.hip), no host read in "
                          "the loss tail; its status is checked where the loss is read for the log line")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
 
     from vidar_amd import checkpoint as C
     from vidar_amd import train as T
-    from vidar_amd.configs import FINETUNE, VARIANTS, get_config
+    from vidar_amd.configs import FINETUNE, VARIANTS, get_config, set_num_cams
     from vidar_amd.plugin.config import Config
     from vidar_amd.synthetic import fpn_features, make_sample
 
@@ -59,7 +63,8 @@ def main():
     torch.cuda.set_device(local)
     file_cfg = None
     if args.config in VARIANTS or args.config in FINETUNE:
-        meta = get_config(args.config, with_backbone=not args.no_backbone)
+        kw = dict(bev_h=args.bev[0], bev_w=args.bev[1]) if args.bev else {}
+        meta = get_config(args.config, with_backbone=not args.no_backbone, **kw)
         model_cfg, opt_cfg, clip = meta["model"], meta["optimizer"], meta["grad_clip"]
     else:
         cfg = file_cfg = Config.fromfile(args.config)
@@ -72,6 +77,8 @@ def main():
         clip = cfg.optimizer_config.grad_clip.max_norm
         if args.no_backbone:
             model_cfg.pop("img_backbone", None); model_cfg.pop("img_neck", None)
+    if args.cams:
+        set_num_cams(model_cfg, args.cams)
     from vidar_amd import gemm_tuning
     gemm_tuning.enable(rank=rank)               # tuned library-GEMM solutions (vidar_amd/gemm_tuning.py)
     torch.manual_seed(args.seed); np.random.seed(args.seed + rank)
@@ -125,18 +132,24 @@ def main():
     work = Path(args.work_dir)
     if rank == 0:
         work.mkdir(parents=True, exist_ok=True)
-    if args.ann_file and detection:
-        raise SystemExit("detection fine-tuning reads synthetic samples only: the data reader has no box annotations yet")
     if args.ann_file:                      # real data: reader -> rank-sharded sampler -> collate -> device
         from vidar_amd.configs import dataset_kwargs
-        from vidar_amd.data import ViDARSequenceDataset
+        from vidar_amd.data import DetectionSequenceDataset, ViDARSequenceDataset
         from vidar_amd.data.loader import build_dataloader
-        # the recipe's own temporal augmentation / subset stride / GT voxel size (not the reader's defaults)
+        # the recipe's own temporal augmentation / subset stride / GT voxel size (not the reader's defaults); a detection
+        # recipe: its queue length, classes, box range and the valid_flag mask of the annotations
         from vidar_amd.data.device_prep import DeviceImagePrep
         from vidar_amd.data.loader import finish_batch
         prep = DeviceImagePrep() if args.device_images else None      # keeps the resample tables of the sizes it has seen
-        ds = ViDARSequenceDataset(args.ann_file, data_root=args.data_root, augment=True, device_images=args.device_images,
-                                  **dataset_kwargs(meta, test_mode=False, file_cfg=file_cfg))
+        data_meta = meta
+        if detection and meta.get("task") != "detection":     # a released fine-tune file (vidar_finetune/**,
+            name = Path(args.config).stem                     # bevformer_1_4_baseline.py): the data set of its recipe
+            data_meta = get_config(f"finetune/{name}" if f"finetune/{name}" in FINETUNE else "finetune/vidar_1_8_nusc_1future")
+        ds = (DetectionSequenceDataset if detection else ViDARSequenceDataset)(
+            args.ann_file, data_root=args.data_root, augment=True, device_images=args.device_images,
+            **dataset_kwargs(data_meta, test_mode=False, file_cfg=file_cfg))
+        if len(ds) == 0:
+            raise SystemExit(f"{args.ann_file}: no usable training index for this recipe")
         spg = file_cfg.data.samples_per_gpu if file_cfg is not None else meta["data"]["samples_per_gpu"]
         loader = build_dataloader(ds, spg, args.workers, world, rank, args.seed)
 
@@ -146,8 +159,13 @@ def main():
             def __iter__(self):
                 loader.sampler.set_epoch(self.epoch); self.epoch += 1
                 for b in loader:
-                    yield dict(img=finish_batch(b, dev, prep)["img"], img_metas=b["img_metas"],
-                               gt_points=[g.to(dev, non_blocking=True) for g in b["gt_points"]])
+                    b = finish_batch(b, dev, prep)
+                    if detection:           # boxes / labels stay on the host: the head stages them through its pinned arena
+                        yield dict(img=b["img"], img_metas=b["img_metas"], gt_bboxes_3d=b["gt_bboxes_3d"],
+                                   gt_labels_3d=b["gt_labels_3d"])
+                    else:
+                        yield dict(img=b["img"], img_metas=b["img_metas"],
+                                   gt_points=[g.to(dev, non_blocking=True) for g in b["gt_points"]])
         batches = _Epochs()
     else:
         batches = [sample(i) for i in range(args.samples)]

@@ -140,7 +140,7 @@ def model_config(name, bev_h=200, bev_w=200, with_backbone=False, latent_render=
 FINETUNE = {
     "finetune/vidar_1_8_nusc_1future": dict(pretrain="vidar_1_8_nusc_1future", lr_step=1.0),
     "finetune/vidar_1_8_nusc_3future": dict(pretrain="vidar_1_8_nusc_3future", lr_step=0.5),
-    "finetune/vidar_full_nusc_1future": dict(pretrain="vidar_full_nusc_1future", lr_step=0.5),
+    "finetune/vidar_full_nusc_1future": dict(pretrain="vidar_full_nusc_1future", lr_step=0.5, use_pretrain_data=False),
 }
 CLASS_NAMES = ("car", "truck", "construction_vehicle", "bus", "trailer", "barrier", "motorcycle", "bicycle", "pedestrian",
                "traffic_cone")
@@ -199,6 +199,9 @@ def get_config(name, bev_h=200, bev_w=200, with_backbone=False, latent_render=No
                    class_names=CLASS_NAMES, load_from=f"work_dirs/{f['pretrain']}/latest.pth",
                    work_dir=f"work_dirs/fine-tune/{f['pretrain']}")
         out["queue_length"] = 3          # the detection dataset's queue_length 4 counts the current frame: 3 history frames
+        # data.train of the fine-tune files (:212-226): the 1/4-subset recipes read the pre-training scan's frames
+        out["data"] = dict(samples_per_gpu=1, workers_per_gpu=4, use_valid_flag=True,
+                           use_pretrain_data=f.get("use_pretrain_data", True), load_interval=1)
         return out
     v = VARIANTS[name]
     h, w = v["img_hw"]
@@ -207,6 +210,14 @@ def get_config(name, bev_h=200, bev_w=200, with_backbone=False, latent_render=No
                 future_frames=v["future_frames"], num_cams=v["cams"], img_hw=v["img_hw"],
                 fpn_shapes=shapes, optimizer=dict(lr=2e-4, weight_decay=0.01), grad_clip=35.0,
                 data=dict(samples_per_gpu=1, workers_per_gpu=4, **v["data"]))
+
+
+def set_num_cams(model_cfg, num_cams):
+    """a model dict for data with another number of cameras per frame than the recipe's (reduced files, plumbing runs)"""
+    transformer = model_cfg["pts_bbox_head"]["transformer"]
+    transformer["num_cams"] = num_cams
+    transformer["encoder"]["transformerlayers"]["attn_cfgs"][1]["num_cams"] = num_cams
+    return model_cfg
 
 
 def dataset_kwargs(meta, test_mode=False, file_cfg=None, test_stride=None):
@@ -220,7 +231,13 @@ def dataset_kwargs(meta, test_mode=False, file_cfg=None, test_stride=None):
     `data.train` (vidar_1_8_nusc_1future.py:338-342) and not to `data.val` / `data.test` (:345-368), where the dataset's
     default None applies (nuscenes_vidar_dataset_template.py:66-68) -- evaluation runs over the whole val split.  A
     stride in test mode is an explicit choice: `test_stride` here (tools/test.py --eval-stride), or a `data.test` entry
-    of the loaded config file that names it."""
+    of the loaded config file that names it.
+    A detection fine-tune recipe answers with the keyword arguments of vidar_amd.data.DetectionSequenceDataset instead
+    (vidar_finetune/nusc_1_4_subset/vidar_1_8_nusc_1future.py:212-236): `queue_length` counting the current frame, the
+    classes, the range of ObjectRangeFilter, and for the training split `use_valid_flag` / `use_pretrain_data`;
+    `test_stride` does not apply (tools/test.py strides over scenes itself)."""
+    if meta.get("task") == "detection":
+        return _detection_dataset_kwargs(meta, test_mode, file_cfg)
     d = dict(meta["data"])
     kw = dict(queue_length=meta["queue_length"], future_length=d["future_test"] if test_mode else meta["future_frames"],
               rand_frame_interval=tuple(d["rand_frame_interval"]),
@@ -241,4 +258,23 @@ def dataset_kwargs(meta, test_mode=False, file_cfg=None, test_stride=None):
                 kw["voxel_size"] = tuple(step["cur_sweep_cfg"]["voxel_size"])
     if test_mode:
         kw["rand_frame_interval"] = (1,)
+    return kw
+
+
+def _detection_dataset_kwargs(meta, test_mode, file_cfg):
+    d = meta["data"]
+    kw = dict(queue_length=meta["queue_length"] + 1, test_mode=test_mode, load_interval=d["load_interval"],
+              class_names=tuple(meta["class_names"]), point_cloud_range=list(PC_RANGE),
+              use_valid_flag=False if test_mode else d["use_valid_flag"],
+              use_pretrain_data=False if test_mode else d["use_pretrain_data"])
+    if file_cfg is not None:
+        split = file_cfg.data.test if test_mode else file_cfg.data.train
+        # a key the file leaves out takes the data set's own default, not the named recipe's value
+        for key, default in (("queue_length", 4), ("load_interval", 1), ("use_valid_flag", False), ("use_pretrain_data", False)):
+            kw[key] = split.get(key, default)
+        if "classes" in split:
+            kw["class_names"] = tuple(split["classes"])
+        for step in split.get("pipeline", []):
+            if step.get("type") == "ObjectRangeFilter":
+                kw["point_cloud_range"] = list(step["point_cloud_range"])
     return kw

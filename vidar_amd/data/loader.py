@@ -77,26 +77,28 @@ class DistributedSampler(Sampler):
 
 
 def collate(samples):
-    """list of dataset samples -> dict(img [bs,T,cams,3,H,W], img_metas [bs] of {t: meta}, gt_points [bs]).
+    """list of dataset samples -> dict(img [bs,T,cams,3,H,W], img_metas [bs] of {t: meta}, gt_points [bs]); detection
+    samples carry gt_bboxes_3d / gt_labels_3d [bs] instead of gt_points, also as per-sample lists.
     Images of different sizes (CropResizeFlipImage draws a resize per sample) are zero-padded at the bottom /
     right to the largest H and W of the batch, like mmcv's collate does for stacked DataContainers."""
     samples = [s for s in samples if s is not None]
+    out = {k: [s[k] for s in samples] for k in ("img_metas", "gt_points", "gt_bboxes_3d", "gt_labels_3d")
+           if samples and k in samples[0]}
     if samples and "img_raw" in samples[0]:      # device-side image pipeline: `finish_batch` turns these into `img`
-        return dict(img_raw=[s["img_raw"] for s in samples], img_plan=[s["img_plan"] for s in samples],
-                    img_metas=[s["img_metas"] for s in samples], gt_points=[s["gt_points"] for s in samples])
+        return dict(img_raw=[s["img_raw"] for s in samples], img_plan=[s["img_plan"] for s in samples], **out)
     imgs = [s["img"] for s in samples]
     H = max(i.shape[-2] for i in imgs); W = max(i.shape[-1] for i in imgs)
     if any(i.shape[-2:] != (H, W) for i in imgs):
         imgs = [torch.nn.functional.pad(i, (0, W - i.shape[-1], 0, H - i.shape[-2])) for i in imgs]
-    return dict(img=torch.stack(imgs), img_metas=[s["img_metas"] for s in samples],
-                gt_points=[s["gt_points"] for s in samples])
+    return dict(img=torch.stack(imgs), **out)
 
 
 def finish_batch(batch, device, prep=None):
     """the device half of a batch: `img` on `device`.  A host-path batch is copied; a `device_images` batch has its
     uint8 frames copied (pinned, non-blocking: a quarter of the fp32 bytes) and put through the image pipeline's kernels
     (`prep`: a device_prep.DeviceImagePrep), samples of different resized sizes zero-padded at the bottom / right to the
-    batch maximum like `collate` does.  -> the batch with `img` [bs, T, cams, 3, H, W] instead of img_raw / img_plan"""
+    batch maximum like `collate` does.  -> the batch with `img` [bs, T, cams, 3, H, W] ([bs, cams, 3, H, W] for samples of
+    one frame without a time axis) instead of img_raw / img_plan"""
     out = {k: v for k, v in batch.items() if k not in ("img_raw", "img_plan")}
     if "img_raw" not in batch:
         out["img"] = batch["img"].to(device, non_blocking=True)
@@ -106,13 +108,17 @@ def finish_batch(batch, device, prep=None):
         prep = DeviceImagePrep()
     imgs = []
     for raw, plan in zip(batch["img_raw"], batch["img_plan"]):
+        single = raw.dim() == 4                  # one frame per sample (detection test items): [cams, H, W, 3], no time axis
+        if single:
+            raw = raw[None]
         T, cams = raw.shape[:2]
         if not raw.is_pinned():
             raw = raw.pin_memory()
         dev_raw = raw.to(device, non_blocking=True).flatten(0, 1)
         flat = dict(plan, photo=None if plan["photo"] is None else np.asarray(plan["photo"]).reshape(T * cams, -1))
         img = prep(dev_raw, flat)
-        imgs.append(img.view(T, cams, *img.shape[1:]))
+        img = img.view(T, cams, *img.shape[1:])
+        imgs.append(img[0] if single else img)
     H = max(i.shape[-2] for i in imgs); W = max(i.shape[-1] for i in imgs)
     if any(i.shape[-2:] != (H, W) for i in imgs):
         imgs = [torch.nn.functional.pad(i, (0, W - i.shape[-1], 0, H - i.shape[-2])) for i in imgs]

@@ -253,7 +253,43 @@ class TrainAugment:
         return plan
 
 
-class ViDARSequenceDataset:
+class _FrameImages:
+    """the image half of a frame record, shared by the forecasting and the detection data sets: reads `data_root`,
+    `device_images`, `augment`, `test_mode` and `img_scale` of the data set"""
+
+    def _path(self, p):
+        return str(Path(self.data_root) / p) if self.data_root and not Path(p).is_absolute() else str(p)
+
+    def _frame_images(self, meta, rec, aug_param=None):
+        """load (+ augment, normalise, pad) the camera images of `meta` into `rec`: `img`, or with device_images the raw
+        uint8 frames and the drawn plan; `meta` gets the image shapes (and the scaled lidar2img)"""
+        if self.device_images:
+            from .device_prep import out_shape
+            raw = load_raw_images_u8([self._path(p) for p in meta["img_filename"]])
+            plan = dict(photo=None, resize_dims=None, crop=None, flip=False)
+            if self.augment is not None and not self.test_mode:
+                aug_param = {} if aug_param is None else aug_param
+                plan.update(self.augment.draw(len(raw), meta, aug_param))
+                rec["aug_param"] = aug_param
+            plan["img_scale"] = self.img_scale
+            h, w = out_shape(plan, *raw[0].shape[:2])
+            shape = ((h + 31) // 32 * 32, (w + 31) // 32 * 32, 3)
+            rec["img_raw"], rec["img_plan"], n = torch.from_numpy(np.stack(raw)), plan, len(raw)
+        else:
+            imgs = load_raw_images([self._path(p) for p in meta["img_filename"]])
+            if self.augment is not None and not self.test_mode:
+                aug_param = {} if aug_param is None else aug_param
+                imgs = self.augment(imgs, meta, aug_param)
+                rec["aug_param"] = aug_param
+            img, shape = normalise_pad(imgs, scale=self.img_scale)
+            rec["img"], n = img, img.shape[0]
+        if self.img_scale is not None:                           # transform_3d.py:317-323
+            k = np.eye(4); k[0, 0] = k[1, 1] = self.img_scale
+            meta["lidar2img"] = [k @ np.asarray(a) for a in meta["lidar2img"]]
+        meta.update(img_shape=[shape] * n, pad_shape=[shape] * n, img_norm_cfg=dict(IMG_NORM))
+
+
+class ViDARSequenceDataset(_FrameImages):
     """`dataset[i]` -> dict(img [T, cams, 3, H, W], img_metas {t: meta}, gt_points [P, 5]): the forward_train /
     forward_test kwargs of one sample (collate = add the batch dimension).
     `device_images=True`: the workers only decode and draw -- the sample carries `img_raw` (uint8 [T, cams, H, W, 3], BGR)
@@ -285,9 +321,6 @@ class ViDARSequenceDataset:
     def __len__(self):
         return len(self.usable_index)
 
-    def _path(self, p):
-        return str(Path(self.data_root) / p) if self.data_root and not Path(p).is_absolute() else str(p)
-
     def frame(self, index, with_images=True, aug_param=None):
         """one frame through the pipeline -> record dict(img, points, img_metas[, aug_param])"""
         meta = frame_meta_from_info(copy.deepcopy(self.infos[index]), self.dataset, self.data_root)
@@ -303,31 +336,8 @@ class ViDARSequenceDataset:
             pts[:, -1] = 0                                           # on the LAST column (nuplan_loading.py:283-288)
             pts = voxel_point_sampler(pts, self.voxel_size, self.point_cloud_range, self.max_voxels)
         rec = dict(points=torch.from_numpy(np.ascontiguousarray(pts)), img_metas=meta)
-        if with_images and self.device_images:
-            from .device_prep import out_shape
-            raw = load_raw_images_u8([self._path(p) for p in meta["img_filename"]])
-            plan = dict(photo=None, resize_dims=None, crop=None, flip=False)
-            if self.augment is not None and not self.test_mode:
-                aug_param = {} if aug_param is None else aug_param
-                plan.update(self.augment.draw(len(raw), meta, aug_param))
-                rec["aug_param"] = aug_param
-            plan["img_scale"] = self.img_scale
-            h, w = out_shape(plan, *raw[0].shape[:2])
-            shape = ((h + 31) // 32 * 32, (w + 31) // 32 * 32, 3)
-            rec["img_raw"], rec["img_plan"], n = torch.from_numpy(np.stack(raw)), plan, len(raw)
-        elif with_images:
-            imgs = load_raw_images([self._path(p) for p in meta["img_filename"]])
-            if self.augment is not None and not self.test_mode:
-                aug_param = {} if aug_param is None else aug_param
-                imgs = self.augment(imgs, meta, aug_param)
-                rec["aug_param"] = aug_param
-            img, shape = normalise_pad(imgs, scale=self.img_scale)
-            rec["img"], n = img, img.shape[0]
         if with_images:
-            if self.img_scale is not None:                           # transform_3d.py:317-323
-                k = np.eye(4); k[0, 0] = k[1, 1] = self.img_scale
-                meta["lidar2img"] = [k @ np.asarray(a) for a in meta["lidar2img"]]
-            meta.update(img_shape=[shape] * n, pad_shape=[shape] * n, img_norm_cfg=dict(IMG_NORM))
+            self._frame_images(meta, rec, aug_param)
         return rec
 
     def _prepare(self, index, rand_interval=None):

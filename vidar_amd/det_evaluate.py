@@ -5,7 +5,9 @@
     print(format_summary(result))
 
 `pred` / `gt`: one dict per sample, in the same order, of tensors ON THE DEVICE.  Boxes are [N, 9] rows (x, y, z, three
-sizes, yaw, vx, vy) in the ego-centred frame of their sample -- what NMSFreeCoder decodes into.
+sizes, yaw, vx, vy) in the EGO frame of their sample: the class ranges are distances to the ego origin.  NMSFreeCoder
+decodes into the LiDAR frame and the info files annotate in it, so both sides go through `boxes_to_ego` with the sample's
+lidar2ego calibration first (`ground_truth_from_infos` does it for the annotations of an info pkl).
     pred[i]: boxes [N, 9], scores [N], labels [N] (index into class_names), optional attrs [N] (index into ATTRIBUTES,
              -1 = none; absent: `default_attributes`, the reference's speed heuristic)
     gt[i]:   boxes [G, 9], labels [G], num_pts [G] (lidar + radar points inside the box), optional attrs [G] (absent: none)
@@ -22,7 +24,10 @@ class, threshold) in one launch of csrc/det_eval.hip (vidar_det_eval_match_f32: 
 atomics, deterministic), then one fp64 torch pass per class over small arrays.  There is no CPU path.
 
 NOT applied: the devkit's bike-rack filter (bicycles / motorcycles inside a bike-rack annotation are dropped); it needs
-annotations the info files do not carry."""
+annotations the info files do not carry.
+
+`write_results_json` / `read_results_json`: the decoded boxes in the nuScenes detection submission layout, so that a run
+can be cross-checked with the devkit elsewhere."""
 from __future__ import annotations
 
 import ctypes
@@ -312,8 +317,9 @@ def summarize(label_aps, label_tp_errors, mean_ap_weight=5):
                 tp_errors=tp_errors, tp_scores=tp_scores, nd_score=nd_score, detail=detail)
 
 
-def format_summary(result) -> str:
-    """the devkit's closing table (without its run time)"""
+def format_summary(result, gt_attrs=True) -> str:
+    """the devkit's closing table (without its run time); `gt_attrs=False`: the ground truth came without attributes
+    (`ground_truth_from_infos`), which the table then says"""
     lines = ["mAP: %.4f" % result["mean_ap"]]
     lines += ["%s: %.4f" % (ERR_NAME_MAPPING[e], v) for e, v in result["tp_errors"].items()]
     lines += ["NDS: %.4f" % result["nd_score"], "Per-class results:", "Object Class\tAP\tATE\tASE\tAOE\tAVE\tAAE"]
@@ -321,4 +327,189 @@ def format_summary(result) -> str:
         tp = result["label_tp_errors"][n]
         lines.append("%s\t%.3f\t%.3f\t%.3f\t%.3f\t%.3f\t%.3f" % (n, ap, tp["trans_err"], tp["scale_err"], tp["orient_err"],
                                                                  tp["vel_err"], tp["attr_err"]))
+    if not gt_attrs:
+        lines.append("(the info files carry no attributes: mAAE is 1 by construction and NDS is lower than the devkit's by "
+                     "that term)")
     return "\n".join(lines)
+
+
+# --- from LiDAR-frame boxes and info files to what `evaluate` takes, and the submission file ---------------------------
+MODALITY = dict(use_lidar=False, use_camera=True, use_radar=False, use_map=False, use_external=True)
+
+
+def _rotation_matrices(q):
+    """unit quaternions (w, x, y, z) [..., 4] fp64 -> rotation matrices [..., 3, 3] ([3P] pyquaternion's formula)"""
+    q = q / q.norm(dim=-1, keepdim=True)
+    w, x, y, z = q.unbind(-1)
+    rows = [1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+            2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+            2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]
+    return torch.stack(rows, -1).reshape(*q.shape[:-1], 3, 3)
+
+
+def _quat_mul(a, b):
+    aw, ax, ay, az = a.unbind(-1)
+    bw, bx, by, bz = b.unbind(-1)
+    return torch.stack([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                        aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw], -1)
+
+
+def _f64(a, device):
+    return torch.as_tensor(a, dtype=torch.float64, device=device)
+
+
+def _rigid(boxes, rotation, translation):
+    """fp64: centres R c + t, the heading vector (cos h, sin h, 0) and the velocity (vx, vy, 0) rotated.  The heading
+    angle h = -yaw - pi/2 is formed in fp32, as output_to_nusc_box_det forms it on the fp32 yaw column, then widened."""
+    b = boxes.double()
+    R = _rotation_matrices(_f64(rotation, b.device))
+    t = _f64(translation, b.device)
+    rot = lambda v: (R @ v.unsqueeze(-1)).squeeze(-1)
+    zero = torch.zeros_like(b[:, 0])
+    h = (-boxes[:, 6].float() - math.pi / 2).double()
+    return b, rot(b[:, :3]) + t, rot(torch.stack([torch.cos(h), torch.sin(h), zero], -1)), \
+        rot(torch.stack([b[:, 7], b[:, 8], zero], -1)), h
+
+
+def boxes_to_ego(boxes, rotation, translation):
+    """Rigid transform of box rows [N, 9] (centre, sizes, yaw, vx, vy): the centre is rotated and moved, the velocity
+    (vx, vy, 0) rotated, the sizes untouched; the heading (the x axis of the box, at -yaw - pi/2 in the devkit's
+    convention for these LiDAR-style rows) is rotated and its yaw read off again as the devkit's quaternion_yaw does --
+    for a rotation about z that ADDS the rotation's yaw to the heading, i.e. subtracts it from the row's yaw.
+    `rotation`: unit quaternion(s) (w, x, y, z), [4] or one per box [N, 4]; `translation`: [3] or [N, 3]; both may be lists,
+    arrays or tensors.  Computed in fp64 on the boxes' device, stored as fp32.  With lidar2ego_rotation / _translation of
+    a sample this takes LiDAR-frame boxes to the ego frame (lidar_nusc_box_to_global,
+    UniAD/projects/mmdet3d_plugin/datasets/data_utils/data_utils.py:118-126); feed it gravity-centred rows."""
+    b, c, head, vel, _ = _rigid(boxes, rotation, translation)
+    yaw = -torch.atan2(head[:, 1], head[:, 0]) - math.pi / 2
+    return torch.cat([c, b[:, 3:6], yaw[:, None], vel[:, :2]], 1).float()
+
+
+def ground_truth_from_infos(infos, class_names=CLASS_NAMES, device="cuda"):
+    """the `gt` list of `DetectionEval.evaluate` from the frames of an info pkl (vidar_amd.data.load_infos), one entry per
+    frame in their order: EVERY annotation of the frame whose name is in `class_names` (not the `valid_flag` subset: the
+    evaluator's own num_pts > 0 filter removes the same boxes the devkit removes), `num_pts` = lidar + radar points (lidar
+    alone where the file has no `num_radar_pts`),
+    gravity-centred boxes moved from the LiDAR frame to the ego frame of the sample with `boxes_to_ego`; a NaN velocity
+    stays NaN, as in the devkit (such a match does not count in mAVE).
+    No attributes: the info files carry none.  Every attr_err is then NaN, mAAE is 1 and NDS is lower than the devkit's by
+    that term (1/10 of the devkit's 1 - mAAE)."""
+    import numpy as np
+    if len(infos) == 0:
+        return []
+    class_names = list(class_names)
+    rows, labels, num_pts, quat, trans, counts = [], [], [], [], [], []
+    for info in infos:
+        names = np.asarray(info["gt_names"])
+        keep = np.array([n in class_names for n in names], bool).reshape(-1)
+        box = np.concatenate([np.asarray(info["gt_boxes"], np.float64).reshape(-1, 7),
+                              np.asarray(info["gt_velocity"], np.float64).reshape(-1, 2)], 1)[keep]
+        rows.append(box)
+        labels.append(np.array([class_names.index(n) for n in names[keep]], np.int64))
+        pts = np.asarray(info["num_lidar_pts"], np.int64)
+        if "num_radar_pts" in info:                      # as annotations.ann_info: older info files carry lidar counts only
+            pts = pts + np.asarray(info["num_radar_pts"], np.int64)
+        num_pts.append(pts[keep])
+        quat.append(np.broadcast_to(np.asarray(info["lidar2ego_rotation"], np.float64), (len(box), 4)))
+        trans.append(np.broadcast_to(np.asarray(info["lidar2ego_translation"], np.float64), (len(box), 3)))
+        counts.append(len(box))
+    dev = torch.device(device)
+    boxes = boxes_to_ego(torch.from_numpy(np.concatenate(rows)).float().to(dev), np.concatenate(quat), np.concatenate(trans))
+    labels = torch.from_numpy(np.concatenate(labels)).to(dev)
+    num_pts = torch.from_numpy(np.concatenate(num_pts)).to(dev)
+    return [dict(boxes=b, labels=l, num_pts=n)
+            for b, l, n in zip(boxes.split(counts), labels.split(counts), num_pts.split(counts))]
+
+
+def _attribute_name(name, speed):
+    """the speed rule of _format_bbox_det (nuscenes_e2e_dataset.py:903-922)"""
+    if speed > 0.2:
+        return _MOVING.get(name, DEFAULT_ATTRIBUTE[name])
+    return _STILL.get(name, DEFAULT_ATTRIBUTE[name])
+
+
+def write_results_json(path, tokens, pred, infos, class_names=CLASS_NAMES, config="detection_cvpr_2019", meta=None):
+    """the decoded boxes in the nuScenes detection submission layout: {"meta": ..., "results": {token: [entry, ...]}}, an
+    entry holding sample_token, translation, size, rotation (w, x, y, z), velocity, detection_name, detection_score and
+    attribute_name, boxes in the GLOBAL frame.
+    `pred[i]`: dict(boxes [N, 9] LiDAR-frame rows with the z of the BOTTOM face -- `boxes_3d.tensor` of the detector's
+    result --, scores [N], labels [N]) of the frame `tokens[i]` / `infos[i]`, tensors anywhere.
+    Semantics of output_to_nusc_box_det + lidar_nusc_box_to_global (UniAD/projects/mmdet3d_plugin/datasets/data_utils/
+    data_utils.py:53-132) + _format_bbox_det (nuscenes_e2e_dataset.py:873-945): gravity centre, the yaw -yaw - pi/2 as a
+    quaternion about z, boxes farther from the ego origin than their class range dropped (in the ego frame), then
+    ego2global; the attribute name from the speed in the global frame.  ([3P] the devkit's Box and pyquaternion are
+    restated in fp64.)  -> kept[i]: the rows of pred[i] that were written, in order."""
+    import json
+    import numpy as np
+    from pathlib import Path
+    class_names = list(class_names)
+    ranges = CONFIGS[config]["class_range"] if isinstance(config, str) else config["class_range"]
+    results, kept = {}, []
+    for token, p, info in zip(tokens, pred, infos):
+        if token != info["token"]:
+            raise ValueError(f"write_results_json: prediction of {token!r} paired with the info of {info['token']!r}")
+        box = p["boxes"].detach().cpu().float()
+        box = torch.cat([box[:, :2], (box[:, 2] + box[:, 5] * 0.5)[:, None], box[:, 3:]], 1)      # gravity_center, fp32
+        labels = p["labels"].detach().cpu().long()
+        scores = p["scores"].detach().cpu().float()
+        n = len(box)
+        l2e, e2g = (_f64(info[k], "cpu") for k in ("lidar2ego_rotation", "ego2global_rotation"))
+        b, ego_c, _, ego_v, h = _rigid(box, l2e, info["lidar2ego_translation"])
+        q = torch.stack([torch.cos(h / 2), torch.zeros_like(h), torch.zeros_like(h), torch.sin(h / 2)], -1)
+        q = _quat_mul(e2g.expand(n, 4), _quat_mul(l2e.expand(n, 4), q))
+        radius = torch.sqrt(ego_c[:, 0] * ego_c[:, 0] + ego_c[:, 1] * ego_c[:, 1])
+        keep = ~(radius > _f64([ranges[class_names[int(l)]] for l in labels], "cpu"))
+        R = _rotation_matrices(e2g)
+        glob_c = ego_c @ R.T + _f64(info["ego2global_translation"], "cpu")
+        glob_v = ego_v @ R.T
+        entries = []
+        for i in torch.nonzero(keep).flatten().tolist():
+            name = class_names[int(labels[i])]
+            v = glob_v[i, :2].tolist()
+            entries.append(dict(sample_token=token, translation=glob_c[i].tolist(), size=b[i, 3:6].tolist(),
+                                rotation=q[i].tolist(), velocity=v, detection_name=name, detection_score=float(scores[i]),
+                                attribute_name=_attribute_name(name, float(np.sqrt(v[0] ** 2 + v[1] ** 2)))))
+        results[token] = entries
+        kept.append(torch.nonzero(keep).flatten())
+    Path(path).parent.mkdir(parents=True, exist_ok=True)
+    Path(path).write_text(json.dumps(dict(meta=dict(meta or MODALITY), results=results)))
+    return kept
+
+
+def read_results_json(path, infos=None, class_names=CLASS_NAMES, device="cpu"):
+    """a submission file -> (tokens, pred): pred[i] = dict(boxes [N, 9] fp32 rows with the gravity centre, scores,
+    labels, attrs (index into ATTRIBUTES, -1 for "")) of tokens[i], plus `rotation` [N, 4] fp64 (the file's quaternion;
+    the row's yaw is the devkit's quaternion_yaw of it, brought back to the rows' convention).
+    Without `infos` the frames come in the file's order and the boxes stay in the GLOBAL frame.  With `infos` the result
+    lists THEIR frames in THEIR order (a frame the file lacks is an error) and the boxes are moved into each sample's EGO
+    frame with the inverse of ego2global (on quaternions, so that the file's orientation loses nothing on the way): what
+    `DetectionEval.evaluate` takes next to `ground_truth_from_infos(infos)`.  The layout keeps two components of the
+    global-frame velocity: with a tilted ego2global the vertical one is gone, and the ego-frame velocity read back is off
+    by up to |R[2, :2]| |v_z| from the one `boxes_to_ego` gives the same box."""
+    import json
+    from pathlib import Path
+    class_names = list(class_names)
+    results = json.loads(Path(path).read_text())["results"]
+    tokens = list(results) if infos is None else [info["token"] for info in infos]
+    dev = torch.device(device)
+    pred = []
+    for k, token in enumerate(tokens):
+        if token not in results:
+            raise KeyError(f"{path}: no results for sample {token!r}")
+        ent = results[token]
+        col = lambda key, width: _f64([e[key] for e in ent], "cpu").reshape(len(ent), width)
+        c, size, q, v = col("translation", 3), col("size", 3), col("rotation", 4), col("velocity", 2)
+        if infos is not None:
+            inv = _f64(infos[k]["ego2global_rotation"], "cpu") * _f64([1.0, -1.0, -1.0, -1.0], "cpu")
+            R = _rotation_matrices(inv)
+            c = (c - _f64(infos[k]["ego2global_translation"], "cpu")) @ R.T
+            v = (torch.cat([v, torch.zeros(len(ent), 1, dtype=torch.float64)], 1) @ R.T)[:, :2]
+            q = _quat_mul(inv.expand(len(ent), 4), q)
+        head = _rotation_matrices(q)[:, :, 0] if len(ent) else torch.zeros(0, 3, dtype=torch.float64)
+        yaw = -torch.atan2(head[:, 1], head[:, 0]) - math.pi / 2
+        pred.append(dict(boxes=torch.cat([c, size, yaw[:, None], v], 1).float().to(dev), rotation=q,
+                         scores=torch.tensor([e["detection_score"] for e in ent], dtype=torch.float32, device=dev),
+                         labels=torch.tensor([class_names.index(e["detection_name"]) for e in ent], dtype=torch.int64,
+                                             device=dev),
+                         attrs=torch.tensor([_attr_id(e["attribute_name"]) for e in ent], dtype=torch.int32, device=dev)))
+    return tokens, pred

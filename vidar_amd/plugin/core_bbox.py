@@ -8,8 +8,9 @@ Restated from the reference's own files:
 Third party, recalled, unpinned (mmdet / mmdet3d are not vendored in the reference):
   * FocalLossCost (mmdet.core.bbox.match_costs, eps 1e-12, sigmoid form), IoUCost (accepted with weight 0 only),
   * AssignResult / PseudoSampler semantics (positives = queries with a 1-based gt index > 0),
-  * LiDARInstance3DBoxes (mmdet3d): `tensor [G, 7|9]` with a BOTTOM-centred z, `gravity_center` lifts z by half the
-    height, `to(device)`, `__len__`;  bbox3d2result: dict(boxes_3d, scores_3d, labels_3d) on the CPU."""
+  * LiDARInstance3DBoxes (mmdet3d): `tensor [G, 7|9]` with a BOTTOM-centred z (`origin` names where the given centre
+    sits inside the box, (0.5, 0.5, 0.5) = gravity centre), `gravity_center` lifts z by half the height, `to(device)`,
+    `__len__`;  bbox3d2result: dict(boxes_3d, scores_3d, labels_3d) on the CPU."""
 from __future__ import annotations
 
 import torch
@@ -50,7 +51,10 @@ class LiDARInstance3DBoxes:
         tensor = torch.as_tensor(tensor, dtype=torch.float32)
         if tensor.numel() == 0:
             tensor = tensor.reshape((0, box_dim or (tensor.size(-1) if tensor.dim() == 2 else 7)))
-        assert tensor.dim() == 2 and tensor.size(-1) in (7, 9) and tuple(origin) == (0.5, 0.5, 0)
+        assert tensor.dim() == 2 and tensor.size(-1) in (7, 9) and len(origin) == 3
+        if tuple(origin) != (0.5, 0.5, 0):          # another reference point of the centre: move it to the bottom face
+            tensor = tensor.clone()
+            tensor[:, :3] += tensor[:, 3:6] * (tensor.new_tensor((0.5, 0.5, 0)) - tensor.new_tensor(origin))
         self.tensor = tensor
         self.box_dim = tensor.size(-1)
 
