@@ -418,6 +418,26 @@ int vidar_ray_max_k(void);
  * other thread launch from then on (same results, different time), so production code leaves it alone. */
 int vidar_ray_force_streamed(int on);
 
+/* Camera-view arg-max march (csrc/ray_march.hip, pixel -> ray in csrc/cam_ray.h): the decode of vidar_ray_argmax_f32
+ * with one ray per pixel of C cameras, generated in the kernel instead of read from a list.
+ *   pix2vox [F,C,4,4] row-major f32 maps the homogeneous pixel (u*d, v*d, d, 1) to voxel coordinates of frame f's
+ *           volume.  It is affine (the inverse of a camera matrix with last row 0 0 0 1): only rows 0..2 are read.
+ *   pixel (x, y) of the [Hs, Ws] grid has u = u0 + x*du, v = v0 + y*dv (fp32, each operation rounded on its own).
+ *   The camera centre is the image of (0,0,0,1), the ray's end point the image of (u,v,1,1); from the end point on
+ *   the march is vidar_ray_argmax_f32's own body (K == 512 register-resident, every other K streamed).
+ *   dist [F,C,Hs,Ws] f32, voxel units: the length of the arg-max waypoint; 0 for a ray without a live waypoint (all
+ *           outside the volume, or on exact zeros of it).  The only store of the kernel, no atomics.
+ * vidar_cam_rays_f32 writes out what the fused kernel marches -- origin [F,C,3], pts [F,C,Hs,Ws,3] -- from the same
+ * device function, so vidar_ray_argmax_f32 per camera on (origin[:,c], pts[:,c], tindex = f) gives the fused kernel's
+ * bits on every ray with a live waypoint (a ray without one gets waypoint 0's length there, the reference's answer).
+ * F, C <= 0, negative Hs / Ws, a NaN or zero pixel pitch, F*C*Hs*Ws beyond the 32-bit ray index, or bad volume / K
+ * (as above) return VIDAR_ERR_BAD_ARG; an empty grid returns 0 without a launch. */
+int vidar_ray_argmax_cam_f32(const float* sigma, const float* pix2vox, float* dist, int F, int C, int Hs, int Ws,
+                             float u0, float v0, float du, float dv, int Z, int Y, int X, int K, float step,
+                             void* stream);
+int vidar_cam_rays_f32(const float* pix2vox, float* origin, float* pts, int F, int C, int Hs, int Ws, float u0,
+                       float v0, float du, float dv, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Modulated deformable convolution v2 (backbone, "next" row SURVEY 8f-1).  Replaces the sampling
  * kernels of mmcv.ops.ModulatedDeformConv2dPack (mmcv-full 1.4.0, third party); the convolution

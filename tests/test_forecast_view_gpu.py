@@ -1,0 +1,247 @@
+"""GPU: the camera-view arg-max march (vidar_ray_argmax_cam_f32 / vidar_cam_rays_f32, csrc/ray_march.hip + cam_ray.h)
+and the forecast API on top of it (ViDARHeadBase.render_rays / render_cameras, ViDAR.forecast).
+
+1. fused == materialised, bit for bit: the fused kernel against vidar_ray_argmax_f32 run per camera on the rays
+   vidar_cam_rays_f32 wrote.  ONE documented difference is applied to the materialised side: a ray without a live waypoint
+   gives 0 in the camera march ("no return"), while vidar_ray_argmax_f32 keeps the reference's answer there (torch.max
+   over all -inf picks waypoint 0, so it returns waypoint 0's length) and is not to change.  Which rays those are is
+   decided by neither kernel: the torch-CPU restatement of the reference's decode (oracle/head.py: the same waypoints,
+   F.grid_sample, `== 0`) says for every ray whether any waypoint samples a non-zero value.
+2. geometry: a volume with one high-logit plane; per-pixel distance against the analytic ray-plane distance.
+3. pix2vox round trip through the fp64 projection.
+4. render_rays on the ground-truth rays == get_point_cloud_prediction, bit for bit.
+5. ViDAR.forecast runs without gt_points.
+Shapes are the smallest that still take every path: 4 x 12 x 14 voxels, F = C = 2, 12 x 20 and 13 x 21 pixels (no multiple
+of the 4 rays of a block), K = 512 (register form) and 37 (streamed, no multiple of 64)."""
+import math
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import head as H
+from forecast_view_cases import C, F_, GRIDS, X, Y, Z, camera, camera_set, volume
+
+pytestmark = pytest.mark.gpu
+GRID_IDS = ["12x20-stride1", "13x21-stride4"]
+MARCHES = [(512, 1.0), (512, 0.5), (37, 1.0), (37, 0.5)]
+
+
+def materialised(sigma, m, grid, K, step):
+    """vidar_ray_argmax_f32 per camera on the output of vidar_cam_rays_f32 -> (dist [F,C,Hs,Ws], origin, pts)"""
+    from vidar_amd.plugin.dense_heads.ray_ops import cam_rays, ray_argmax
+    Hs, Ws, u0, v0, du, dv = grid
+    origin, pts = cam_rays(m, (Hs, Ws), u0, v0, du, dv)
+    n_f, n_c = m.shape[:2]
+    tindex = torch.arange(n_f, device=m.device, dtype=torch.float32).repeat_interleave(Hs * Ws)
+    out = torch.empty(n_f, n_c, Hs, Ws, device=m.device)
+    for c in range(n_c):
+        pred, _ = ray_argmax(sigma, origin[:, c].contiguous(), pts[:, c].reshape(-1, 3).contiguous(), tindex, step, K)
+        out[:, c] = pred.view(n_f, Hs, Ws)
+    return out, origin, pts
+
+
+def live_rays(sigma, origin, pts, K, step):
+    """[F,C,Hs,Ws] bool on the CPU: does any of the ray's K waypoints sample a non-zero value?  The reference's decode
+    (vidar_head_base.py:716-728) restated by oracle/head.py; no kernel of the product is involved."""
+    n_f, n_c, Hs, Ws, _ = pts.shape
+    zs, ys, xs = sigma.shape[1:]
+    live = torch.zeros(n_f, n_c, Hs, Ws, dtype=torch.bool)
+    for f in range(n_f):
+        for c in range(n_c):
+            g, _ = H._waypoints(origin[f, c].view(1, 3), pts[f, c].reshape(-1, 3), K, step, with_end=False)
+            gn = H._normalise(g, zs, ys, xs)
+            s = F.grid_sample(sigma[f].view(1, 1, zs, ys, xs), gn.view(1, 1, *gn.shape),
+                              align_corners=False).view(gn.shape[0], -1)
+            live[f, c] = (s != 0).any(1).view(Hs, Ws)
+    return live
+
+
+@pytest.mark.parametrize("K,step", MARCHES, ids=[f"K{k}-step{s}" for k, s in MARCHES])
+@pytest.mark.parametrize("grid", GRIDS, ids=GRID_IDS)
+def test_fused_march_equals_materialised_march_bit_for_bit(grid, K, step):
+    from vidar_amd.plugin.dense_heads.ray_ops import ray_argmax_cam
+    Hs, Ws, u0, v0, du, dv = grid
+    sigma, m = volume().cuda(), camera_set().cuda()
+    fused = ray_argmax_cam(sigma, m, (Hs, Ws), u0, v0, du, dv, step, K)
+    assert fused.shape == (F_, C, Hs, Ws)
+    mat, origin, pts = materialised(sigma, m, grid, K, step)
+    assert torch.equal(origin.cpu(), camera_set()[..., :3, 3])
+    live = live_rays(volume(), origin.cpu(), pts.cpu(), K, step)
+    # camera (1, 0) looks away from the volume: every ray misses; camera (0, 1) sits inside: every ray has a live waypoint
+    assert not bool(live[1, 0].any()) and bool(live[0, 1].all())
+    assert bool(live[0, 0].any()) and bool(live[1, 1].any())
+    want = torch.where(live, mat.cpu(), torch.zeros(()))
+    got = fused.cpu()
+    print(f"rays {live.numel()}, live {int(live.sum())}, differing {int((got != want).sum())}")
+    assert torch.equal(got, want)
+    assert float(got[1, 0].abs().max()) == 0.0                     # all zeros, and +0
+    assert bool((got[live] > 0).all())
+    # where the materialised decode differs from the camera march it returned waypoint 0, as the reference does
+    miss = ~live
+    w0 = torch.sqrt(((H._waypoints(origin[1, 0].cpu().view(1, 3), pts[1, 0].cpu().reshape(-1, 3), 1, step,
+                                   with_end=False)[0][:, 0] - origin[1, 0].cpu().view(1, 3)) ** 2).sum(-1))
+    torch.testing.assert_close(mat.cpu()[1, 0].reshape(-1), w0, rtol=1e-5, atol=1e-6)
+    assert bool(miss[1, 0].all())
+
+
+def test_k512_streamed_form_gives_the_register_forms_bits():
+    from vidar_amd.plugin.dense_heads.ray_ops import force_streamed, ray_argmax_cam
+    Hs, Ws, u0, v0, du, dv = GRIDS[1]
+    sigma, m = volume().cuda(), camera_set().cuda()
+    a = ray_argmax_cam(sigma, m, (Hs, Ws), u0, v0, du, dv, 0.5, 512)
+    with force_streamed():
+        b = ray_argmax_cam(sigma, m, (Hs, Ws), u0, v0, du, dv, 0.5, 512)
+    assert torch.equal(a, b)
+
+
+# ---- 2. geometry ---------------------------------------------------------------------------------------------------
+PLANE_X = 6                                   # the voxel layer; trilinear samples peak on its centre plane x = 6.5
+PLANE_CAM = dict(centre=(-2.0, 3.0, 1.5), forward=(1.0, 0.0, 0.0), focal=40.0, principal=(10.0, 6.0))
+PLANE_GRIDS = [(12, 20, 0.5, 0.5, 1.0, 1.0), (13, 21, -11.0, -7.0, 2.0, 2.0)]
+
+
+def plane_model(m64, grid, K, step):
+    """fp64, from the inputs alone: (t [Hs,Ws] distance from the camera centre to the plane x = PLANE_X + 0.5 along each
+    pixel's ray, meets [Hs,Ws]: the crossing lies inside the volume's y / z extent and within reach of the K waypoints)"""
+    Hs, Ws, u0, v0, du, dv = grid
+    u = u0 + np.arange(Ws) * du
+    v = v0 + np.arange(Hs) * dv
+    uu, vv = np.meshgrid(u, v)
+    pix = np.stack([uu, vv, np.ones_like(uu), np.ones_like(uu)], -1)
+    p = pix @ m64[:3].T
+    o = m64[:3, 3]
+    d = (p - o) / np.linalg.norm(p - o, axis=-1, keepdims=True)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = (PLANE_X + 0.5 - o[0]) / d[..., 0]
+    hit = o + t[..., None] * d
+    meets = (t > 0) & (t < K * step) & (hit[..., 1] > 0) & (hit[..., 1] < Y) & (hit[..., 2] > 0) & (hit[..., 2] < Z)
+    return t, meets, d
+
+
+@pytest.mark.parametrize("K,step", [(512, 1.0), (37, 0.5)], ids=["K512-step1", "K37-step0.5"])
+@pytest.mark.parametrize("grid", PLANE_GRIDS, ids=["12x20", "13x21-stride2"])
+def test_distance_to_a_plane_of_high_logits(grid, K, step):
+    """The arg-max waypoint has a positive sample, so it lies less than one voxel from the plane in x, i.e. less than
+    1 / |d_x| <= 1.21 voxels from the crossing along these rays (|d_x| >= 0.83 for this camera); the bound asked for is
+    one waypoint spacing plus one voxel diagonal."""
+    from vidar_amd.plugin.dense_heads.ray_ops import ray_argmax_cam
+    Hs, Ws, u0, v0, du, dv = grid
+    m64 = camera(**PLANE_CAM)
+    t, meets, d = plane_model(m64, grid, K, step)
+    assert meets.mean() >= 0.5, meets.mean()                     # the analytic model alone: at least half the pixels
+    assert np.abs(d[..., 0]).min() >= 0.83
+    sigma = torch.full((1, Z, Y, X), -1.0)
+    sigma[:, :, :, PLANE_X] = 100.0
+    m = torch.from_numpy(m64).float().view(1, 1, 4, 4)
+    dist = ray_argmax_cam(sigma.cuda(), m.cuda(), (Hs, Ws), u0, v0, du, dv, step, K)[0, 0].cpu().double().numpy()
+    bound = step + math.sqrt(3.0)
+    err = np.abs(dist - t)[meets]
+    print(f"pixels {meets.size}, meeting the plane {int(meets.sum())}, max |dist - t| {err.max():.4f}, bound {bound:.4f}")
+    assert (err <= bound).all()
+    assert (dist[meets] > 0).all()
+
+
+# ---- 3. pix2vox round trip -------------------------------------------------------------------------------------------
+def test_pix2vox_round_trip_through_the_fp64_projection():
+    """64 voxel points that project onto pixel centres: the ray vidar_cam_rays_f32 writes for that pixel passes within
+    the fp32 rounding of the point's 4 x 4 product.  With o, p the exact origin and depth-1 point and the point at depth d
+    P = o + d (p - o), the written ray passes through o + e_o and p + e_p, hence within |1 - d| |e_o| + d |e_p| of P, where
+    per coordinate i  |e_o,i| <= 2^-24 |M_i3| (the entry's rounding) and |e_p,i| <= 6 * 2^-24 * sum_j |M_ij| |x_j|
+    (the entry's rounding, one product and at most three sums of partial results no larger than that sum, one spare)."""
+    from vidar_amd import forecast as FC
+    from vidar_amd.plugin.dense_heads.ray_ops import cam_rays
+    from vidar_amd.synthetic import PC_RANGE, camera_matrices
+    bev, pillar, stride = 200, 16, 4
+    l2i = camera_matrices()                                        # [8, 4, 4] fp64, 928 x 1600 images
+    n_c = l2i.shape[0]
+    Hs, Ws = 928 // stride, 1600 // stride
+    u0 = v0 = stride / 2.0
+    to_vox = np.eye(4)
+    for a, n in enumerate((bev, bev, pillar)):
+        span = PC_RANGE[a + 3] - PC_RANGE[a]
+        to_vox[a, a] = n / span
+        to_vox[a, 3] = -PC_RANGE[a] * n / span
+    m64 = np.stack([to_vox @ np.linalg.inv(l2i[c]) for c in range(n_c)])          # pixel -> voxel, fp64
+    m32 = FC.pix2vox(l2i, PC_RANGE, bev, bev, pillar)
+    assert m32.shape == (1, n_c, 4, 4)
+    np.testing.assert_array_equal(m32[0].numpy(), m64.astype(np.float32))         # fp64 composition, rounded once
+    origin, pts = cam_rays(m32.cuda(), (Hs, Ws), u0, v0, float(stride), float(stride))
+    origin, pts = origin.cpu().double().numpy()[0], pts.cpu().double().numpy()[0]
+    rng = np.random.default_rng(1)
+    worst = 0.0
+    for _ in range(64):
+        c, x, y = int(rng.integers(n_c)), int(rng.integers(Ws)), int(rng.integers(Hs))
+        depth = float(rng.uniform(0.5, 60.0))
+        u, v = u0 + x * stride, v0 + y * stride
+        pix = np.array([u * depth, v * depth, depth, 1.0])
+        P = (m64[c] @ pix)[:3]                                                    # the known voxel point
+        back = l2i[c] @ np.linalg.inv(to_vox) @ np.append(P, 1.0)                 # voxel -> metric -> image, fp64
+        assert round((back[0] / back[2] - u0) / stride) == x and round((back[1] / back[2] - v0) / stride) == y
+        o, p = origin[c], pts[c, y, x]
+        line = (p - o) / np.linalg.norm(p - o)
+        away = (P - o) - np.dot(P - o, line) * line
+        mag = np.abs(m64[c, :3]) @ np.array([abs(u), abs(v), 1.0, 1.0])
+        bound = np.linalg.norm(abs(1 - depth) * 2.0 ** -24 * np.abs(m64[c, :3, 3]) + depth * 6 * 2.0 ** -24 * mag)
+        worst = max(worst, np.linalg.norm(away) / bound)
+        assert np.linalg.norm(away) <= bound, (c, x, y, depth, np.linalg.norm(away), bound)
+    print(f"largest distance / bound over 64 points: {worst:.3f}")
+
+
+# ---- 4. / 5. the head and the detector ---------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def small_model():
+    from vidar_amd import train as T
+    from vidar_amd.configs import get_config
+    from vidar_amd.synthetic import fpn_features, make_sample
+    torch.manual_seed(0); np.random.seed(0)
+    cfg = get_config("vidar_1_8_nusc_3future", bev_h=24, bev_w=24)     # the reduced BEV of tests/test_step_gpu.py
+    metas, gt = make_sample(0, rays_per_frame=200, future_frames=6)     # GT clouds for the 6 test futures
+    feats = [f.cuda() for f in fpn_features(0, 5, shapes=[(15, 25), (8, 13), (4, 7), (2, 4)])]
+    model = T.build_model(cfg).cuda().eval()
+    return model, [metas], [torch.from_numpy(gt).cuda()], feats
+
+
+def test_render_rays_on_the_ground_truth_rays_is_the_decode(small_model):
+    model, metas, gt, feats = small_model
+    with torch.no_grad():
+        pred_dict, cur_metas = model._future_pred_dict(metas, None, feats)
+    geom = dict(tgt_bev_h=model.bev_h, tgt_bev_w=model.bev_w, tgt_pc_range=model.point_cloud_range)
+    head = model.future_pred_head
+    decode = head.get_point_cloud_prediction(pred_dict, gt, 0, img_metas=cur_metas, **geom)
+    rendered = head.render_rays(pred_dict, end_points=gt, img_metas=cur_metas, **geom)
+    assert len(rendered) == 1 and len(rendered[0]) == len(decode["pred_pcds"][0]) == 7
+    for a, b in zip(rendered[0], decode["pred_pcds"][0]):
+        assert a.shape == (200, 3) and torch.equal(a, b)
+    with pytest.raises(ValueError):
+        head.render_rays(pred_dict, **geom)
+    with pytest.raises(ValueError):
+        head.render_rays(pred_dict, directions=torch.zeros(1, 3), end_points=gt, **geom)
+
+
+def test_forecast_needs_no_ground_truth(small_model):
+    from vidar_amd import forecast as FC
+    model, metas, _, feats = small_model
+    rays = FC.lidar_pattern(4, 16)
+    out = model.forecast(img_metas=metas, img_feats=feats, rays=rays, cameras=[0, 3], stride=32)
+    assert out["valid_frames"] == list(range(7))
+    assert len(out["sweep"]) == 1 and len(out["sweep"][0]) == 7
+    lo = torch.tensor(model.point_cloud_range[:3]); hi = torch.tensor(model.point_cloud_range[3:])
+    for pts, idx in zip(out["sweep"][0], out["sweep_index"][0]):
+        pts, idx = pts.cpu(), idx.cpu()
+        assert pts.dim() == 2 and pts.shape[1] == 3 and 0 < pts.shape[0] <= 64 and idx.shape == (pts.shape[0],)
+        assert bool(torch.isfinite(pts).all())
+        assert bool(((pts >= lo) & (pts <= hi)).all())
+        assert bool((idx[1:] > idx[:-1]).all()) and int(idx.min()) >= 0 and int(idx.max()) < 64
+        # a kept point lies on its ray: the direction from the sensor origin (the frame's own LiDAR centre, |o| ~ 0)
+        unit = pts / pts.norm(dim=1, keepdim=True)
+        assert float((unit - rays[idx]).abs().max()) < 1e-3
+    depth = out["depth"].cpu()
+    assert depth.shape == (1, 7, 2, 29, 50)                        # ceil(928 / 32) x ceil(1600 / 32)
+    assert bool(torch.isfinite(depth).all()) and float(depth.min()) >= 0.0 and float(depth.max()) > 0.0
+    # nothing can be further than the volume's diagonal in the decode's own scale
+    cell = (model.point_cloud_range[3] - model.point_cloud_range[0]) / model.bev_w
+    assert float(depth.max()) <= cell * math.sqrt(24 ** 2 + 24 ** 2 + 16 ** 2) + cell
+    only = model.forecast(img_metas=metas, img_feats=feats, rays=rays)
+    assert "depth" not in only and all(torch.equal(a, b) for a, b in zip(only["sweep"][0], out["sweep"][0]))

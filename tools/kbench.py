@@ -932,6 +932,64 @@ def bench_imgprep(which):
                host_images_timed=k, host_threads=torch.get_num_threads())
 
 
+def bench_forecast_view(which):
+    """the camera-view decode of one predicted frame at 200 x 200 x 16, K = 512, step 1: 6 cameras of 900 x 1600 pixels at
+    strides 1 / 2 / 4, the fused entry (vidar_ray_argmax_cam_f32: the rays are never stored) against the materialised
+    route (vidar_cam_rays_f32, then vidar_ray_argmax_f32 once per camera) in the same process on the same build.  HIP
+    events, the two routes alternating, three repeats of 2 warm-up + 5 timed calls each; the spread is (max - min) /
+    median over the repeats.  Writes profiles/kbench_forecast_view.md."""
+    from vidar_amd import forecast as FC
+    from vidar_amd.plugin.dense_heads.ray_ops import cam_rays, ray_argmax, ray_argmax_cam
+    from vidar_amd.synthetic import PC_RANGE, camera_matrices
+    dev = torch.device("cuda", 0)
+    Z, Y, X, C, H, W, K = 16, 200, 200, 6, 900, 1600, 512
+    sigma = torch.randn(1, Z, Y, X, generator=torch.Generator().manual_seed(0)).to(dev)
+    m = FC.pix2vox(camera_matrices(img_hw=(H, W))[:C], PC_RANGE, Y, X, Z).to(dev)
+    rows = []
+    for stride in (1, 2, 4):
+        Hs, Ws = -(-H // stride), -(-W // stride)
+        geom = ((Hs, Ws), stride / 2.0, stride / 2.0, float(stride), float(stride))
+        tindex = torch.zeros(Hs * Ws, device=dev)
+
+        def fused():
+            return ray_argmax_cam(sigma, m, *geom, 1.0, K)
+
+        def two_launch():
+            origin, pts = cam_rays(m, *geom)
+            return [ray_argmax(sigma, origin[:, c].contiguous(), pts[0, c].reshape(-1, 3), tindex, 1.0, K)[0]
+                    for c in range(C)]
+        a, b = fused(), torch.stack(two_launch()).view(1, C, Hs, Ws)
+        live = a != 0
+        same = bool(torch.equal(a[live], b[live]))
+        fs, ts = [], []
+        for _ in range(3):
+            fs.append(timeit(fused, warm=2, it=5)); ts.append(timeit(two_launch, warm=2, it=5))
+        med = lambda v: float(np.median(v))
+        spread = lambda v: (max(v) - min(v)) / med(v)
+        rays = C * Hs * Ws
+        row = dict(stride=stride, rays=rays, ray_bytes_MB=round(rays * 12 / 1e6, 1), fused_ms=[round(v, 3) for v in fs],
+                   two_launch_ms=[round(v, 3) for v in ts], fused_median_ms=round(med(fs), 3),
+                   two_launch_median_ms=round(med(ts), 3), fused_spread=round(spread(fs), 4),
+                   two_launch_spread=round(spread(ts), 4), fused_over_two_launch=round(med(fs) / med(ts), 4),
+                   live_rays=int(live.sum()), same_bits_on_live_rays=same)
+        rows.append(row)
+        report("forecast_view", med(fs), **row)
+    out = os.environ.get("VIDAR_KBENCH_OUT")
+    path = Path(out) if out else ROOT / "profiles" / "kbench_forecast_view.md"
+    path.write_text(
+        "# Camera-view decode on an MI355X: `python tools/kbench.py forecast_view`\n\n"
+        f"One predicted frame, volume {Z} x {Y} x {X}, K = {K}, step 1, {C} cameras of {H} x {W} pixels (the pin-hole rig of\n"
+        "`vidar_amd.synthetic.camera_matrices`), random-normal logits.  `fused`: `vidar_ray_argmax_cam_f32`;\n"
+        "`two_launch`: `vidar_cam_rays_f32` + `vidar_ray_argmax_f32` per camera (7 launches, the rays written and read back).\n"
+        "HIP events, the routes alternating, 3 repeats of 2 warm-up + 5 timed calls; spread = (max - min) / median.\n\n"
+        "```\n" + json.dumps({"device": torch.cuda.get_device_name(0)}) + "\n"
+        + "\n".join(json.dumps(dict(op="forecast_view", **r)) for r in rows) + "\n```\n\n"
+        "| stride | rays | rays as [R,3] fp32 | fused ms (median) | two-launch ms (median) | fused / two-launch | spread fused | spread two-launch |\n"
+        "|---|---|---|---|---|---|---|---|\n"
+        + "".join(f"| {r['stride']} | {r['rays']} | {r['ray_bytes_MB']} MB | {r['fused_median_ms']} | {r['two_launch_median_ms']} | "
+                  f"{r['fused_over_two_launch']} | {r['fused_spread']} | {r['two_launch_spread']} |\n" for r in rows))
+
+
 if __name__ == "__main__":
     import os
     if os.environ.get("VIDAR_MSDA_ITEM_ORDER") is not None:          # A/B of the gather kernels' item order (0 banded, 1 head-major)

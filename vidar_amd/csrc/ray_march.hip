@@ -7,6 +7,8 @@
 //   ray_argmax  : test-time decode in get_point_cloud_prediction (:697-731)
 //   ray_dist    : the use_dist_loss branch (:575-585): _custom_gumbel_softmax_distance over the K + 1 logits
 //                 {end point, K waypoints} of the GT rays
+//   ray_argmax_cam : ray_argmax on rays that are a function of (frame, camera, pixel) and are never stored
+//                 (cam_ray.h; no counterpart in the reference); cam_rays writes those rays out
 // The reference materialises ~8 arrays of [rays, 513] floats per call (waypoints, lengths, masks,
 // sampled logits, -inf masks, softmax); here one wave owns one ray, its 512 waypoints live in
 // registers (8 per lane) and only O(1) values per ray ever reach HBM.
@@ -40,6 +42,7 @@
 #include "vidar_common.h"
 #include "scatter_copies.h"
 #include "det_scatter.h"
+#include "cam_ray.h"
 
 namespace {
 
@@ -58,19 +61,53 @@ struct Ray {
   int f;                          // frame slot, -1 = skip
 };
 
-__device__ __forceinline__ Ray load_ray(const float* __restrict__ origin,
-                                        const float* __restrict__ pts,
-                                        const float* __restrict__ tindex, int r, const VolDims& v) {
-  Ray ray;
-  const float t = tindex[r];
-  ray.f = (t >= 0.f && t < (float)v.F) ? (int)t : -1;   // NaN / -1 padding -> skip
-  const int f = ray.f < 0 ? 0 : ray.f;
-  ray.ox = origin[f * 3 + 0]; ray.oy = origin[f * 3 + 1]; ray.oz = origin[f * 3 + 2];
-  ray.px = pts[(size_t)r * 3 + 0]; ray.py = pts[(size_t)r * 3 + 1]; ray.pz = pts[(size_t)r * 3 + 2];
+// Where a kernel's rays come from: the ray-source policy of load_ray.  Either source hands over a frame slot, an fp32
+// origin and an fp32 end point; the unit direction is derived from those two in one place (aim), so a ray read from a
+// list and the same ray generated from its pixel march with the same bits.
+// kTarget: the end point is a measured target -- the decode also reports |p - o|, and a ray without a live waypoint keeps
+// the reference's answer (torch.max over all -inf picks waypoint 0).  A camera ray's end point is only the point at
+// depth 1: nothing to report, and a ray without a live waypoint gives 0, "no return".
+struct ListedRays {       // origin [F,3], pts [R,3], tindex [R]: every op of the head
+  static constexpr bool kTarget = true;
+  const float* __restrict__ origin;
+  const float* __restrict__ pts;
+  const float* __restrict__ tindex;
+};
+struct CameraRays {       // ray r = pixel (f, c, y, x) of [F, C, Hs, Ws] through pix2vox [F,C,4,4] (cam_ray.h)
+  static constexpr bool kTarget = false;
+  const float* __restrict__ pix2vox;
+  vidar_cam::CamGrid g;
+};
+
+__device__ __forceinline__ void aim(Ray& ray) {
   const float rx = ray.px - ray.ox, ry = ray.py - ray.oy, rz = ray.pz - ray.oz;
   const float n = sqrtf(rx * rx + ry * ry + rz * rz);
   ray.dx = rx / n; ray.dy = ry / n; ray.dz = rz / n;
+}
+
+__device__ __forceinline__ Ray load_ray(const ListedRays& s, int r, const VolDims& v) {
+  Ray ray;
+  const float t = s.tindex[r];
+  ray.f = (t >= 0.f && t < (float)v.F) ? (int)t : -1;   // NaN / -1 padding -> skip
+  const int f = ray.f < 0 ? 0 : ray.f;
+  ray.ox = s.origin[f * 3 + 0]; ray.oy = s.origin[f * 3 + 1]; ray.oz = s.origin[f * 3 + 2];
+  ray.px = s.pts[(size_t)r * 3 + 0]; ray.py = s.pts[(size_t)r * 3 + 1]; ray.pz = s.pts[(size_t)r * 3 + 2];
+  aim(ray);
   return ray;
+}
+__device__ __forceinline__ Ray load_ray(const CameraRays& s, int r, const VolDims&) {
+  int fc, x, y;
+  Ray ray;
+  vidar_cam::split_ray_index(r, s.g, ray.f, fc, x, y);
+  const vidar_cam::CamRay c = vidar_cam::pixel_ray(s.pix2vox + (size_t)fc * 16, s.g, x, y);
+  ray.ox = c.ox; ray.oy = c.oy; ray.oz = c.oz;
+  ray.px = c.px; ray.py = c.py; ray.pz = c.pz;
+  aim(ray);
+  return ray;
+}
+__device__ __forceinline__ Ray load_ray(const float* __restrict__ origin, const float* __restrict__ pts,
+                                        const float* __restrict__ tindex, int r, const VolDims& v) {
+  return load_ray(ListedRays{origin, pts, tindex}, r, v);
 }
 
 struct Tri {
@@ -321,26 +358,29 @@ __device__ __forceinline__ void ray_sample_fwd_body(
   }
 }
 
-// test-time decode (:697-731): arg-max waypoint -> distance
-template <bool K512>
+// test-time decode (:697-731): arg-max waypoint -> distance.  `src` is the ray source: the listed rays of the head's
+// decode, or a camera grid (gt_dist is not touched; see kTarget).
+template <bool K512, class Src>
 __device__ __forceinline__ void ray_argmax_body(
-    const float* __restrict__ sigma, const float* __restrict__ origin, const float* __restrict__ pts,
-    const float* __restrict__ tindex, float* __restrict__ pred_dist, float* __restrict__ gt_dist,
+    const float* __restrict__ sigma, const Src& src, float* __restrict__ pred_dist, float* __restrict__ gt_dist,
     int R, VolDims v, float step, int K) {
   const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
   if (r >= R) return;
   const int lane = threadIdx.x % kWave;
-  const Ray ray = load_ray(origin, pts, tindex, r, v);
+  const Ray ray = load_ray(src, r, v);
   float o_pred = 0.f, o_gt = 0.f;
   if (ray.f >= 0) {
     Waypoints<K512, false> w{sigma + (size_t)ray.f * v.Z * v.Y * v.X, ray, v, step, lane, K};
     Best best;
     w.first([&](int k, float z, float len) { best.take(z, k, len); });
     wave_argmax(best);
-    o_pred = best.len;
+    o_pred = (!Src::kTarget && best.v == kNegInf) ? 0.f : best.len;
     o_gt = dist_to(ray, ray.px, ray.py, ray.pz);
   }
-  if (lane == 0) { pred_dist[r] = o_pred; gt_dist[r] = o_gt; }
+  if (lane == 0) {
+    pred_dist[r] = o_pred;
+    if (Src::kTarget) gt_dist[r] = o_gt;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -461,11 +501,32 @@ RAY_KERNEL ray_dist_bwd_kernel(RAY_IN, const float* __restrict__ aux, const floa
 
 RAY_KERNEL ray_argmax_kernel(RAY_IN, float* __restrict__ pred_dist, float* __restrict__ gt_dist, int R, VolDims v,
                              float step) {
-  ray_argmax_body<true>(sigma, origin, pts, tindex, pred_dist, gt_dist, R, v, step, kK);
+  ray_argmax_body<true>(sigma, ListedRays{origin, pts, tindex}, pred_dist, gt_dist, R, v, step, kK);
 }
 RAY_KERNEL ray_argmax_any_kernel(RAY_IN, float* __restrict__ pred_dist, float* __restrict__ gt_dist, int R, VolDims v,
                                  float step, int K) {
-  ray_argmax_body<false>(sigma, origin, pts, tindex, pred_dist, gt_dist, R, v, step, K);
+  ray_argmax_body<false>(sigma, ListedRays{origin, pts, tindex}, pred_dist, gt_dist, R, v, step, K);
+}
+
+// camera-view decode: the same body on rays generated from their pixel; dist [F,C,Hs,Ws] is the only store
+RAY_KERNEL ray_argmax_cam_kernel(const float* __restrict__ sigma, CameraRays cam, float* __restrict__ dist, int R,
+                                 VolDims v, float step) {
+  ray_argmax_body<true>(sigma, cam, dist, nullptr, R, v, step, kK);
+}
+RAY_KERNEL ray_argmax_cam_any_kernel(const float* __restrict__ sigma, CameraRays cam, float* __restrict__ dist, int R,
+                                     VolDims v, float step, int K) {
+  ray_argmax_body<false>(sigma, cam, dist, nullptr, R, v, step, K);
+}
+// what ray_argmax_cam_kernel marches, written out: origin [F,C,3], pts [F,C,Hs,Ws,3]; a thread per pixel
+__global__ __launch_bounds__(kThreads) void cam_rays_kernel(CameraRays cam, float* __restrict__ origin,
+                                                            float* __restrict__ pts, int R) {
+  const int r = blockIdx.x * kThreads + threadIdx.x;
+  if (r >= R) return;
+  int f, fc, x, y;
+  vidar_cam::split_ray_index(r, cam.g, f, fc, x, y);
+  const vidar_cam::CamRay c = vidar_cam::pixel_ray(cam.pix2vox + (size_t)fc * 16, cam.g, x, y);
+  pts[(size_t)r * 3 + 0] = c.px; pts[(size_t)r * 3 + 1] = c.py; pts[(size_t)r * 3 + 2] = c.pz;
+  if (x == 0 && y == 0) { origin[fc * 3 + 0] = c.ox; origin[fc * 3 + 1] = c.oy; origin[fc * 3 + 2] = c.oz; }
 }
 
 // Deterministic mode (det_acc.h): the same body under the measure policy, then under the fixed-point policy, adding
@@ -483,6 +544,15 @@ RAY_KERNEL ray_bwd_det_kernel(RAY_IN, const float* __restrict__ saved, const flo
 
 inline bool rm_bad(int F, int R, int Z, int Y, int X, int K) {
   return F <= 0 || R < 0 || Z <= 0 || Y <= 0 || X <= 0 || K < 1 || K > kKMax;
+}
+// camera grid: F*C*Hs*Ws rays must fit the 32-bit ray index; `R` is set only when the geometry is good
+inline bool cam_bad(int F, int C, int Hs, int Ws, float u0, float v0, float du, float dv, int& R) {
+  if (F <= 0 || C <= 0 || Hs < 0 || Ws < 0) return true;
+  if (!(u0 == u0 && v0 == v0 && du == du && dv == dv) || du == 0.f || dv == 0.f) return true;
+  const uint64_t n = (uint64_t)F * (uint64_t)C * (uint64_t)Hs * (uint64_t)Ws;
+  if (n > (uint64_t)0x7fffffff - kThreads) return true;
+  R = (int)n;
+  return false;
 }
 std::atomic<int> g_force_streamed{0};   // vidar_ray_force_streamed
 inline bool rm_k512(int K) { return K == kK && !g_force_streamed.load(std::memory_order_relaxed); }
@@ -624,6 +694,31 @@ int vidar_ray_argmax_f32(const float* sigma, const float* origin, const float* p
   VolDims v{F, Z, Y, X};
   rm_launch(ray_argmax_kernel, ray_argmax_any_kernel, R, K, (hipStream_t)stream, sigma, origin, pts, tindex, pred_dist,
             gt_dist, R, v, step);
+  return vidar_last_error();
+}
+
+int vidar_ray_argmax_cam_f32(const float* sigma, const float* pix2vox, float* dist, int F, int C, int Hs, int Ws,
+                             float u0, float v0, float du, float dv, int Z, int Y, int X, int K, float step,
+                             void* stream) {
+  VIDAR_ENTER();
+  int R = 0;
+  if (cam_bad(F, C, Hs, Ws, u0, v0, du, dv, R) || rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
+  if (R == 0) return 0;
+  VolDims v{F, Z, Y, X};
+  const CameraRays cam{pix2vox, vidar_cam::CamGrid{C, Hs, Ws, u0, v0, du, dv}};
+  rm_launch(ray_argmax_cam_kernel, ray_argmax_cam_any_kernel, R, K, (hipStream_t)stream, sigma, cam, dist, R, v, step);
+  return vidar_last_error();
+}
+
+int vidar_cam_rays_f32(const float* pix2vox, float* origin, float* pts, int F, int C, int Hs, int Ws, float u0,
+                       float v0, float du, float dv, void* stream) {
+  VIDAR_ENTER();
+  int R = 0;
+  if (cam_bad(F, C, Hs, Ws, u0, v0, du, dv, R)) return VIDAR_ERR_BAD_ARG;
+  if (R == 0) return 0;
+  const CameraRays cam{pix2vox, vidar_cam::CamGrid{C, Hs, Ws, u0, v0, du, dv}};
+  hipLaunchKernelGGL(cam_rays_kernel, dim3((R + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, cam,
+                     origin, pts, R);
   return vidar_last_error();
 }
 

@@ -1,0 +1,168 @@
+"""A forecast without ground truth: the geometry and the pictures around `ViDAR.forecast` / `ViDARHeadBase.render_rays`.
+
+  pix2vox        camera pixel -> voxel coordinates of a predicted volume (input of ray_ops.ray_argmax_cam)
+  lidar_pattern  unit directions of a spinning LiDAR, for a sweep nobody measured
+  bev_image      bird's-eye picture of labelled points; a restatement of the reference's `_dbg_draw_pc_function`
+                 (utils/e2e_predictor_utils.py:188-224), NOT a pixel copy of what matplotlib renders
+  depth_overlay  per-pixel depth laid over the camera frame
+torch + PIL only; nothing here launches a kernel of its own."""
+from __future__ import annotations
+
+import math
+import os
+
+import numpy as np
+import torch
+
+LABEL_COLOURS = ((0, 0, 230), (219, 112, 147), (255, 0, 0))      # detectors/vidar.py:523-525: prediction, ground truth, ego
+
+
+def pix2vox(lidar2img, pc_range, bev_h, bev_w, pillar_num, align=None):
+    """[F, C, 4, 4] fp32 maps of the homogeneous pixel (u*d, v*d, d, 1) to voxel coordinates of each frame's volume.
+
+    lidar2img [C, 4, 4]: the CURRENT frame's camera matrices (img_metas[...]["lidar2img"]), affine (last row 0 0 0 1).
+    align [F, 4, 4] or None: per frame, the row-vector transform (p_row @ M) from the frame's own LiDAR coordinates to
+    the coordinates its volume is predicted in -- what the head applies to the ground-truth rays of that frame
+    (ViDARHeadV1._get_reference_gt_points); None = identity for one frame.
+    The metric -> voxel map is e2e_predictor_utils.coords_to_voxel_grids.  Everything is composed in fp64 and rounded to
+    fp32 once.
+
+    ASSUMPTION (rigid rig): the cameras are fixed to the ego vehicle, so the current frame's lidar2img also describes
+    where the cameras sit in every FUTURE frame's own LiDAR coordinates; the depth of future frame f is therefore what
+    the rig would see from where the vehicle will be, not from where it is now."""
+    l2i = np.asarray([np.asarray(m, dtype=np.float64) for m in lidar2img], dtype=np.float64)
+    if l2i.ndim != 3 or l2i.shape[1:] != (4, 4):
+        raise ValueError("lidar2img must be [C, 4, 4]")
+    if not np.allclose(l2i[:, 3], [0.0, 0.0, 0.0, 1.0]):
+        raise ValueError("lidar2img must be affine (last row 0 0 0 1)")
+    align = np.eye(4)[None] if align is None else np.asarray(align, dtype=np.float64)
+    pc = [float(v) for v in pc_range]
+    to_vox = np.eye(4)
+    for axis, n in enumerate((bev_w, bev_h, pillar_num)):
+        to_vox[axis, axis] = n / (pc[axis + 3] - pc[axis])
+        to_vox[axis, 3] = -pc[axis] * n / (pc[axis + 3] - pc[axis])
+    inv = np.linalg.inv(l2i)                                          # [C, 4, 4] pixel -> LiDAR, column vectors
+    out = np.einsum("ij,fjk,ckl->fcil", to_vox, np.transpose(align, (0, 2, 1)), inv)
+    out[..., 3, :] = [0.0, 0.0, 0.0, 1.0]
+    return torch.from_numpy(out.astype(np.float32))
+
+
+def lidar_pattern(beams=32, azimuths=1080, elevation_deg=(-30.67, 10.67)):
+    """Unit directions [beams * azimuths, 3] (x forward, y left, z up) of a spinning LiDAR: `beams` elevations evenly
+    spaced over `elevation_deg` (both ends included), `azimuths` evenly spaced turns in [-pi, pi), beam-major.
+
+    The defaults are the Velodyne HDL-32E's figures (32 beams over -30.67 .. +10.67 degrees; 1080 columns a turn is about
+    its horizontal resolution at 10 Hz) as RECALLED from its data sheet, not pinned against a file of this repository
+    or the nuScenes sweeps: they make a plausible sweep, not that sensor's calibrated beam table."""
+    if beams < 1 or azimuths < 1:
+        raise ValueError("beams and azimuths must be >= 1")
+    lo, hi = (math.radians(float(e)) for e in elevation_deg)
+    el = torch.linspace(lo, hi, beams, dtype=torch.float64)
+    az = -math.pi + torch.arange(azimuths, dtype=torch.float64) * (2.0 * math.pi / azimuths)
+    el, az = el[:, None], az[None, :]
+    d = torch.stack([el.cos() * az.cos(), el.cos() * az.sin(), el.sin().expand(beams, azimuths)], -1).reshape(-1, 3)
+    d = d / d.norm(dim=1, keepdim=True)
+    return d.float()
+
+
+def _cross(img, row, col, arm, colour):
+    size = img.shape[0]
+    k = torch.arange(-arm, arm + 1, device=img.device)
+    for rr, cc in ((row + k, col + k), (row + k, col - k)):
+        ok = (rr >= 0) & (rr < size) & (cc >= 0) & (cc < size)
+        img[rr[ok], cc[ok]] = colour
+
+
+def _to_pixel(xy, size_px, limit_m):
+    """metric (x, y) fp64 -> (row, col, inside): a square of +-limit_m, x to the right, y up; the pixel is the floor of
+    the position in pixel units, so the window is closed at -limit_m and open at +limit_m; NaN is outside."""
+    col = torch.floor((xy[..., 0] + limit_m) / (2.0 * limit_m) * size_px)
+    up = torch.floor((xy[..., 1] + limit_m) / (2.0 * limit_m) * size_px)
+    inside = (col >= 0) & (col < size_px) & (up >= 0) & (up < size_px)        # False for NaN
+    col = torch.where(inside, col, torch.zeros_like(col)).long()
+    row = size_px - 1 - torch.where(inside, up, torch.zeros_like(up)).long()
+    return row, col, inside
+
+
+def bev_image(points, labels, centre=None, size_px=720, limit_m=40):
+    """Bird's-eye picture [size_px, size_px, 3] uint8 of points [N, >=2] (metres) coloured by labels [N] (indices into
+    LABEL_COLOURS) on white ground: one pixel per point, a later point paints over an earlier one, NaN points and points
+    outside the +-limit_m window are skipped; then a diagonal cross in label 0's colour at every `centre` [M, >=2] and a
+    red one at (0, 0).  A restatement of the reference's matplotlib scatter (its window, its colours, its markers' places
+    and its draw order), not a copy of its pixels."""
+    dev = points.device
+    n = points.shape[0]
+    colours = torch.tensor(LABEL_COLOURS, dtype=torch.uint8, device=dev)
+    img = torch.full((size_px * size_px, 3), 255, dtype=torch.uint8, device=dev)
+    if n:
+        row, col, inside = _to_pixel(points[:, :2].double(), size_px, float(limit_m))
+        pix = (row * size_px + col)[inside]
+        order = torch.arange(n, device=dev)[inside]
+        # the last point of every pixel: max of the point index (index_put_ with duplicate pixels has no defined winner)
+        last = torch.full((size_px * size_px,), -1, dtype=torch.int64, device=dev)
+        last = last.scatter_reduce(0, pix, order, reduce="amax", include_self=True)
+        hit = last >= 0
+        img[hit] = colours[labels.to(dev).long()[last[hit]]]
+    img = img.view(size_px, size_px, 3)
+    arm = max(2, size_px // 64)
+    marks = [] if centre is None else [(c, colours[0]) for c in centre.to(dev).double().view(-1, centre.shape[-1])]
+    marks.append((torch.zeros(2, dtype=torch.float64, device=dev), colours[2]))
+    for xy, colour in marks:
+        row, col, inside = _to_pixel(xy[:2], size_px, float(limit_m))
+        if bool(inside):
+            _cross(img, int(row), int(col), arm, colour)
+    return img
+
+
+def colour_table(device="cpu"):
+    """[256, 3] uint8, a piecewise-linear blue - cyan - green - yellow - red ramp in integer arithmetic"""
+    i = torch.arange(256, dtype=torch.int64, device=device)
+    ch = [(384 - (4 * i - peak).abs()).clamp(0, 255) for peak in (768, 512, 256)]
+    return torch.stack(ch, 1).to(torch.uint8)
+
+
+def depth_overlay(depth, frame_u8, near=1.0, far=60.0, alpha=160):
+    """depth [Hs, Ws] (metres, 0 or NaN = no return) over frame_u8 [H, W, 3] uint8 -> [H, W, 3] uint8.
+
+    The stride is s = ceil(H / Hs) (it must reproduce Hs and Ws): image pixel (y, x) takes depth[y // s, x // s].  Colour
+    index = clamp(floor((far - d) / (far - near) * 255 + 0.5), 0, 255) into colour_table (near = red end, computed in
+    fp64); out = (alpha * colour + (255 - alpha) * image + 127) // 255 in integers where there is a return, the image
+    elsewhere."""
+    H, W = frame_u8.shape[:2]
+    Hs, Ws = depth.shape
+    s = -(-H // Hs)
+    if s < 1 or -(-H // s) != Hs or -(-W // s) != Ws:
+        raise ValueError(f"depth {tuple(depth.shape)} is no strided grid of a {H} x {W} frame")
+    a = int(alpha)
+    if not 0 <= a <= 255 or not far > near:
+        raise ValueError("alpha must be 0..255 and far > near")
+    dev = frame_u8.device
+    d = depth.to(dev).double()
+    idx = torch.floor((far - d) / (far - near) * 255.0 + 0.5)
+    live = (d > 0) & torch.isfinite(d)
+    idx = torch.where(live, idx, torch.zeros_like(idx)).clamp(0, 255).long()
+    ys = torch.arange(H, device=dev) // s
+    xs = torch.arange(W, device=dev) // s
+    colour = colour_table(dev)[idx][ys][:, xs].to(torch.int32)           # [H, W, 3]
+    live = live[ys][:, xs]
+    img = frame_u8.to(torch.int32)
+    mixed = (a * colour + (255 - a) * img + 127) // 255
+    return torch.where(live[..., None], mixed, img).to(torch.uint8)
+
+
+def save_png(img_u8, path):
+    """[H, W, 3] uint8 tensor -> PNG file (its directory is created)"""
+    from PIL import Image
+    root = os.path.dirname(str(path))
+    if root:
+        os.makedirs(root, exist_ok=True)
+    Image.fromarray(img_u8.cpu().numpy(), "RGB").save(str(path))
+
+
+def sweep_bev(pred, gt=None, centre=None, size_px=720, limit_m=40):
+    """the reference's `_viz_pcd` (detectors/vidar.py:521-536): the prediction as label 0, then the ground truth as
+    label 1 painted over it, the sensor origin as the centre cross"""
+    pts = pred[:, :3] if gt is None else torch.cat([pred[:, :3], gt[:, :3].to(pred.device)], 0)
+    lab = torch.zeros(pts.shape[0], dtype=torch.int64, device=pts.device)
+    lab[pred.shape[0]:] = 1
+    return bev_image(pts, lab, centre, size_px, limit_m)

@@ -170,3 +170,37 @@ def ray_argmax(sigma, origin, pts, tindex, step=1.0, K=K_SAMPLES):
     check(lib().vidar_ray_argmax_f32(ptr(sigma), ptr(origin), ptr(pts), ptr(tindex), ptr(pred),
                                      ptr(gt), F_, R, Z, Y, X, int(K), step, stream_of(sigma)), "ray_argmax")
     return pred, gt
+
+
+def _cam_args(pix2vox, hw, u0, v0, du, dv):
+    if pix2vox.dim() != 4 or pix2vox.shape[-2:] != (4, 4):
+        raise ValueError("pix2vox must be [F, C, 4, 4]")
+    F_, C = pix2vox.shape[:2]
+    return F_, C, int(hw[0]), int(hw[1]), float(u0), float(v0), float(du), float(dv)
+
+
+def ray_argmax_cam(sigma, pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0, step=1.0, K=K_SAMPLES):
+    """camera-view decode: sigma [F,Z,Y,X], pix2vox [F,C,4,4] (homogeneous pixel -> voxel, affine), one ray per pixel
+    (x, y) of the hw = (Hs, Ws) grid at u = u0 + x*du, v = v0 + y*dv -> dist [F,C,Hs,Ws] in voxel units, 0 where the
+    ray meets nothing.  The rays are never stored (vidar_ray_argmax_cam_f32); no grad."""
+    sigma, pix2vox = _f(sigma.detach()), _f(pix2vox)
+    geom = _cam_args(pix2vox, hw, u0, v0, du, dv)
+    F_, Z, Y, X = sigma.shape
+    if geom[0] != F_:
+        raise ValueError(f"pix2vox holds {geom[0]} frames, sigma {F_}")
+    if pix2vox.device != sigma.device:
+        raise RuntimeError(f"pix2vox is on {pix2vox.device}, sigma on {sigma.device}")
+    dist = torch.empty(geom[:4], device=sigma.device)
+    check(lib().vidar_ray_argmax_cam_f32(ptr(sigma), ptr(pix2vox), ptr(dist), *geom, Z, Y, X, int(K), step,
+                                         stream_of(sigma)), "ray_argmax_cam")
+    return dist
+
+
+def cam_rays(pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0):
+    """the rays ray_argmax_cam marches, written out: -> (origin [F,C,3], pts [F,C,Hs,Ws,3]) in voxel units."""
+    pix2vox = _f(pix2vox)
+    geom = _cam_args(pix2vox, hw, u0, v0, du, dv)
+    origin = torch.empty((*geom[:2], 3), device=pix2vox.device)
+    pts = torch.empty((*geom[:4], 3), device=pix2vox.device)
+    check(lib().vidar_cam_rays_f32(ptr(pix2vox), ptr(origin), ptr(pts), *geom, stream_of(pix2vox)), "cam_rays")
+    return origin, pts

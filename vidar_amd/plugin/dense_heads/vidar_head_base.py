@@ -277,3 +277,71 @@ class ViDARHeadBase(ViDARHeadTemplate):
             pred_pcds=self.get_rendered_pcds(origin_pts, gt_xyz, tindex, gt, pred, tgt_pc_range),
             gt_pcds=self.get_rendered_pcds(origin_pts, gt_xyz, tindex, gt, gt, tgt_pc_range),
             origin=origin_pts)
+
+    def _ray_frame_labels(self, valid_frames):
+        """the value the last column of a point holds for each frame slot of `valid_frames`"""
+        return [float(f) for f in valid_frames]
+
+    def _decode_preds(self, pred_dict):
+        """the logits get_point_cloud_prediction decodes: [F, inter, bs, Q, Z]"""
+        return pred_dict["next_bev_preds"]
+
+    def frame_alignment(self, valid_frames, img_metas):
+        """[bs, F, 4, 4] fp64, row-vector form: frame slot f's own LiDAR coordinates -> the coordinates its decoded
+        volume lives in (the identity here: this head takes its rays as they are)."""
+        return np.tile(np.eye(4), (len(img_metas), len(valid_frames), 1, 1))
+
+    @torch.no_grad()
+    def render_cameras(self, pred_dict, img_metas, tgt_bev_h, tgt_bev_w, tgt_pc_range, cameras=None, stride=4):
+        """The decode seen from the cameras: one ray per `stride` x `stride` block of every camera's pixels, through the
+        block's centre, marched by ray_ops.ray_argmax_cam (the rays are never stored).
+        cameras: indices into img_metas[b]["lidar2img"] (None = all; their images must share one size).
+        -> depth [bs, F, C, Hs, Ws], Hs = ceil(H / stride): metres along the ray (voxel units times the BEV cell size, the
+        decode's own scale), 0 where the ray meets nothing.  The cameras of a future frame are the current frame's, by the
+        rigid-rig assumption of vidar_amd.forecast.pix2vox."""
+        from ...forecast import pix2vox
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError("stride must be >= 1")
+        bev_preds = self._decode_preds(pred_dict).float()
+        F_, inter_num, bs, token_num, Z = bev_preds.shape
+        last = bev_preds[:, -1:]
+        align = self.frame_alignment(pred_dict["valid_frames"], img_metas)
+        scale = (tgt_pc_range[3] - tgt_pc_range[0]) / tgt_bev_w
+        out = []
+        for b in range(bs):
+            meta = img_metas[b]
+            cams = list(range(len(meta["lidar2img"]))) if cameras is None else [int(c) for c in cameras]
+            sizes = {tuple(meta["img_shape"][c][:2]) for c in cams}
+            if len(sizes) != 1:
+                raise ValueError(f"the cameras' images must share one size, got {sorted(sizes)}")
+            H, W = sizes.pop()
+            m = pix2vox([meta["lidar2img"][c] for c in cams], tgt_pc_range, tgt_bev_h, tgt_bev_w, Z, align[b])
+            d = ray_ops.ray_argmax_cam(self._volumes(last, b, Z, tgt_bev_h, tgt_bev_w), m.to(bev_preds.device),
+                                       (-(-H // stride), -(-W // stride)), u0=stride / 2.0, v0=stride / 2.0,
+                                       du=float(stride), dv=float(stride), step=self.ray_grid_step, K=self.ray_grid_num)
+            out.append(d * scale)
+        return torch.stack(out)
+
+    @torch.no_grad()
+    def render_rays(self, pred_dict, directions=None, end_points=None, *, tgt_bev_h, tgt_bev_w, tgt_pc_range,
+                    img_metas=None, start_idx=0, batched_origin_points=None):
+        """The decode of get_point_cloud_prediction along rays handed in instead of taken from `gt_points`: the same
+        origin, voxel mapping, ray_argmax call and masking, because it IS that call.  Exactly one of
+          directions [R, 3]: unit directions in every predicted frame's own sensor coordinates, shared by all samples
+                             and frames (vidar_amd.forecast.lidar_pattern); the ray's end point is the point 1 m out;
+          end_points list[bs] of [N, >=4]: points in the layout of gt_points (xyz first, the frame label last).
+        -> list[bs] of list[frames] of [n, 3] predicted points, ray order kept within a frame.  A ray without a live
+        waypoint comes back at waypoint 0 (the reference's decode); with eval_within_grid the end point's own
+        membership still selects the ray, as for ground truth."""
+        if (directions is None) == (end_points is None):
+            raise ValueError("give either directions or end_points")
+        if end_points is None:
+            bs = pred_dict["next_bev_preds"].shape[-3]
+            d = directions.float()
+            cols = [torch.cat([d, d.new_full((d.shape[0], 1), lab)], 1)
+                    for lab in self._ray_frame_labels(pred_dict["valid_frames"])]
+            end_points = [torch.cat(cols, 0)] * bs
+        return self.get_point_cloud_prediction(pred_dict, end_points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range,
+                                               img_metas=img_metas,
+                                               batched_origin_points=batched_origin_points)["pred_pcds"]

@@ -118,10 +118,24 @@ class ViDARHeadV1(ViDARHeadBase):
             keys.append("loss.dense_voxel")
         return keys
 
+    def _ray_frame_labels(self, valid_frames):
+        return [float(f + self.history_queue_length) for f in valid_frames]   # the dataset's frame numbering
+
+    def _decode_preds(self, pred_dict):
+        return pred_dict["next_bev_preds"][:, :, self.pred_history_frame_num, ...].contiguous()
+
+    def frame_alignment(self, valid_frames, img_metas):
+        """[bs, F, 4, 4] fp64, row-vector form: frame slot f's own LiDAR coordinates -> the coordinates its decoded
+        volume lives in; the transform get_point_cloud_prediction applies to the rays (source = target frame, so the
+        identity up to the rounding of the stored pair of inverse matrices)."""
+        frames = np.array(valid_frames) + self.history_queue_length
+        return np.array([[np.asarray(m["total_cur2ref_lidar_transform"][t], dtype=np.float64)
+                          @ np.asarray(m["total_ref2cur_lidar_transform"][t], dtype=np.float64) for t in frames]
+                         for m in img_metas])
+
     def get_point_cloud_prediction(self, pred_dict, gt_points, start_idx, tgt_bev_h, tgt_bev_w,
                                    tgt_pc_range, img_metas=None, batched_origin_points=None, as_rays=False):
-        pred_dict = dict(pred_dict)
-        pred_dict["next_bev_preds"] = pred_dict["next_bev_preds"][:, :, self.pred_history_frame_num, ...].contiguous()
+        pred_dict = dict(pred_dict, next_bev_preds=self._decode_preds(pred_dict))
         valid_frames = np.array(pred_dict["valid_frames"])
         gt, origin = self._get_reference_gt_points(
             gt_points, src_frame_idx_list=valid_frames + self.history_queue_length,
