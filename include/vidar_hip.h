@@ -438,6 +438,29 @@ int vidar_ray_argmax_cam_f32(const float* sigma, const float* pix2vox, float* di
 int vidar_cam_rays_f32(const float* pix2vox, float* origin, float* pts, int F, int C, int Hs, int Ws, float u0,
                        float v0, float du, float dv, void* stream);
 
+/* The decode with its confidence (csrc/ray_march.hip, ray_stats_body): vidar_ray_argmax_f32 / vidar_ray_argmax_cam_f32
+ * plus four statistics of the softmax over the ray's waypoints.  Same waypoints and sampler as the decode: zero padding,
+ * an exact 0 sample counts as -inf, a NaN coordinate samples as 0.  z_k = logit, l_k = length of waypoint k; a waypoint
+ * is live iff z_k is not -inf.  With m = max z_k, e_k = exp(z_k - m) (0 for a dead waypoint), S = sum e_k and d = the
+ * arg-max length (first index wins), stats[r] = {p_max, mean, rms, entropy}, voxel units:
+ *   p_max   = exp(z_argmax - m) / S, in (0, 1]
+ *   mean    = d + sum e_k (l_k - d) / S          expected length, accumulated as a deviation from d
+ *   rms     = sqrt(sum e_k (l_k - d)^2 / S)      spread about the decoded depth
+ *   entropy = log S - sum_live e_k (z_k - m) / S  nats, >= 0; dead waypoints are skipped (no 0 * -inf)
+ * A skipped ray (tindex < 0, NaN or >= F) and a ray without a live waypoint give four zeros.  pred_dist / gt_dist and dist
+ * are what the two arg-max entries write for the ray, bit for bit (waypoint 0's length for a dead listed ray, 0 for a
+ * dead camera ray).  +inf or NaN logits may give non-finite statistics.  fp32 sums in a fixed order, no atomics, no
+ * workspace: equal inputs give equal bits, and K == 512 gives the same bits through the streamed kernels.
+ * stats [R,4] / [F,C,Hs,Ws,4] is written as one 16-byte store per ray and must be 16-byte aligned; otherwise arguments
+ * and VIDAR_ERR_BAD_ARG cases are those of the arg-max entries, and an empty problem returns 0 without a launch. */
+int vidar_ray_stats_f32(const float* sigma, const float* origin, const float* pts, const float* tindex,
+                        float* pred_dist, float* gt_dist, float* stats /*[R,4]*/,
+                        int F, int R, int Z, int Y, int X, int K, float step, void* stream);
+int vidar_ray_stats_cam_f32(const float* sigma, const float* pix2vox, float* dist /*[F,C,Hs,Ws]*/,
+                            float* stats /*[F,C,Hs,Ws,4]*/, int F, int C, int Hs, int Ws,
+                            float u0, float v0, float du, float dv, int Z, int Y, int X, int K, float step,
+                            void* stream);
+
 /* ---------------------------------------------------------------------------
  * Modulated deformable convolution v2 (backbone, "next" row SURVEY 8f-1).  Replaces the sampling
  * kernels of mmcv.ops.ModulatedDeformConv2dPack (mmcv-full 1.4.0, third party); the convolution

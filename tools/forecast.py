@@ -10,6 +10,11 @@ Per sample i and frame k (0 = the current frame, 1.. the futures) it writes into
     bev_{i}_{k}.png          bird's-eye picture of that sweep
     depth_{i}_{k}_cam{c}.png the depth of every --stride-th pixel of camera c (ViDAR.forecast, rigid-rig assumption) over
                              the CURRENT frame of that camera; skipped with --no-depth
+with --stats, --min-prob P or --max-rms M (metres; a ray below P or above M is dropped from the sweep and its pixel from
+the depth picture) also
+    sweep_stats_{i}_{k}.npy  [n, 4] float32, row for row with sweep_{i}_{k}.npy: peak probability, mean depth (m), spread
+                             about the decoded depth (m) and entropy (nats) of the softmax along the ray
+    conf_{i}_{k}_cam{c}.png  the peak probability of camera c's pixels over the same frame (blue = 0 .. red = 1)
 and prints one JSON line per sample with its wall time (device drained).  The frame under the overlay is the network's own
 input de-normalised (with --device-images that input comes from the device image pipeline); without a backbone
 (--no-backbone: synthetic feature pyramids) the overlay is drawn on black.  No ground truth is read."""
@@ -55,6 +60,9 @@ def main(argv=None):
     ap.add_argument("--near", type=float, default=1.0)
     ap.add_argument("--far", type=float, default=60.0)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--stats", action="store_true", help="also write the decode's confidence (sweep_stats_*, conf_*)")
+    ap.add_argument("--min-prob", type=float, metavar="P", help="drop rays whose peak probability is below P")
+    ap.add_argument("--max-rms", type=float, metavar="M", help="drop rays whose spread about the depth exceeds M metres")
     args = ap.parse_args(argv)
     if (args.source == "synthetic") == bool(args.ann_file):
         raise SystemExit("give either `synthetic` or --ann-file")
@@ -108,10 +116,13 @@ def main(argv=None):
     out_dir = Path(args.out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
     rays = FC.lidar_pattern(args.beams, args.azimuths).to(dev)
+    confidence = {}                                                    # without the flags: the call and the files of before
+    if args.stats or args.min_prob is not None or args.max_rms is not None:
+        confidence = dict(stats=True, min_prob=args.min_prob, max_rms=args.max_rms)
     for i in range(n_samples):
         b = batch(i)
         torch.cuda.synchronize(); t0 = time.perf_counter()
-        out = model.forecast(rays=rays, cameras=None if args.no_depth else "all", stride=args.stride, **b)
+        out = model.forecast(rays=rays, cameras=None if args.no_depth else "all", stride=args.stride, **confidence, **b)
         torch.cuda.synchronize(); t_model = time.perf_counter() - t0
         cur = b["img_metas"][0][T_img - 1] if isinstance(b["img_metas"][0], (list, tuple)) else b["img_metas"][0]
         files = 0
@@ -119,6 +130,9 @@ def main(argv=None):
             np.save(out_dir / f"sweep_{i}_{k}.npy", pts.cpu().numpy().astype(np.float32))
             FC.save_png(FC.sweep_bev(pts, centre=pts.new_zeros(1, 3)), out_dir / f"bev_{i}_{k}.png")
             files += 2
+            if confidence:
+                np.save(out_dir / f"sweep_stats_{i}_{k}.npy", out["sweep_stats"][0][k].cpu().numpy().astype(np.float32))
+                files += 1
         if not args.no_depth:
             depth = out["depth"][0]                                    # [F, C, Hs, Ws]
             for c in range(depth.shape[1]):
@@ -128,6 +142,11 @@ def main(argv=None):
                 for k in range(depth.shape[0]):
                     FC.save_png(FC.depth_overlay(depth[k, c], frame, args.near, args.far), out_dir / f"depth_{i}_{k}_cam{c}.png")
                     files += 1
+                    if confidence:
+                        # the peak probability of the pixels that are left: a dropped pixel shows the frame, as in depth_*
+                        p_max = out["depth_stats"][0, k, c, ..., 0] * (depth[k, c] > 0)
+                        FC.save_png(FC.confidence_overlay(p_max, frame), out_dir / f"conf_{i}_{k}_cam{c}.png")
+                        files += 1
         torch.cuda.synchronize()
         print(json.dumps(dict(sample=i, sample_idx=str(cur.get("sample_idx")), frames=len(out["sweep"][0]),
                               sweep_points=[int(p.shape[0]) for p in out["sweep"][0]], files=files,

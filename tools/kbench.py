@@ -990,6 +990,68 @@ def bench_forecast_view(which):
                   f"{r['fused_over_two_launch']} | {r['fused_spread']} | {r['two_launch_spread']} |\n" for r in rows))
 
 
+def bench_ray_stats(which):
+    """the decode with its confidence (vidar_ray_stats_f32 / vidar_ray_stats_cam_f32) against the plain arg-max decode
+    (vidar_ray_argmax_f32 / vidar_ray_argmax_cam_f32) in the same process on the same build: 30 000 listed rays, and 6
+    cameras of 900 x 1600 pixels at strides 1 / 2 / 4, on a 16 x 200 x 200 volume at K = 512 (register form) and K = 1026
+    (streamed form), step 1.  HIP events, the two decodes alternating, three repeats of 2 warm-up + 5 timed calls each
+    (50 for the listed rays); the spread is (max - min) / median over the repeats.  Writes profiles/kbench_ray_stats.md."""
+    from vidar_amd import forecast as FC
+    from vidar_amd.plugin.dense_heads.ray_ops import ray_argmax, ray_argmax_cam, ray_stats, ray_stats_cam
+    from vidar_amd.synthetic import PC_RANGE, camera_matrices, ray_set
+    dev = torch.device("cuda", 0)
+    Z, Y, X, C, H, W = 16, 200, 200, 6, 900, 1600
+    sigma = torch.randn(1, Z, Y, X, generator=torch.Generator().manual_seed(0)).to(dev)
+    _, origin, points, tindex = ray_set(seed=0, N=1, T=1, rays_per_frame=30000)
+    o, p, ti = (torch.from_numpy(a[0]).to(dev) for a in (origin, points, tindex))
+    m = FC.pix2vox(camera_matrices(img_hw=(H, W))[:C], PC_RANGE, Y, X, Z).to(dev)
+    med = lambda v: float(np.median(v))
+    spread = lambda v: (max(v) - min(v)) / med(v)
+    rows = []
+
+    def compare(rays, K, plain, stats, it=5, **tag):
+        a, b = plain(), stats()
+        same = bool(torch.equal(a, b[0]))
+        ps, ss = [], []
+        for _ in range(3):
+            ps.append(timeit(plain, warm=2, it=it)); ss.append(timeit(stats, warm=2, it=it))
+        row = dict(rays=tag.pop("rays_name"), **tag, R=rays, K=K, form="register" if K == 512 else "streamed",
+                   argmax_ms=[round(v, 3) for v in ps], stats_ms=[round(v, 3) for v in ss],
+                   argmax_median_ms=round(med(ps), 3), stats_median_ms=round(med(ss), 3),
+                   argmax_spread=round(spread(ps), 4), stats_spread=round(spread(ss), 4),
+                   stats_over_argmax=round(med(ss) / med(ps), 4), same_distance_bits=same,
+                   mean_p_max=round(float(b[-1][..., 0].mean()), 4))
+        rows.append(row)
+        report("ray_stats", med(ss), **row)
+
+    for K in (512, 1026):
+        compare(p.shape[0], K, lambda: ray_argmax(sigma, o, p, ti, 1.0, K)[0], lambda: ray_stats(sigma, o, p, ti, 1.0, K),
+                it=50, rays_name="listed", stride="-")
+    for K in (512, 1026):
+        for stride in (1, 2, 4):
+            Hs, Ws = -(-H // stride), -(-W // stride)
+            geom = ((Hs, Ws), stride / 2.0, stride / 2.0, float(stride), float(stride))
+            compare(C * Hs * Ws, K, lambda: ray_argmax_cam(sigma, m, *geom, 1.0, K),
+                    lambda: ray_stats_cam(sigma, m, *geom, 1.0, K), rays_name="camera", stride=stride)
+    out = os.environ.get("VIDAR_KBENCH_OUT")
+    path = Path(out) if out else ROOT / "profiles" / "kbench_ray_stats.md"
+    path.write_text(
+        "# The decode with its confidence on an MI355X: `python tools/kbench.py ray_stats`\n\n"
+        f"Volume {Z} x {Y} x {X}, random-normal logits, step 1.  `listed`: 30 000 rays of `vidar_amd.synthetic.ray_set`\n"
+        f"(`vidar_ray_stats_f32` against `vidar_ray_argmax_f32`); `camera`: {C} cameras of {H} x {W} pixels, the pin-hole rig of\n"
+        "`vidar_amd.synthetic.camera_matrices` (`vidar_ray_stats_cam_f32` against `vidar_ray_argmax_cam_f32`).  K = 512 runs\n"
+        "the register form, K = 1026 the streamed one.  Both decodes in one process on one build, alternating; HIP events,\n"
+        "3 repeats of 2 warm-up + 5 timed calls (50 for the listed rays); spread = (max - min) / median.  Each call\n"
+        "allocates its outputs.\n\n"
+        "```\n" + json.dumps({"device": torch.cuda.get_device_name(0)}) + "\n"
+        + "\n".join(json.dumps(dict(op="ray_stats", **r)) for r in rows) + "\n```\n\n"
+        "| rays | stride | R | K | form | arg-max ms (median) | stats ms (median) | stats / arg-max | spread arg-max | spread stats |\n"
+        "|---|---|---|---|---|---|---|---|---|---|\n"
+        + "".join(f"| {r['rays']} | {r['stride']} | {r['R']} | {r['K']} | {r['form']} | {r['argmax_median_ms']} | "
+                  f"{r['stats_median_ms']} | {r['stats_over_argmax']} | {r['argmax_spread']} | {r['stats_spread']} |\n"
+                  for r in rows))
+
+
 if __name__ == "__main__":
     import os
     if os.environ.get("VIDAR_MSDA_ITEM_ORDER") is not None:          # A/B of the gather kernels' item order (0 banded, 1 head-major)

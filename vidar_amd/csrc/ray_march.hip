@@ -9,6 +9,8 @@
 //                 {end point, K waypoints} of the GT rays
 //   ray_argmax_cam : ray_argmax on rays that are a function of (frame, camera, pixel) and are never stored
 //                 (cam_ray.h; no counterpart in the reference); cam_rays writes those rays out
+//   ray_stats / ray_stats_cam : the two decodes with the softmax along the ray summarised next to the distance
+//                 (peak probability, mean length, spread, entropy; no counterpart in the reference)
 // The reference materialises ~8 arrays of [rays, 513] floats per call (waypoints, lengths, masks,
 // sampled logits, -inf masks, softmax); here one wave owns one ray, its 512 waypoints live in
 // registers (8 per lane) and only O(1) values per ray ever reach HBM.
@@ -383,6 +385,55 @@ __device__ __forceinline__ void ray_argmax_body(
   }
 }
 
+// The decode with its confidence: ray_argmax_body's first visit, then a second one over the softmax of the ray's live
+// waypoints (live = logit not -inf).  With m = max logit (the arg-max's own logit: no noise here, so Best carries it),
+// e_k = exp(z_k - m), S = sum e_k and d = the decoded length, stats[r] = {p_max, mean, rms, entropy}:
+//   p_max = exp(z_argmax - m) / S = 1 / S        mean = d + sum e_k (l_k - d) / S
+//   rms = sqrt(sum e_k (l_k - d)^2 / S)          entropy = log S - sum e_k (z_k - m) / S   (nats)
+// The lengths enter as deviations from d: the mass sits near d, so the sums stay small next to l_k and the spread needs
+// no difference of two large sums.  A dead waypoint is skipped altogether (no 0 * -inf, no 0 * NaN length); a skipped
+// ray and a ray without a live waypoint give four zeros; the distances are ray_argmax_body's, bit for bit.
+// +inf / NaN logits may give non-finite statistics.
+template <bool K512, class Src>
+__device__ __forceinline__ void ray_stats_body(
+    const float* __restrict__ sigma, const Src& src, float* __restrict__ pred_dist, float* __restrict__ gt_dist,
+    float* __restrict__ stats, int R, VolDims v, float step, int K) {
+  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
+  if (r >= R) return;
+  const int lane = threadIdx.x % kWave;
+  const Ray ray = load_ray(src, r, v);
+  float o_pred = 0.f, o_gt = 0.f;
+  float4 o_st = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (ray.f >= 0) {
+    Waypoints<K512, false> w{sigma + (size_t)ray.f * v.Z * v.Y * v.X, ray, v, step, lane, K};
+    Best best;
+    w.first([&](int k, float z, float len) { best.take(z, k, len); });
+    wave_argmax(best);
+    const bool live = best.v != kNegInf;                 // the same in every lane
+    o_pred = (!Src::kTarget && !live) ? 0.f : best.len;
+    o_gt = dist_to(ray, ray.px, ray.py, ray.pz);
+    if (live) {
+      const float m = best.v, d = best.len;
+      float se = 0.f, s1 = 0.f, s2 = 0.f, sz = 0.f;
+      w.second([&](int, float z, float len) {
+        if (z == kNegInf) return;
+        const float e = expf(z - m), dl = len - d;
+        se += e;
+        s1 += e * dl;
+        s2 += e * dl * dl;
+        sz += e * (z - m);
+      });
+      se = wave_sum(se); s1 = wave_sum(s1); s2 = wave_sum(s2); sz = wave_sum(sz);
+      o_st = make_float4(1.f / se, d + s1 / se, sqrtf(s2 / se), logf(se) - sz / se);
+    }
+  }
+  if (lane == 0) {
+    pred_dist[r] = o_pred;
+    if (Src::kTarget) gt_dist[r] = o_gt;
+    reinterpret_cast<float4*>(stats)[r] = o_st;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // The backwards: d loss / d logit of every live entry, scattered through the entry's trilinear weights.
 // A Coef is built from what the forward saved for ray r and gives g * d loss_r / d logit of an entry with softmax
@@ -517,6 +568,23 @@ RAY_KERNEL ray_argmax_cam_any_kernel(const float* __restrict__ sigma, CameraRays
                                      VolDims v, float step, int K) {
   ray_argmax_body<false>(sigma, cam, dist, nullptr, R, v, step, K);
 }
+// the decode with its confidence, on listed rays and on camera rays: stats [R,4]
+RAY_KERNEL ray_stats_kernel(RAY_IN, float* __restrict__ pred_dist, float* __restrict__ gt_dist,
+                            float* __restrict__ stats, int R, VolDims v, float step) {
+  ray_stats_body<true>(sigma, ListedRays{origin, pts, tindex}, pred_dist, gt_dist, stats, R, v, step, kK);
+}
+RAY_KERNEL ray_stats_any_kernel(RAY_IN, float* __restrict__ pred_dist, float* __restrict__ gt_dist,
+                                float* __restrict__ stats, int R, VolDims v, float step, int K) {
+  ray_stats_body<false>(sigma, ListedRays{origin, pts, tindex}, pred_dist, gt_dist, stats, R, v, step, K);
+}
+RAY_KERNEL ray_stats_cam_kernel(const float* __restrict__ sigma, CameraRays cam, float* __restrict__ dist,
+                                float* __restrict__ stats, int R, VolDims v, float step) {
+  ray_stats_body<true>(sigma, cam, dist, nullptr, stats, R, v, step, kK);
+}
+RAY_KERNEL ray_stats_cam_any_kernel(const float* __restrict__ sigma, CameraRays cam, float* __restrict__ dist,
+                                    float* __restrict__ stats, int R, VolDims v, float step, int K) {
+  ray_stats_body<false>(sigma, cam, dist, nullptr, stats, R, v, step, K);
+}
 // what ray_argmax_cam_kernel marches, written out: origin [F,C,3], pts [F,C,Hs,Ws,3]; a thread per pixel
 __global__ __launch_bounds__(kThreads) void cam_rays_kernel(CameraRays cam, float* __restrict__ origin,
                                                             float* __restrict__ pts, int R) {
@@ -554,6 +622,8 @@ inline bool cam_bad(int F, int C, int Hs, int Ws, float u0, float v0, float du, 
   R = (int)n;
   return false;
 }
+// stats [R,4] is stored as one 16-byte value per ray
+inline bool stats_misaligned(const float* stats) { return ((uintptr_t)stats & 15) != 0; }
 std::atomic<int> g_force_streamed{0};   // vidar_ray_force_streamed
 inline bool rm_k512(int K) { return K == kK && !g_force_streamed.load(std::memory_order_relaxed); }
 inline dim3 rm_grid(int R) { return dim3((R + kRaysPerBlock - 1) / kRaysPerBlock); }
@@ -707,6 +777,33 @@ int vidar_ray_argmax_cam_f32(const float* sigma, const float* pix2vox, float* di
   VolDims v{F, Z, Y, X};
   const CameraRays cam{pix2vox, vidar_cam::CamGrid{C, Hs, Ws, u0, v0, du, dv}};
   rm_launch(ray_argmax_cam_kernel, ray_argmax_cam_any_kernel, R, K, (hipStream_t)stream, sigma, cam, dist, R, v, step);
+  return vidar_last_error();
+}
+
+int vidar_ray_stats_f32(const float* sigma, const float* origin, const float* pts, const float* tindex,
+                        float* pred_dist, float* gt_dist, float* stats, int F, int R, int Z, int Y, int X, int K,
+                        float step, void* stream) {
+  VIDAR_ENTER();
+  if (rm_bad(F, R, Z, Y, X, K) || stats_misaligned(stats)) return VIDAR_ERR_BAD_ARG;
+  if (R == 0) return 0;
+  VolDims v{F, Z, Y, X};
+  rm_launch(ray_stats_kernel, ray_stats_any_kernel, R, K, (hipStream_t)stream, sigma, origin, pts, tindex, pred_dist,
+            gt_dist, stats, R, v, step);
+  return vidar_last_error();
+}
+
+int vidar_ray_stats_cam_f32(const float* sigma, const float* pix2vox, float* dist, float* stats, int F, int C, int Hs,
+                            int Ws, float u0, float v0, float du, float dv, int Z, int Y, int X, int K, float step,
+                            void* stream) {
+  VIDAR_ENTER();
+  int R = 0;
+  if (cam_bad(F, C, Hs, Ws, u0, v0, du, dv, R) || rm_bad(F, R, Z, Y, X, K) || stats_misaligned(stats))
+    return VIDAR_ERR_BAD_ARG;
+  if (R == 0) return 0;
+  VolDims v{F, Z, Y, X};
+  const CameraRays cam{pix2vox, vidar_cam::CamGrid{C, Hs, Ws, u0, v0, du, dv}};
+  rm_launch(ray_stats_cam_kernel, ray_stats_cam_any_kernel, R, K, (hipStream_t)stream, sigma, cam, dist, stats, R, v,
+            step);
   return vidar_last_error();
 }
 

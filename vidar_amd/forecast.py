@@ -5,6 +5,7 @@
   bev_image      bird's-eye picture of labelled points; a restatement of the reference's `_dbg_draw_pc_function`
                  (utils/e2e_predictor_utils.py:188-224), NOT a pixel copy of what matplotlib renders
   depth_overlay  per-pixel depth laid over the camera frame
+  confidence_mask / confidence_overlay  which rays pass a threshold on ray_ops.ray_stats' statistics; p_max as a picture
 torch + PIL only; nothing here launches a kernel of its own."""
 from __future__ import annotations
 
@@ -128,17 +129,24 @@ def depth_overlay(depth, frame_u8, near=1.0, far=60.0, alpha=160):
     index = clamp(floor((far - d) / (far - near) * 255 + 0.5), 0, 255) into colour_table (near = red end, computed in
     fp64); out = (alpha * colour + (255 - alpha) * image + 127) // 255 in integers where there is a return, the image
     elsewhere."""
+    if not far > near:
+        raise ValueError("alpha must be 0..255 and far > near")
+    return _ramp_overlay(depth, frame_u8, alpha, lambda d: (far - d) / (far - near))
+
+
+def _ramp_overlay(value, frame_u8, alpha, unit):
+    """depth_overlay's strided grid, colour ramp and blend; `unit` maps the fp64 values to [0, 1] of the ramp (1 = red)"""
     H, W = frame_u8.shape[:2]
-    Hs, Ws = depth.shape
+    Hs, Ws = value.shape
     s = -(-H // Hs)
     if s < 1 or -(-H // s) != Hs or -(-W // s) != Ws:
-        raise ValueError(f"depth {tuple(depth.shape)} is no strided grid of a {H} x {W} frame")
+        raise ValueError(f"depth {tuple(value.shape)} is no strided grid of a {H} x {W} frame")
     a = int(alpha)
-    if not 0 <= a <= 255 or not far > near:
+    if not 0 <= a <= 255:
         raise ValueError("alpha must be 0..255 and far > near")
     dev = frame_u8.device
-    d = depth.to(dev).double()
-    idx = torch.floor((far - d) / (far - near) * 255.0 + 0.5)
+    d = value.to(dev).double()
+    idx = torch.floor(unit(d) * 255.0 + 0.5)
     live = (d > 0) & torch.isfinite(d)
     idx = torch.where(live, idx, torch.zeros_like(idx)).clamp(0, 255).long()
     ys = torch.arange(H, device=dev) // s
@@ -148,6 +156,26 @@ def depth_overlay(depth, frame_u8, near=1.0, far=60.0, alpha=160):
     img = frame_u8.to(torch.int32)
     mixed = (a * colour + (255 - a) * img + 127) // 255
     return torch.where(live[..., None], mixed, img).to(torch.uint8)
+
+
+def confidence_mask(stats, min_prob=None, max_rms=None):
+    """stats [..., 4] = (p_max, mean, rms, entropy) of ray_ops.ray_stats -> bool [...]: True where the ray is kept, i.e.
+    p_max >= min_prob and rms <= max_rms for each threshold that is given (rms in the unit of `stats`: metres for what
+    the head and ViDAR.forecast return).  A NaN statistic fails the threshold it is held against; with both thresholds
+    None every ray is kept, NaN or not.  Pure torch, any device."""
+    keep = torch.ones(stats.shape[:-1], dtype=torch.bool, device=stats.device)
+    if min_prob is not None:
+        keep = keep & (stats[..., 0] >= float(min_prob))
+    if max_rms is not None:
+        keep = keep & (stats[..., 2] <= float(max_rms))
+    return keep
+
+
+def confidence_overlay(p_max, frame_u8, alpha=160):
+    """p_max [Hs, Ws] (0 or NaN = no return) over frame_u8 [H, W, 3] uint8 -> [H, W, 3] uint8: depth_overlay's strided
+    grid, integer colour ramp and blend with the colour index clamp(floor(p * 255 + 0.5), 0, 255), so that p = 1 is the
+    red end and p -> 0 the blue one."""
+    return _ramp_overlay(p_max, frame_u8, alpha, lambda p: p)
 
 
 def save_png(img_u8, path):

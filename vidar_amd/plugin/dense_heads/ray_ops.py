@@ -196,6 +196,36 @@ def ray_argmax_cam(sigma, pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0, step=1.0,
     return dist
 
 
+def ray_stats(sigma, origin, pts, tindex, step=1.0, K=K_SAMPLES):
+    """ray_argmax with its confidence -> (pred_dist [R], gt_dist [R], stats [R, 4]) in voxel units, no grad.  The two
+    distances are ray_argmax's bits; stats = (p_max, mean, rms, entropy) of the softmax over the ray's live waypoints
+    (include/vidar_hip.h: vidar_ray_stats_f32), four zeros for a skipped ray or one without a live waypoint."""
+    sigma, origin, pts, tindex = _f(sigma.detach()), _f(origin), _f(pts), _f(tindex)
+    F_, R, Z, Y, X = _dims(sigma, pts)
+    pred = torch.empty(R, device=sigma.device); gt = torch.empty_like(pred)
+    stats = torch.empty((R, 4), device=sigma.device)
+    check(lib().vidar_ray_stats_f32(ptr(sigma), ptr(origin), ptr(pts), ptr(tindex), ptr(pred), ptr(gt), ptr(stats),
+                                    F_, R, Z, Y, X, int(K), step, stream_of(sigma)), "ray_stats")
+    return pred, gt, stats
+
+
+def ray_stats_cam(sigma, pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0, step=1.0, K=K_SAMPLES):
+    """ray_argmax_cam with its confidence -> (dist [F,C,Hs,Ws], stats [F,C,Hs,Ws,4]) in voxel units, no grad: dist is
+    ray_argmax_cam's bits, stats as in ray_stats (four zeros where the ray meets nothing)."""
+    sigma, pix2vox = _f(sigma.detach()), _f(pix2vox)
+    geom = _cam_args(pix2vox, hw, u0, v0, du, dv)
+    F_, Z, Y, X = sigma.shape
+    if geom[0] != F_:
+        raise ValueError(f"pix2vox holds {geom[0]} frames, sigma {F_}")
+    if pix2vox.device != sigma.device:
+        raise RuntimeError(f"pix2vox is on {pix2vox.device}, sigma on {sigma.device}")
+    dist = torch.empty(geom[:4], device=sigma.device)
+    stats = torch.empty((*geom[:4], 4), device=sigma.device)
+    check(lib().vidar_ray_stats_cam_f32(ptr(sigma), ptr(pix2vox), ptr(dist), ptr(stats), *geom, Z, Y, X, int(K), step,
+                                        stream_of(sigma)), "ray_stats_cam")
+    return dist, stats
+
+
 def cam_rays(pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0):
     """the rays ray_argmax_cam marches, written out: -> (origin [F,C,3], pts [F,C,Hs,Ws,3]) in voxel units."""
     pix2vox = _f(pix2vox)

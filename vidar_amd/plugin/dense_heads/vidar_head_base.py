@@ -25,6 +25,13 @@ from ..registry import HEADS, build_positional_encoding, build_transformer
 from ..utils import e2e_predictor_utils
 from . import ray_ops
 
+_STATS_KEY = "ray_stats"      # entry of a pred_dict: decode with ray_ops.ray_stats and return "pred_stats" as well
+
+
+def _metre_stats(stats, scale):
+    """[..., 4] (p_max, mean, rms, entropy) of ray_ops.ray_stats: the two lengths from voxel units to metres"""
+    return stats * const_tensor([1.0, scale, scale, 1.0], stats.device, stats.dtype)
+
 
 @HEADS.register_module()
 class ViDARHeadTemplate(nn.Module):
@@ -121,15 +128,25 @@ class ViDARHeadTemplate(nn.Module):
         for b in range(bs):
             per_frame = []
             for t in range(num_frames):
-                mask = (tindex[b] == t) & (gt_dist[b] > 0.)
-                if self.eval_within_grid:
-                    mask = mask & e2e_predictor_utils.get_inside_mask(points[b], pc_range)
+                mask = self._rendered_mask(points[b], tindex[b], gt_dist[b], t, pc_range)
                 p = points[b][mask]
                 r = p - origin[b, t].view(1, 3)
                 rn = r / torch.sqrt((r ** 2).sum(1, keepdim=True))
                 per_frame.append(origin[b, t].view(1, 3) + rn * pred_dist[b][mask].view(-1, 1))
             pcds.append(per_frame)
         return pcds
+
+    def _rendered_mask(self, points, tindex, gt_dist, t, pc_range):
+        """the rays of one sample that get_rendered_pcds keeps for frame t"""
+        mask = (tindex == t) & (gt_dist > 0.)
+        if self.eval_within_grid:
+            mask = mask & e2e_predictor_utils.get_inside_mask(points, pc_range)
+        return mask
+
+    def get_rendered_stats(self, points, tindex, gt_dist, stats, pc_range, num_frames):
+        """per-ray values stats [bs, N, 4] laid out like get_rendered_pcds' points: list[bs] of list[frames] of [n, 4]"""
+        return [[stats[b][self._rendered_mask(points[b], tindex[b], gt_dist[b], t, pc_range)]
+                 for t in range(num_frames)] for b in range(len(stats))]
 
     def get_rendered_rays(self, origin, points, tindex, gt_dist, pred_dist, pc_range):
         """get_rendered_pcds without the boolean selections (no host sync): every ray keeps its place, the selection
@@ -254,7 +271,9 @@ class ViDARHeadBase(ViDARHeadTemplate):
     def get_point_cloud_prediction(self, pred_dict, gt_points, start_idx, tgt_bev_h, tgt_bev_w,
                                    tgt_pc_range, img_metas=None, batched_origin_points=None, as_rays=False):
         """arg-max decode (:663-752) -> dict(pred_pcds, gt_pcds, origin); as_rays: the dict of get_rendered_rays
-        instead (the device metrics' input: nothing is selected on the host)."""
+        instead (the device metrics' input: nothing is selected on the host).  A true pred_dict["ray_stats"] (set by
+        render_rays, never by the detector's evaluation) decodes with ray_ops.ray_stats -- the same distances -- and adds
+        pred_stats: list[bs] of list[frames] of [n, 4], row for row with pred_pcds, mean and rms in metres."""
         bev_preds = pred_dict["next_bev_preds"].float()
         valid_frames = pred_dict["valid_frames"]
         F_, inter_num, bs, token_num, Z = bev_preds.shape
@@ -262,21 +281,27 @@ class ViDARHeadBase(ViDARHeadTemplate):
         origin_grids, origin_pts, gt_grids, gt_xyz, tindex = self._process_gt_points(
             bev_preds, gt_points, batched_origin_points, valid_frames, start_idx, F_, H, W, tgt_pc_range)
         last = bev_preds[:, -1:]
-        pred, gt = [], []
+        # render_rays(return_stats=True) asks for the confidence through the dict every head hands on
+        decode = ray_ops.ray_stats if pred_dict.get(_STATS_KEY) else ray_ops.ray_argmax
+        pred, gt, stats = [], [], []
         for b in range(bs):
-            p, g = ray_ops.ray_argmax(self._volumes(last, b, Z, H, W), origin_grids[b],
-                                      torch.nan_to_num(gt_grids[b], nan=-1.0e6), tindex[b],
-                                      self.ray_grid_step, self.ray_grid_num)
-            pred.append(p); gt.append(g)
+            p, g, *s = decode(self._volumes(last, b, Z, H, W), origin_grids[b],
+                              torch.nan_to_num(gt_grids[b], nan=-1.0e6), tindex[b],
+                              self.ray_grid_step, self.ray_grid_num)
+            pred.append(p); gt.append(g); stats.extend(s)
         scale = (tgt_pc_range[3] - tgt_pc_range[0]) / W
         pred = torch.stack(pred) * scale
         gt = torch.stack(gt) * scale
         if as_rays:
             return self.get_rendered_rays(origin_pts, gt_xyz, tindex, gt, pred, tgt_pc_range)
-        return dict(
+        out = dict(
             pred_pcds=self.get_rendered_pcds(origin_pts, gt_xyz, tindex, gt, pred, tgt_pc_range),
             gt_pcds=self.get_rendered_pcds(origin_pts, gt_xyz, tindex, gt, gt, tgt_pc_range),
             origin=origin_pts)
+        if stats:
+            out["pred_stats"] = self.get_rendered_stats(gt_xyz, tindex, gt, _metre_stats(torch.stack(stats), scale),
+                                                        tgt_pc_range, origin_pts.shape[1])
+        return out
 
     def _ray_frame_labels(self, valid_frames):
         """the value the last column of a point holds for each frame slot of `valid_frames`"""
@@ -292,13 +317,16 @@ class ViDARHeadBase(ViDARHeadTemplate):
         return np.tile(np.eye(4), (len(img_metas), len(valid_frames), 1, 1))
 
     @torch.no_grad()
-    def render_cameras(self, pred_dict, img_metas, tgt_bev_h, tgt_bev_w, tgt_pc_range, cameras=None, stride=4):
+    def render_cameras(self, pred_dict, img_metas, tgt_bev_h, tgt_bev_w, tgt_pc_range, cameras=None, stride=4,
+                       return_stats=False):
         """The decode seen from the cameras: one ray per `stride` x `stride` block of every camera's pixels, through the
         block's centre, marched by ray_ops.ray_argmax_cam (the rays are never stored).
         cameras: indices into img_metas[b]["lidar2img"] (None = all; their images must share one size).
         -> depth [bs, F, C, Hs, Ws], Hs = ceil(H / stride): metres along the ray (voxel units times the BEV cell size, the
         decode's own scale), 0 where the ray meets nothing.  The cameras of a future frame are the current frame's, by the
-        rigid-rig assumption of vidar_amd.forecast.pix2vox."""
+        rigid-rig assumption of vidar_amd.forecast.pix2vox.
+        return_stats: march with ray_ops.ray_stats_cam instead (the same depth bits) -> (depth, stats [bs, F, C, Hs, Ws, 4]):
+        (p_max, mean, rms, entropy) of the softmax along each ray, mean and rms in metres, zeros where it meets nothing."""
         from ...forecast import pix2vox
         stride = int(stride)
         if stride < 1:
@@ -308,7 +336,8 @@ class ViDARHeadBase(ViDARHeadTemplate):
         last = bev_preds[:, -1:]
         align = self.frame_alignment(pred_dict["valid_frames"], img_metas)
         scale = (tgt_pc_range[3] - tgt_pc_range[0]) / tgt_bev_w
-        out = []
+        decode = ray_ops.ray_stats_cam if return_stats else ray_ops.ray_argmax_cam
+        out, stats = [], []
         for b in range(bs):
             meta = img_metas[b]
             cams = list(range(len(meta["lidar2img"]))) if cameras is None else [int(c) for c in cameras]
@@ -317,15 +346,20 @@ class ViDARHeadBase(ViDARHeadTemplate):
                 raise ValueError(f"the cameras' images must share one size, got {sorted(sizes)}")
             H, W = sizes.pop()
             m = pix2vox([meta["lidar2img"][c] for c in cams], tgt_pc_range, tgt_bev_h, tgt_bev_w, Z, align[b])
-            d = ray_ops.ray_argmax_cam(self._volumes(last, b, Z, tgt_bev_h, tgt_bev_w), m.to(bev_preds.device),
-                                       (-(-H // stride), -(-W // stride)), u0=stride / 2.0, v0=stride / 2.0,
-                                       du=float(stride), dv=float(stride), step=self.ray_grid_step, K=self.ray_grid_num)
+            d = decode(self._volumes(last, b, Z, tgt_bev_h, tgt_bev_w), m.to(bev_preds.device),
+                       (-(-H // stride), -(-W // stride)), u0=stride / 2.0, v0=stride / 2.0,
+                       du=float(stride), dv=float(stride), step=self.ray_grid_step, K=self.ray_grid_num)
+            if return_stats:
+                d, s = d
+                stats.append(s)
             out.append(d * scale)
+        if return_stats:
+            return torch.stack(out), _metre_stats(torch.stack(stats), scale)
         return torch.stack(out)
 
     @torch.no_grad()
     def render_rays(self, pred_dict, directions=None, end_points=None, *, tgt_bev_h, tgt_bev_w, tgt_pc_range,
-                    img_metas=None, start_idx=0, batched_origin_points=None):
+                    img_metas=None, start_idx=0, batched_origin_points=None, return_stats=False):
         """The decode of get_point_cloud_prediction along rays handed in instead of taken from `gt_points`: the same
         origin, voxel mapping, ray_argmax call and masking, because it IS that call.  Exactly one of
           directions [R, 3]: unit directions in every predicted frame's own sensor coordinates, shared by all samples
@@ -333,7 +367,10 @@ class ViDARHeadBase(ViDARHeadTemplate):
           end_points list[bs] of [N, >=4]: points in the layout of gt_points (xyz first, the frame label last).
         -> list[bs] of list[frames] of [n, 3] predicted points, ray order kept within a frame.  A ray without a live
         waypoint comes back at waypoint 0 (the reference's decode); with eval_within_grid the end point's own
-        membership still selects the ray, as for ground truth."""
+        membership still selects the ray, as for ground truth.
+        return_stats: decode with ray_ops.ray_stats instead (the same points) -> (points, stats): list[bs] of list[frames]
+        of [n, 4], row for row the points' (p_max, mean, rms, entropy), mean and rms in metres; a ray without a live
+        waypoint has four zeros."""
         if (directions is None) == (end_points is None):
             raise ValueError("give either directions or end_points")
         if end_points is None:
@@ -342,6 +379,8 @@ class ViDARHeadBase(ViDARHeadTemplate):
             cols = [torch.cat([d, d.new_full((d.shape[0], 1), lab)], 1)
                     for lab in self._ray_frame_labels(pred_dict["valid_frames"])]
             end_points = [torch.cat(cols, 0)] * bs
-        return self.get_point_cloud_prediction(pred_dict, end_points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range,
-                                               img_metas=img_metas,
-                                               batched_origin_points=batched_origin_points)["pred_pcds"]
+        if return_stats:
+            pred_dict = dict(pred_dict, **{_STATS_KEY: True})
+        out = self.get_point_cloud_prediction(pred_dict, end_points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range,
+                                              img_metas=img_metas, batched_origin_points=batched_origin_points)
+        return (out["pred_pcds"], out["pred_stats"]) if return_stats else out["pred_pcds"]

@@ -341,7 +341,8 @@ class ViDAR(nn.Module):
 
     # ---- forecast without ground truth ---------------------------------------------------------------
     @torch.no_grad()
-    def forecast(self, img=None, img_metas=None, rays=None, cameras=None, stride=4, img_feats=None):
+    def forecast(self, img=None, img_metas=None, rays=None, cameras=None, stride=4, img_feats=None, stats=False,
+                 min_prob=None, max_rms=None):
         """What the model expects to be seen, with no future sweep to take rays from: the no-grad history, future decoder
         and forward_head of forward_test, then
           rays [R, 3] unit directions (vidar_amd.forecast.lidar_pattern) -> "sweep": list[bs] of list[frames] of [n, 3]
@@ -349,25 +350,47 @@ class ViDAR(nn.Module):
               range; "sweep_index": for each of them the rows of `rays` that were kept, in order;
           cameras: camera indices or "all" -> "depth" [bs, F, C, Hs, Ws], metres along the ray of every stride-th pixel of
               the current frame's cameras, 0 = nothing met (future_pred_head.render_cameras; rigid-rig assumption).
-        Frame 0 is the current frame, frames 1.. the test futures.  -> dict(valid_frames, sweep?, sweep_index?, depth?)."""
+        Frame 0 is the current frame, frames 1.. the test futures.  -> dict(valid_frames, sweep?, sweep_index?, depth?).
+          stats=True adds the confidence of every decoded ray (ray_ops.ray_stats: p_max, mean, rms, entropy of the softmax
+              along the ray; mean and rms in metres): "sweep_stats", [n, 4] row for row with "sweep", and "depth_stats"
+              [bs, F, C, Hs, Ws, 4];
+          min_prob / max_rms (metres): a ray whose p_max < min_prob or whose rms > max_rms is dropped from the sweep
+              ("sweep_index" names the rows of `rays` that are left) and its pixel's depth becomes 0, "nothing met"
+              (vidar_amd.forecast.confidence_mask).  A threshold computes the statistics and returns them as stats=True does.
+        Without the three the decode, its launches and the result are those of the plain arg-max."""
         if img_metas is None or (img is None and img_feats is None):
             raise ValueError("forecast needs img_metas and img (or img_feats)")
+        from ...forecast import confidence_mask
+        stats = bool(stats) or min_prob is not None or max_rms is not None
+        more = dict(return_stats=True) if stats else {}
         pred_dict, cur_metas = self._future_pred_dict(img_metas, img, img_feats)
         geom = dict(tgt_bev_h=self.bev_h, tgt_bev_w=self.bev_w, tgt_pc_range=self.point_cloud_range)
         out = dict(valid_frames=list(pred_dict["valid_frames"]))
         if rays is not None:
             dev = pred_dict["next_bev_preds"].device
-            sweep = self.future_pred_head.render_rays(pred_dict, directions=rays.to(dev), img_metas=cur_metas, **geom)
+            sweep = self.future_pred_head.render_rays(pred_dict, directions=rays.to(dev), img_metas=cur_metas, **geom,
+                                                      **more)
             # The model says nothing about the world outside its volume, and the decode can put a point there: it turns
             # voxel lengths into metres with the BEV cell size alone (exact only for cubic voxels) and a sample half a
             # voxel outside the volume still counts.  Like the metrics (compute_chamfer_distance_inner), keep the range.
+            if stats:
+                sweep, sweep_stats = sweep
             keep = [[e2e_predictor_utils.get_inside_mask(p, self.point_cloud_range) for p in per] for per in sweep]
+            if stats:
+                keep = [[k & confidence_mask(s, min_prob, max_rms) for k, s in zip(ks, per)]
+                        for ks, per in zip(keep, sweep_stats)]
+                out["sweep_stats"] = [[s[k] for s, k in zip(per, ks)] for per, ks in zip(sweep_stats, keep)]
             out["sweep"] = [[p[k] for p, k in zip(per, ks)] for per, ks in zip(sweep, keep)]
             out["sweep_index"] = [[k.nonzero().squeeze(-1) for k in ks] for ks in keep]
         if cameras is not None:
             cams = None if isinstance(cameras, str) and cameras == "all" else cameras
-            out["depth"] = self.future_pred_head.render_cameras(pred_dict, cur_metas, cameras=cams, stride=stride,
-                                                                **geom)
+            depth = self.future_pred_head.render_cameras(pred_dict, cur_metas, cameras=cams, stride=stride, **geom,
+                                                         **more)
+            if stats:
+                depth, out["depth_stats"] = depth
+                depth = torch.where(confidence_mask(out["depth_stats"], min_prob, max_rms), depth,
+                                    torch.zeros_like(depth))
+            out["depth"] = depth
         return out
 
     def _save_prediction(self, pred_pcd, img_meta, frame_idx):
