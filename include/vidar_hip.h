@@ -461,6 +461,32 @@ int vidar_ray_stats_cam_f32(const float* sigma, const float* pix2vox, float* dis
                             float u0, float v0, float du, float dv, int Z, int Y, int X, int K, float step,
                             void* stream);
 
+/* Occupancy evidence (csrc/ray_march.hip, ray_occupancy_body): the softmax of the decode scattered back onto the voxels
+ * it was read from -- an inverse sensor model of the forecast.  Same rays, waypoints and sampler as vidar_ray_argmax_f32 /
+ * vidar_ray_argmax_cam_f32; a waypoint is dead iff its sample is exactly 0 or its coordinate is NaN.  Over the live
+ * waypoints of a ray, with m = max z_k, e_k = exp(z_k - m), S = sum e_k:
+ *   p_k = e_k / S                  the return lies at k
+ *   b_k = sum_{j > k, live} p_j    the return lies beyond k: the ray passed k
+ * and with w_kc the eight trilinear weights of waypoint k (corners outside the volume dropped, as the zero padding
+ * dropped them from the sample):
+ *   hit [f, corner c of k] += p_k * w_kc          free[f, corner c of k] += b_k * w_kc
+ * hit, free [F,Z,Y,X] f32 are zeroed by the call.  A dead waypoint, a skipped ray and a ray without a live waypoint add
+ * nothing; R == 0 (an empty camera grid) leaves zeros.  b_k is a sum of non-negative terms taken from the far end, so
+ * b_k >= 0 and the last live waypoint has b == 0 exactly.  +inf or NaN logits may give non-finite output.
+ * The adds are those of the ray backwards: fp32 atomics, into 8 private copies of both volumes given a `workspace` of
+ * *bytes of vidar_ray_occupancy_workspace_bytes(F,Z,Y,X,&bytes) (NULL: straight into the outputs; results agree to fp32
+ * summation order).  Deterministic mode: the query gives 8 * (2*F*Z*Y*X + 2) and both volumes are accumulated in fixed
+ * point -- the same bits for every K form and ray order; a missing or small workspace is VIDAR_ERR_BAD_ARG.
+ * Other VIDAR_ERR_BAD_ARG cases are those of the arg-max entries; the query's: a NULL `bytes`, non-positive dimensions. */
+int vidar_ray_occupancy_workspace_bytes(int F, int Z, int Y, int X, int64_t* bytes);
+int vidar_ray_occupancy_f32(const float* sigma, const float* origin, const float* pts, const float* tindex,
+                            float* hit, float* free_, int F, int R, int Z, int Y, int X, int K, float step,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int vidar_ray_occupancy_cam_f32(const float* sigma, const float* pix2vox, float* hit, float* free_,
+                                int F, int C, int Hs, int Ws, float u0, float v0, float du, float dv,
+                                int Z, int Y, int X, int K, float step,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Modulated deformable convolution v2 (backbone, "next" row SURVEY 8f-1).  Replaces the sampling
  * kernels of mmcv.ops.ModulatedDeformConv2dPack (mmcv-full 1.4.0, third party); the convolution

@@ -1052,6 +1052,106 @@ def bench_ray_stats(which):
                   for r in rows))
 
 
+def bench_ray_occupancy(which):
+    """occupancy evidence (vidar_ray_occupancy_f32 / vidar_ray_occupancy_cam_f32) on a 16 x 200 x 200 volume, step 1, at
+    K = 512 (register form) and K = 1026 (streamed), default and deterministic mode: the 34 560 rays of
+    vidar_amd.forecast.lidar_pattern() from the volume's centre, and 6 cameras of 900 x 1600 pixels at strides 4 and 8.
+    In the same process each row stands next to ray_stats on the same rays (the march without the scatter) and, for the
+    listed rays, the ray_ce backward (the same scatter pattern into one volume).  HIP events, the ops alternating, three
+    repeats of 2 warm-up + 5 timed calls (20 for the listed rays); the spread is (max - min) / median over the repeats.
+    Writes profiles/kbench_ray_occupancy.md."""
+    from vidar_amd import deterministic
+    from vidar_amd import forecast as FC
+    from vidar_amd.plugin.dense_heads.ray_ops import (cam_rays, ray_ce, ray_occupancy, ray_occupancy_cam, ray_stats,
+                                                      ray_stats_cam)
+    from vidar_amd.synthetic import PC_RANGE, camera_matrices
+    dev = torch.device("cuda", 0)
+    Z, Y, X, C, H, W = 16, 200, 200, 6, 900, 1600
+    sigma = torch.randn(1, Z, Y, X, generator=torch.Generator().manual_seed(0)).to(dev)
+    o = torch.tensor([[X / 2.0, Y / 2.0, Z / 4.0]], device=dev)
+    p = o + FC.lidar_pattern().to(dev)
+    ti = torch.zeros(p.shape[0], device=dev)
+    m = FC.pix2vox(camera_matrices(img_hw=(H, W))[:C], PC_RANGE, Y, X, Z).to(dev)
+    size = torch.tensor([X, Y, Z], device=dev, dtype=torch.float32)
+    med = lambda v: float(np.median(v))
+    spread = lambda v: (max(v) - min(v)) / med(v)
+    rows = []
+
+    def live_waypoints(origin, pts, K):
+        """waypoints with a corner inside the volume (random-normal logits: no sample is an exact zero)"""
+        n = 0
+        k = (torch.arange(K, device=dev, dtype=torch.float32) + 0.5).view(1, K, 1)
+        for i in range(0, pts.shape[0], 32768):
+            d = pts[i:i + 32768] - origin[i:i + 32768]
+            d = d / d.norm(dim=1, keepdim=True)
+            pix = origin[i:i + 32768, None] + d[:, None] * k - 0.5
+            n += int(((pix > -1) & (pix < size)).all(-1).sum())
+        return n
+
+    def compare(R, K, det, live, occ, stats, ce_bwd=None, it=5, **tag):
+        with deterministic.use(det):
+            hit, free = occ()
+            ts = {"occupancy": [], "ray_stats": [], "ray_ce_bwd": []}
+            for _ in range(3):
+                ts["occupancy"].append(timeit(occ, warm=2, it=it)); ts["ray_stats"].append(timeit(stats, warm=2, it=it))
+                if ce_bwd is not None:
+                    ts["ray_ce_bwd"].append(timeit(ce_bwd, warm=2, it=it))
+        t = med(ts["occupancy"])
+        row = dict(**tag, R=R, K=K, form="register" if K == 512 else "streamed", mode="deterministic" if det else "default",
+                   occupancy_ms=[round(v, 3) for v in ts["occupancy"]], occupancy_median_ms=round(t, 3),
+                   occupancy_spread=round(spread(ts["occupancy"]), 4), ray_stats_median_ms=round(med(ts["ray_stats"]), 3),
+                   ray_stats_spread=round(spread(ts["ray_stats"]), 4),
+                   ray_ce_bwd_median_ms=round(med(ts["ray_ce_bwd"]), 3) if ce_bwd else None,
+                   ray_ce_bwd_spread=round(spread(ts["ray_ce_bwd"]), 4) if ce_bwd else None,
+                   live_waypoints=live, atomic_adds=live * 16, giga_adds_per_s=round(live * 16 / t / 1e6, 1),
+                   hit_sum=round(float(hit.sum()), 2), free_max=round(float(free.max()), 2))
+        rows.append(row)
+        report("ray_occupancy", t, **row)
+
+    for K in (512, 1026):
+        live = live_waypoints(o.expand(p.shape[0], 3), p, K)
+        sg = sigma.clone().requires_grad_(True)
+        for det in (False, True):
+            with deterministic.use(det):
+                ce, _ = ray_ce(sg, o, p, ti, 1.0, K)
+            g = torch.ones_like(ce)
+            compare(p.shape[0], K, det, live, lambda: ray_occupancy(sigma, o, p, ti, 1.0, K),
+                    lambda: ray_stats(sigma, o, p, ti, 1.0, K),
+                    lambda: torch.autograd.grad(ce, sg, g, retain_graph=True), it=20, rays="sweep", stride="-")
+    for K in (512, 1026):
+        for stride in (8, 4):
+            Hs, Ws = -(-H // stride), -(-W // stride)
+            geom = ((Hs, Ws), stride / 2.0, stride / 2.0, float(stride), float(stride))
+            co, cp = cam_rays(m, *geom)
+            live = live_waypoints(co[0, :, None, None].expand(C, Hs, Ws, 3).reshape(-1, 3), cp[0].reshape(-1, 3), K)
+            del co, cp
+            for det in (False, True):
+                compare(C * Hs * Ws, K, det, live, lambda: ray_occupancy_cam(sigma, m, *geom, 1.0, K),
+                        lambda: ray_stats_cam(sigma, m, *geom, 1.0, K), rays="camera", stride=stride)
+    out = os.environ.get("VIDAR_KBENCH_OUT")
+    path = Path(out) if out else ROOT / "profiles" / "kbench_ray_occupancy.md"
+    cell = lambda v: "-" if v is None else v
+    path.write_text(
+        "# Occupancy evidence on an MI355X: `python tools/kbench.py ray_occupancy`\n\n"
+        f"Volume {Z} x {Y} x {X}, random-normal logits, step 1.  `sweep`: the {p.shape[0]} rays of\n"
+        f"`vidar_amd.forecast.lidar_pattern()` from the volume's centre (`vidar_ray_occupancy_f32`); `camera`: {C} cameras of\n"
+        f"{H} x {W} pixels, the pin-hole rig of `vidar_amd.synthetic.camera_matrices` (`vidar_ray_occupancy_cam_f32`).  K = 512\n"
+        "runs the register form, K = 1026 the streamed one; `default` adds with fp32 atomics into 8 private copies of both\n"
+        "volumes, `deterministic` measures and then adds in 64-bit fixed point.  Next to each row, in the same process on the\n"
+        "same rays: `ray_stats` (the march without the scatter) and, for the sweep, the `ray_ce` backward through autograd\n"
+        "(the same scatter pattern into one volume).  HIP events, the ops alternating, 3 repeats of 2 warm-up + 5 timed calls\n"
+        "(20 for the sweep); spread = (max - min) / median.  Each call allocates its outputs and its workspace.\n"
+        "`atomic adds` = live waypoints x 8 corners x 2 volumes (an upper bound: corners outside the volume are dropped; the\n"
+        "deterministic mode visits them twice, once to measure); `G adds / s` = that count over the median time.\n\n"
+        "```\n" + json.dumps({"device": torch.cuda.get_device_name(0)}) + "\n"
+        + "\n".join(json.dumps(dict(op="ray_occupancy", **r)) for r in rows) + "\n```\n\n"
+        "| rays | stride | R | K | mode | occupancy ms (median) | spread | ray_stats ms | ray_ce_bwd ms | live waypoints | atomic adds | G adds / s |\n"
+        "|---|---|---|---|---|---|---|---|---|---|---|---|\n"
+        + "".join(f"| {r['rays']} | {r['stride']} | {r['R']} | {r['K']} | {r['mode']} | {r['occupancy_median_ms']} | "
+                  f"{r['occupancy_spread']} | {r['ray_stats_median_ms']} | {cell(r['ray_ce_bwd_median_ms'])} | "
+                  f"{r['live_waypoints']} | {r['atomic_adds']} | {r['giga_adds_per_s']} |\n" for r in rows))
+
+
 if __name__ == "__main__":
     import os
     if os.environ.get("VIDAR_MSDA_ITEM_ORDER") is not None:          # A/B of the gather kernels' item order (0 banded, 1 head-major)

@@ -11,6 +11,8 @@
 //                 (cam_ray.h; no counterpart in the reference); cam_rays writes those rays out
 //   ray_stats / ray_stats_cam : the two decodes with the softmax along the ray summarised next to the distance
 //                 (peak probability, mean length, spread, entropy; no counterpart in the reference)
+//   ray_occupancy / ray_occupancy_cam : the decode's softmax scattered back onto the voxels, mass at / beyond every
+//                 waypoint (hit / free evidence of an occupancy grid; no counterpart in the reference)
 // The reference materialises ~8 arrays of [rays, 513] floats per call (waypoints, lengths, masks,
 // sampled logits, -inf masks, softmax); here one wave owns one ray, its 512 waypoints live in
 // registers (8 per lane) and only O(1) values per ray ever reach HBM.
@@ -263,6 +265,23 @@ struct Waypoints {
       first(fn);
     }
   }
+  // A further visit in passes of 64 consecutive waypoints (k = 64 j + lane, one per lane: the layout of the registers)
+  // from the LAST pass to the first: fn(k, logit).  Every lane runs every pass -- a lane with k >= K gets -inf, never
+  // sampled -- so fn may hold cross-lane operations.
+  template <class Fn>
+  __device__ __forceinline__ void passes_down(Fn fn) const {
+    if (K512) {
+#pragma unroll
+      for (int j = kPerLane - 1; j >= 0; --j) fn(lane + j * kWave, f[j]);
+    } else {
+      for (int j = (K + kWave - 1) / kWave - 1; j >= 0; --j) {
+        const int k = lane + j * kWave;
+        float z = kNegInf, l;
+        if (k < K) sample(k, z, l);
+        fn(k, z);
+      }
+    }
+  }
 };
 
 // END_POINT, in the bodies below: the ray's end point is an entry of its own in front of the K waypoints (lane 0 carries
@@ -494,6 +513,74 @@ __device__ __forceinline__ void ray_bwd_body(
 }
 
 // ---------------------------------------------------------------------------------------------
+// Occupancy evidence: the decode's softmax, scattered back onto the voxels it was read from (an inverse sensor model).
+// Over the live waypoints of a ray (live as in ray_stats_body), with m = max z_k, e_k = exp(z_k - m), S = sum e_k:
+//   p_k = e_k / S            the return lies at k          hit [f, corner c of k] += p_k * w_kc
+//   b_k = sum_{j>k} p_j      the ray passed k              free[f, corner c of k] += b_k * w_kc
+// w_kc: the trilinear weights the logit was sampled with; corners outside the volume are dropped, as the zero padding
+// dropped them from the sample.  A dead waypoint, a skipped ray and a ray without a live waypoint add nothing.
+// Visit 1 / 2 find m and S as ray_stats_body does; the third visit (Waypoints::passes_down) walks the passes of 64
+// consecutive waypoints from the far end: b of a pass is the wave's exclusive suffix sum of p plus the carry of the later
+// passes -- a sum of non-negative terms, never 1 - prefix, so b >= 0 and the last live waypoint has b == 0 exactly.
+// The scatter is the backwards': a lane pair per waypoint (two half-passes of 32), the private copies, the Acc policy.
+// ---------------------------------------------------------------------------------------------
+// exclusive suffix sum over the wave: lane l gets v[l+1] + ... + v[63], lane 63 gets 0
+__device__ __forceinline__ float wave_suffix_excl(float v, int lane) {
+  float s = __shfl_down(v, 1, kWave);
+  if (lane == kWave - 1) s = 0.f;
+#pragma unroll
+  for (int d = 1; d < kWave; d <<= 1) {
+    const float t = __shfl_down(s, d, kWave);
+    if (lane + d < kWave) s += t;
+  }
+  return s;
+}
+
+template <bool K512, class Src, class Acc>
+__device__ __forceinline__ void ray_occupancy_body(
+    const float* __restrict__ sigma, const Src& src, float* __restrict__ hit, float* __restrict__ free_, int R,
+    VolDims v, float step, int ncopies, int K, Acc& acc_hit, Acc& acc_free) {
+  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
+  if (r >= R) return;
+  const int lane = threadIdx.x % kWave;
+  const Ray ray = load_ray(src, r, v);
+  if (ray.f < 0) return;
+  const size_t slice = (size_t)ray.f * v.Z * v.Y * v.X;
+  Waypoints<K512, false> w{sigma + slice, ray, v, step, lane, K};
+  float m = kNegInf;
+  w.first([&](int, float z, float) { m = fmaxf(m, z); });
+  m = wave_max(m);
+  if (m == kNegInf) return;                              // no live waypoint; the same in every lane
+  float se = 0.f;
+  w.second([&](int, float z, float) { if (z != kNegInf) se += expf(z - m); });
+  se = wave_sum(se);
+  const size_t copy = scatter_copy_of_block(ncopies) * v.F * v.Z * v.Y * v.X + slice;
+  float* hvol = hit + copy;
+  float* fvol = free_ + copy;
+  const int cx = lane & 1;
+  float carry = 0.f;                                     // mass of the later passes
+  w.passes_down([&](int k, float z) {
+    const bool live = z != kNegInf;
+    const float p = live ? expf(z - m) / se : 0.f;
+    const float beyond = wave_suffix_excl(p, lane) + carry;
+    carry = __shfl(beyond + p, 0, kWave);
+    const float b = live ? beyond : 0.f;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {                        // 32 waypoints per half-pass, a lane pair per waypoint
+      const int from = h * (kWave / 2) + (lane >> 1);
+      const float pk = __shfl(p, from, kWave), bk = __shfl(b, from, kWave);
+      const bool lk = __shfl((int)live, from, kWave) != 0;
+      if (!lk) continue;
+      float sx, sy, sz;
+      waypoint(ray, k - lane + from, step, sx, sy, sz);
+      const Tri t = make_tri<false>(sx, sy, sz, v);
+      tri_scatter_x(hvol, t, pk, cx, acc_hit);
+      tri_scatter_x(fvol, t, bk, cx, acc_free);
+    }
+  });
+}
+
+// ---------------------------------------------------------------------------------------------
 // The kernels: one instantiation of a body each.  The ones without a suffix are the register form (K == kK);
 // ray_dist runs the streamed form for every K.
 // ---------------------------------------------------------------------------------------------
@@ -607,6 +694,17 @@ RAY_KERNEL ray_bwd_det_kernel(RAY_IN, const float* __restrict__ saved, const flo
   ray_bwd_body<K512, END_POINT, Coef>(sigma, origin, pts, tindex, saved, grad, grad_sigma, R, v, step, 1, K, acc);
   acc.flush();
 }
+// Occupancy evidence, every mode: Acc = AccAtomic is the default launch (private copies when ncopies > 1), AccMeasure /
+// AccFixed the deterministic mode's two passes (ncopies == 1).  `src`: ListedRays or CameraRays.
+template <bool K512, class Src, class Acc>
+RAY_KERNEL ray_occupancy_kernel(const float* __restrict__ sigma, Src src, float* __restrict__ hit,
+                                float* __restrict__ free_, int R, VolDims v, float step, int ncopies, int K,
+                                typename Acc::Param param_hit, typename Acc::Param param_free) {
+  Acc acc_hit(hit, param_hit), acc_free(free_, param_free);
+  ray_occupancy_body<K512>(sigma, src, hit, free_, R, v, step, ncopies, K, acc_hit, acc_free);
+  acc_hit.flush();
+  acc_free.flush();
+}
 #undef RAY_KERNEL
 #undef RAY_IN
 
@@ -656,6 +754,27 @@ int rm_bwd(const float* sigma, const float* origin, const float* pts, const floa
         hipLaunchKernelGGL(k, rm_grid(R), dim3(kThreads), 0, s, sigma, origin, pts, tindex, saved, grad, grad_sigma, R,
                            v, step, k512 ? kK : K, param);
       });
+}
+
+// The occupancy march from either ray source: the same shell with hit and free as its two outputs, at most 8 corners of
+// K waypoints per ray and output.
+template <class Acc> struct Policy { using type = Acc; };   // names a policy on the host (AccAtomic has no host object)
+template <class Src>
+int rm_occupancy(const float* sigma, const Src& src, float* hit, float* free_, int R, int K, VolDims v, float step,
+                 void* workspace, size_t workspace_bytes, hipStream_t s) {
+  const bool k512 = rm_k512(K);
+  const auto launch = [&](auto policy, float* h, float* f, int ncopies, auto p_hit, auto p_free) {
+    using Acc = typename decltype(policy)::type;
+    const auto k = k512 ? ray_occupancy_kernel<true, Src, Acc> : ray_occupancy_kernel<false, Src, Acc>;
+    hipLaunchKernelGGL(k, rm_grid(R), dim3(kThreads), 0, s, sigma, src, h, f, R, v, step, ncopies, k512 ? kK : K, p_hit,
+                       p_free);
+  };
+  return scatter_backward(
+      hit, free_, rm_cells(v), rm_cells(v), (uint64_t)R * (uint64_t)K * 8, R == 0, workspace, workspace_bytes, s,
+      [&](float* h, float* f, int ncopies) {
+        launch(Policy<det::AccAtomic>{}, h, f, ncopies, det::AccAtomic::Param{}, det::AccAtomic::Param{});
+      },
+      [&](auto tag, auto p_hit, auto p_free) { launch(Policy<decltype(tag)>{}, hit, free_, 1, p_hit, p_free); });
 }
 
 }  // namespace
@@ -805,6 +924,32 @@ int vidar_ray_stats_cam_f32(const float* sigma, const float* pix2vox, float* dis
   rm_launch(ray_stats_cam_kernel, ray_stats_cam_any_kernel, R, K, (hipStream_t)stream, sigma, cam, dist, stats, R, v,
             step);
   return vidar_last_error();
+}
+
+int vidar_ray_occupancy_workspace_bytes(int F, int Z, int Y, int X, int64_t* bytes) {
+  if (!bytes || F <= 0 || Z <= 0 || Y <= 0 || X <= 0) return VIDAR_ERR_BAD_ARG;
+  *bytes = (int64_t)scatter_backward_workspace_bytes(2 * rm_cells(VolDims{F, Z, Y, X}), 2);
+  return 0;
+}
+
+int vidar_ray_occupancy_f32(const float* sigma, const float* origin, const float* pts, const float* tindex, float* hit,
+                            float* free_, int F, int R, int Z, int Y, int X, int K, float step, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  VIDAR_ENTER();
+  if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
+  return rm_occupancy(sigma, ListedRays{origin, pts, tindex}, hit, free_, R, K, VolDims{F, Z, Y, X}, step, workspace,
+                      workspace_bytes, (hipStream_t)stream);
+}
+
+int vidar_ray_occupancy_cam_f32(const float* sigma, const float* pix2vox, float* hit, float* free_, int F, int C, int Hs,
+                                int Ws, float u0, float v0, float du, float dv, int Z, int Y, int X, int K, float step,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  VIDAR_ENTER();
+  int R = 0;
+  if (cam_bad(F, C, Hs, Ws, u0, v0, du, dv, R) || rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
+  const CameraRays cam{pix2vox, vidar_cam::CamGrid{C, Hs, Ws, u0, v0, du, dv}};
+  return rm_occupancy(sigma, cam, hit, free_, R, K, VolDims{F, Z, Y, X}, step, workspace, workspace_bytes,
+                      (hipStream_t)stream);
 }
 
 int vidar_cam_rays_f32(const float* pix2vox, float* origin, float* pts, int F, int C, int Hs, int Ws, float u0,

@@ -6,6 +6,7 @@
                  (utils/e2e_predictor_utils.py:188-224), NOT a pixel copy of what matplotlib renders
   depth_overlay  per-pixel depth laid over the camera frame
   confidence_mask / confidence_overlay  which rays pass a threshold on ray_ops.ray_stats' statistics; p_max as a picture
+  occupancy_grid / occupancy_bev  occupied / free / unseen voxels from ray_ops.ray_occupancy's evidence; as a picture
 torch + PIL only; nothing here launches a kernel of its own."""
 from __future__ import annotations
 
@@ -176,6 +177,45 @@ def confidence_overlay(p_max, frame_u8, alpha=160):
     grid, integer colour ramp and blend with the colour index clamp(floor(p * 255 + 0.5), 0, 255), so that p = 1 is the
     red end and p -> 0 the blue one."""
     return _ramp_overlay(p_max, frame_u8, alpha, lambda p: p)
+
+
+UNSEEN_COLOUR = (176, 196, 222)      # occupancy_bev: a column without a seen voxel
+
+
+def occupancy_grid(hit, free, min_evidence=0.5):
+    """hit, free [..., Z, H, W] of ray_ops.ray_occupancy (the softmax mass the marched rays put AT a voxel / BEYOND it)
+    -> (occ, evidence), both of that shape: evidence = hit + free; occ = hit / evidence where evidence >= min_evidence,
+    NaN elsewhere -- never seen, or occluded (every ray that came by had already spent its mass).
+    Evidence is counted in waypoints: 1.0 is one waypoint of one ray wholly attributed to the voxel and certainly not
+    occluded; half of one is the default floor.  min_evidence is a parameter of the answer, not a tolerance.  A NaN
+    evidence fails the floor (and 0 / 0 under a floor of 0 is NaN as well).  Pure torch, any device."""
+    evidence = hit + free
+    occ = torch.where(evidence >= float(min_evidence), hit / evidence, torch.full_like(evidence, float("nan")))
+    return occ, evidence
+
+
+def occupancy_bev(occ, size_px=None):
+    """occ [Z, H, W] of occupancy_grid (NaN = unseen) -> bird's-eye picture [size_px, size_px, 3] uint8 ([H, W, 3] for
+    size_px None): per column the max over Z among the seen voxels, as the integer grey
+    255 - clamp(floor(occ * 255 + 0.5), 0, 255) (free white, occupied black); UNSEEN_COLOUR where no voxel of the column
+    was seen.  bev_image's orientation: x to the right, y up (row 0 is y = H - 1).  A size_px other than H / W picks
+    the nearest cell: picture pixel (r, c) shows cell (y, x) = (((size_px - 1 - r) * H) // size_px, (c * W) // size_px)."""
+    if occ.dim() != 3:
+        raise ValueError("occ must be [Z, H, W]")
+    seen = ~torch.isnan(occ)
+    top = torch.where(seen, occ, torch.full_like(occ, -float("inf"))).max(0)[0].double()
+    any_seen = seen.any(0)
+    level = torch.floor(torch.where(any_seen, top, torch.zeros_like(top)) * 255.0 + 0.5).clamp(0, 255).long()
+    grey = (255 - level).to(torch.uint8)
+    unseen = torch.tensor(UNSEEN_COLOUR, dtype=torch.uint8, device=occ.device)
+    img = torch.where(any_seen[..., None], grey[..., None].expand(-1, -1, 3), unseen.expand(*grey.shape, 3))
+    H, W = grey.shape
+    rows, cols = (H, W) if size_px is None else (int(size_px), int(size_px))
+    if rows < 1:
+        raise ValueError("size_px must be >= 1")
+    ys = ((rows - 1 - torch.arange(rows, device=occ.device)) * H) // rows
+    xs = (torch.arange(cols, device=occ.device) * W) // cols
+    return img[ys][:, xs].contiguous()
 
 
 def save_png(img_u8, path):

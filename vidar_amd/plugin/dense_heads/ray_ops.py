@@ -6,6 +6,7 @@ kernels, every other value the streamed ones."""
 from __future__ import annotations
 
 import contextlib
+import ctypes
 
 import torch
 from torch.autograd import Function
@@ -224,6 +225,46 @@ def ray_stats_cam(sigma, pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0, step=1.0, 
     check(lib().vidar_ray_stats_cam_f32(ptr(sigma), ptr(pix2vox), ptr(dist), ptr(stats), *geom, Z, Y, X, int(K), step,
                                         stream_of(sigma)), "ray_stats_cam")
     return dist, stats
+
+
+def occupancy_workspace_bytes(F_, Z, Y, X):
+    """bytes of caller-owned scratch for ray_occupancy / ray_occupancy_cam under the library's current mode"""
+    nbytes = ctypes.c_int64(0)
+    check(lib().vidar_ray_occupancy_workspace_bytes(F_, Z, Y, X, ctypes.addressof(nbytes)), "ray_occupancy")
+    return nbytes.value
+
+
+def ray_occupancy(sigma, origin, pts, tindex, step=1.0, K=K_SAMPLES):
+    """occupancy evidence of the rays ray_argmax marches -> (hit, free), both [F,Z,Y,X] fp32, no grad: the softmax of
+    every ray's live waypoints splatted through the trilinear weights its logits were read with -- hit takes p_k (the
+    return lies at k), free takes b_k = the mass beyond k (the ray passed k); include/vidar_hip.h:
+    vidar_ray_occupancy_f32.  Under the deterministic mode both volumes are accumulated in fixed point."""
+    sigma, origin, pts, tindex = _f(sigma.detach()), _f(origin), _f(pts), _f(tindex)
+    F_, R, Z, Y, X = _dims(sigma, pts)
+    hit = torch.empty_like(sigma); free = torch.empty_like(sigma)
+    deterministic.sync()
+    ws, wsp, wsn = workspace(occupancy_workspace_bytes, F_, Z, Y, X, like=sigma)
+    check(lib().vidar_ray_occupancy_f32(ptr(sigma), ptr(origin), ptr(pts), ptr(tindex), ptr(hit), ptr(free),
+                                        F_, R, Z, Y, X, int(K), step, wsp, wsn, stream_of(sigma)), "ray_occupancy")
+    return hit, free
+
+
+def ray_occupancy_cam(sigma, pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0, step=1.0, K=K_SAMPLES):
+    """ray_occupancy on the rays ray_argmax_cam marches (one per pixel of the hw grid, never stored) -> (hit, free)
+    [F,Z,Y,X], no grad."""
+    sigma, pix2vox = _f(sigma.detach()), _f(pix2vox)
+    geom = _cam_args(pix2vox, hw, u0, v0, du, dv)
+    F_, Z, Y, X = sigma.shape
+    if geom[0] != F_:
+        raise ValueError(f"pix2vox holds {geom[0]} frames, sigma {F_}")
+    if pix2vox.device != sigma.device:
+        raise RuntimeError(f"pix2vox is on {pix2vox.device}, sigma on {sigma.device}")
+    hit = torch.empty_like(sigma); free = torch.empty_like(sigma)
+    deterministic.sync()
+    ws, wsp, wsn = workspace(occupancy_workspace_bytes, F_, Z, Y, X, like=sigma)
+    check(lib().vidar_ray_occupancy_cam_f32(ptr(sigma), ptr(pix2vox), ptr(hit), ptr(free), *geom, Z, Y, X, int(K), step,
+                                            wsp, wsn, stream_of(sigma)), "ray_occupancy_cam")
+    return hit, free
 
 
 def cam_rays(pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0):

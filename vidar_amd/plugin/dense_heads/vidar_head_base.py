@@ -26,6 +26,7 @@ from ..utils import e2e_predictor_utils
 from . import ray_ops
 
 _STATS_KEY = "ray_stats"      # entry of a pred_dict: decode with ray_ops.ray_stats and return "pred_stats" as well
+_OCC_KEY = "ray_occupancy"    # entry of a pred_dict: march the decode's rays with ray_ops.ray_occupancy, return its grids
 
 
 def _metre_stats(stats, scale):
@@ -273,7 +274,9 @@ class ViDARHeadBase(ViDARHeadTemplate):
         """arg-max decode (:663-752) -> dict(pred_pcds, gt_pcds, origin); as_rays: the dict of get_rendered_rays
         instead (the device metrics' input: nothing is selected on the host).  A true pred_dict["ray_stats"] (set by
         render_rays, never by the detector's evaluation) decodes with ray_ops.ray_stats -- the same distances -- and adds
-        pred_stats: list[bs] of list[frames] of [n, 4], row for row with pred_pcds, mean and rms in metres."""
+        pred_stats: list[bs] of list[frames] of [n, 4], row for row with pred_pcds, mean and rms in metres.
+        A true pred_dict["ray_occupancy"] (set by render_occupancy) hands the very rays of the decode to
+        ray_ops.ray_occupancy instead and returns [bs, F, 2, Z, H, W], hit and free."""
         bev_preds = pred_dict["next_bev_preds"].float()
         valid_frames = pred_dict["valid_frames"]
         F_, inter_num, bs, token_num, Z = bev_preds.shape
@@ -281,6 +284,10 @@ class ViDARHeadBase(ViDARHeadTemplate):
         origin_grids, origin_pts, gt_grids, gt_xyz, tindex = self._process_gt_points(
             bev_preds, gt_points, batched_origin_points, valid_frames, start_idx, F_, H, W, tgt_pc_range)
         last = bev_preds[:, -1:]
+        if pred_dict.get(_OCC_KEY):
+            return torch.stack([torch.stack(ray_ops.ray_occupancy(
+                self._volumes(last, b, Z, H, W), origin_grids[b], torch.nan_to_num(gt_grids[b], nan=-1.0e6), tindex[b],
+                self.ray_grid_step, self.ray_grid_num), 1) for b in range(bs)])
         # render_rays(return_stats=True) asks for the confidence through the dict every head hands on
         decode = ray_ops.ray_stats if pred_dict.get(_STATS_KEY) else ray_ops.ray_argmax
         pred, gt, stats = [], [], []
@@ -327,6 +334,21 @@ class ViDARHeadBase(ViDARHeadTemplate):
         rigid-rig assumption of vidar_amd.forecast.pix2vox.
         return_stats: march with ray_ops.ray_stats_cam instead (the same depth bits) -> (depth, stats [bs, F, C, Hs, Ws, 4]):
         (p_max, mean, rms, entropy) of the softmax along each ray, mean and rms in metres, zeros where it meets nothing."""
+        scale = (tgt_pc_range[3] - tgt_pc_range[0]) / tgt_bev_w
+        decode = ray_ops.ray_stats_cam if return_stats else ray_ops.ray_argmax_cam
+        out, stats = [], []
+        for args, kw in self._camera_marches(pred_dict, img_metas, tgt_bev_h, tgt_bev_w, tgt_pc_range, cameras, stride):
+            d = decode(*args, **kw)
+            if return_stats:
+                d, s = d
+                stats.append(s)
+            out.append(d * scale)
+        if return_stats:
+            return torch.stack(out), _metre_stats(torch.stack(stats), scale)
+        return torch.stack(out)
+
+    def _camera_marches(self, pred_dict, img_metas, tgt_bev_h, tgt_bev_w, tgt_pc_range, cameras, stride):
+        """per sample, the arguments of a ray_ops.*_cam call on render_cameras' rays: ((sigma, pix2vox, hw), keywords)"""
         from ...forecast import pix2vox
         stride = int(stride)
         if stride < 1:
@@ -335,9 +357,6 @@ class ViDARHeadBase(ViDARHeadTemplate):
         F_, inter_num, bs, token_num, Z = bev_preds.shape
         last = bev_preds[:, -1:]
         align = self.frame_alignment(pred_dict["valid_frames"], img_metas)
-        scale = (tgt_pc_range[3] - tgt_pc_range[0]) / tgt_bev_w
-        decode = ray_ops.ray_stats_cam if return_stats else ray_ops.ray_argmax_cam
-        out, stats = [], []
         for b in range(bs):
             meta = img_metas[b]
             cams = list(range(len(meta["lidar2img"]))) if cameras is None else [int(c) for c in cameras]
@@ -346,16 +365,10 @@ class ViDARHeadBase(ViDARHeadTemplate):
                 raise ValueError(f"the cameras' images must share one size, got {sorted(sizes)}")
             H, W = sizes.pop()
             m = pix2vox([meta["lidar2img"][c] for c in cams], tgt_pc_range, tgt_bev_h, tgt_bev_w, Z, align[b])
-            d = decode(self._volumes(last, b, Z, tgt_bev_h, tgt_bev_w), m.to(bev_preds.device),
-                       (-(-H // stride), -(-W // stride)), u0=stride / 2.0, v0=stride / 2.0,
-                       du=float(stride), dv=float(stride), step=self.ray_grid_step, K=self.ray_grid_num)
-            if return_stats:
-                d, s = d
-                stats.append(s)
-            out.append(d * scale)
-        if return_stats:
-            return torch.stack(out), _metre_stats(torch.stack(stats), scale)
-        return torch.stack(out)
+            yield ((self._volumes(last, b, Z, tgt_bev_h, tgt_bev_w), m.to(bev_preds.device),
+                    (-(-H // stride), -(-W // stride))),
+                   dict(u0=stride / 2.0, v0=stride / 2.0, du=float(stride), dv=float(stride), step=self.ray_grid_step,
+                        K=self.ray_grid_num))
 
     @torch.no_grad()
     def render_rays(self, pred_dict, directions=None, end_points=None, *, tgt_bev_h, tgt_bev_w, tgt_pc_range,
@@ -371,6 +384,16 @@ class ViDARHeadBase(ViDARHeadTemplate):
         return_stats: decode with ray_ops.ray_stats instead (the same points) -> (points, stats): list[bs] of list[frames]
         of [n, 4], row for row the points' (p_max, mean, rms, entropy), mean and rms in metres; a ray without a live
         waypoint has four zeros."""
+        end_points = self._listed_end_points(pred_dict, directions, end_points)
+        if return_stats:
+            pred_dict = dict(pred_dict, **{_STATS_KEY: True})
+        out = self.get_point_cloud_prediction(pred_dict, end_points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range,
+                                              img_metas=img_metas, batched_origin_points=batched_origin_points)
+        return (out["pred_pcds"], out["pred_stats"]) if return_stats else out["pred_pcds"]
+
+    def _listed_end_points(self, pred_dict, directions, end_points):
+        """render_rays' rays in the layout of gt_points: the end points as they are, or the points 1 m out along
+        `directions` in every frame"""
         if (directions is None) == (end_points is None):
             raise ValueError("give either directions or end_points")
         if end_points is None:
@@ -379,8 +402,31 @@ class ViDARHeadBase(ViDARHeadTemplate):
             cols = [torch.cat([d, d.new_full((d.shape[0], 1), lab)], 1)
                     for lab in self._ray_frame_labels(pred_dict["valid_frames"])]
             end_points = [torch.cat(cols, 0)] * bs
-        if return_stats:
-            pred_dict = dict(pred_dict, **{_STATS_KEY: True})
-        out = self.get_point_cloud_prediction(pred_dict, end_points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range,
-                                              img_metas=img_metas, batched_origin_points=batched_origin_points)
-        return (out["pred_pcds"], out["pred_stats"]) if return_stats else out["pred_pcds"]
+        return end_points
+
+    @torch.no_grad()
+    def render_occupancy(self, pred_dict, directions=None, end_points=None, *, cameras=None, stride=4, tgt_bev_h,
+                         tgt_bev_w, tgt_pc_range, img_metas=None, start_idx=0, batched_origin_points=None):
+        """Occupancy evidence of the decoded volumes -> [bs, F, 2, Z, H, W] fp32, hit and free (ray_ops.ray_occupancy):
+        how much softmax mass the marched rays put AT each voxel and how much BEYOND it (the ray passed through).
+          directions / end_points: the listed rays, exactly those render_rays would hand to ray_argmax (the same origin,
+              voxel mapping and nan_to_num); every marched ray contributes, whatever eval_within_grid later selects;
+          cameras: camera indices or "all" -> the rays of render_cameras at `stride` are added (ray_ops.ray_occupancy_cam).
+        At least one source; the two sources' grids are summed in torch.  vidar_amd.forecast.occupancy_grid turns the
+        pair into an occupied / free / unseen answer."""
+        listed = directions is not None or end_points is not None
+        if not listed and cameras is None:
+            raise ValueError("give directions, end_points or cameras")
+        total = None
+        if listed:
+            end_points = self._listed_end_points(pred_dict, directions, end_points)
+            total = self.get_point_cloud_prediction(
+                dict(pred_dict, **{_OCC_KEY: True}), end_points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range,
+                img_metas=img_metas, batched_origin_points=batched_origin_points)
+        if cameras is not None:
+            cams = None if isinstance(cameras, str) and cameras == "all" else cameras
+            cam = torch.stack([torch.stack(ray_ops.ray_occupancy_cam(*args, **kw), 1) for args, kw in
+                               self._camera_marches(pred_dict, img_metas, tgt_bev_h, tgt_bev_w, tgt_pc_range, cams,
+                                                    stride)])
+            total = cam if total is None else total + cam
+        return total

@@ -342,7 +342,7 @@ class ViDAR(nn.Module):
     # ---- forecast without ground truth ---------------------------------------------------------------
     @torch.no_grad()
     def forecast(self, img=None, img_metas=None, rays=None, cameras=None, stride=4, img_feats=None, stats=False,
-                 min_prob=None, max_rms=None):
+                 min_prob=None, max_rms=None, occupancy=False, min_evidence=0.5):
         """What the model expects to be seen, with no future sweep to take rays from: the no-grad history, future decoder
         and forward_head of forward_test, then
           rays [R, 3] unit directions (vidar_amd.forecast.lidar_pattern) -> "sweep": list[bs] of list[frames] of [n, 3]
@@ -357,7 +357,13 @@ class ViDAR(nn.Module):
           min_prob / max_rms (metres): a ray whose p_max < min_prob or whose rms > max_rms is dropped from the sweep
               ("sweep_index" names the rows of `rays` that are left) and its pixel's depth becomes 0, "nothing met"
               (vidar_amd.forecast.confidence_mask).  A threshold computes the statistics and returns them as stats=True does.
-        Without the three the decode, its launches and the result are those of the plain arg-max."""
+        Without the three the decode, its launches and the result are those of the plain arg-max.
+          occupancy=True | "sweep" | "cameras" | "both" adds the per-voxel answer (future_pred_head.render_occupancy on the
+              rays of `rays`, of `cameras` at `stride`, or both; True means "sweep"): "evidence" [bs, F, 2, Z, H, W], the
+              softmax mass the marched rays put at each voxel (hit) and beyond it (free), and "occupancy" [bs, F, Z, H, W]
+              = hit / (hit + free) where hit + free >= min_evidence, NaN (never seen, or occluded) elsewhere
+              (vidar_amd.forecast.occupancy_grid).  Without it nothing more is launched and every other output keeps its
+              bits."""
         if img_metas is None or (img is None and img_feats is None):
             raise ValueError("forecast needs img_metas and img (or img_feats)")
         from ...forecast import confidence_mask
@@ -391,6 +397,21 @@ class ViDAR(nn.Module):
                 depth = torch.where(confidence_mask(out["depth_stats"], min_prob, max_rms), depth,
                                     torch.zeros_like(depth))
             out["depth"] = depth
+        if occupancy:
+            from ...forecast import occupancy_grid
+            source = "sweep" if occupancy is True else occupancy
+            if source not in ("sweep", "cameras", "both"):
+                raise ValueError('occupancy must be False, True, "sweep", "cameras" or "both"')
+            if source != "cameras" and rays is None:
+                raise ValueError(f"occupancy={source!r} needs rays")
+            if source != "sweep" and cameras is None:
+                raise ValueError(f"occupancy={source!r} needs cameras")
+            dev = pred_dict["next_bev_preds"].device
+            evidence = self.future_pred_head.render_occupancy(
+                pred_dict, directions=None if source == "cameras" else rays.to(dev),
+                cameras=None if source == "sweep" else cameras, stride=stride, img_metas=cur_metas, **geom)
+            out["evidence"] = evidence
+            out["occupancy"] = occupancy_grid(evidence[:, :, 0], evidence[:, :, 1], min_evidence)[0]
         return out
 
     def _save_prediction(self, pred_pcd, img_meta, frame_idx):
