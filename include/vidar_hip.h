@@ -487,6 +487,52 @@ int vidar_ray_occupancy_cam_f32(const float* sigma, const float* pix2vox, float*
                                 int Z, int Y, int X, int K, float step,
                                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* Measured evidence of a sweep (csrc/ray_march.hip, sweep_evidence_body; per-ray weight in csrc/occ_score_math.h): the
+ * measured side of the inverse sensor model above, for rays whose end point is a measured return.  The rays are those of
+ * vidar_ray_occupancy_f32 -- origin [F,3], pts [R,3], tindex [R], voxel units, the same skip rule, the same waypoints
+ * s_k = o + rhat (k + 0.5) step, k < K, the same trilinear weights w_kc with corners outside the volume dropped -- and no
+ * volume is read.  With L = |p - o| in fp32, a ray that is not skipped and has a finite L > 0 adds
+ *   free[f, corner c of s_k] += a_k * w_kc     a_k = clamp((L - (k + 0.5) step) / step, 0, 1)
+ *   hit [f, corner c of p  ] += w_pc           the trilinear weights of the END POINT itself
+ * a_k is 1 well before the return, 0 from the return on and a ramp in between, so both grids are continuous in L and in
+ * the waypoints; waypoints with a_k == 0 are not marched.  The return is splatted where it was measured, for every
+ * marched ray, also when it lies beyond the marched range K * step.  Units are the predicted evidence's: free in
+ * waypoints, hit in returns.  hit, free [F,Z,Y,X] f32 are zeroed by the call; all rays skipped, or R == 0, leaves exact
+ * zeros; a ray with L == 0 or a non-finite L adds nothing.
+ * The adds, the workspace (vidar_ray_occupancy_workspace_bytes) and the VIDAR_ERR_BAD_ARG cases are those of
+ * vidar_ray_occupancy_f32; the deterministic mode's fixed point is sized for R * (K + 1) * 8 contributions. */
+int vidar_sweep_evidence_f32(const float* origin, const float* pts, const float* tindex, float* hit, float* free_,
+                             int F, int R, int Z, int Y, int X, int K, float step,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Occupancy score (csrc/occ_score.hip, per-voxel decisions in csrc/occ_score_math.h): a predicted evidence grid held
+ * against a measured one, for S segments -- (sample, frame) pairs -- at once.
+ *   pred, meas [S,2,V] f32 on the device: the hit plane, then the free plane, of every segment ([bs,F,2,Z,H,W] as it is);
+ *   thresholds: T floats on the HOST, 1 <= T <= 8 (duplicates allowed); bins B, 0 <= B <= 16.
+ * Per voxel, in fp32, every operation rounded on its own:
+ *   ev_p = hit_p + free_p     ev_m = hit_m + free_m     o_p = hit_p / ev_p
+ *   both = ev_p >= min_pred_evidence && ev_m >= min_meas_evidence
+ *   y    = hit_m >= min_hits      a return was measured in this cell, whatever the free evidence says
+ * A voxel with a non-finite value in any of its four planes takes part in no column.
+ *   table [S, 5 + 3T + 2B] f64 (passed as void*, 8-byte aligned), written completely:
+ *     [0] n_pred (ev_p reaches its floor)   [1] n_meas   [2] n_both   [3] n_occ (both and y)
+ *     [4] brier = sum over both of (o_p - y)^2, the terms and the sum in fp64
+ *     [5 + 3j ..] tp_j, fp_j, fn_j over both, with yhat = o_p >= thresholds[j]
+ *     [5 + 3T + 2b ..] cnt_b, pos_b (those with y) over both, with b = min(int(o_p * B), B - 1)
+ * Every column but brier is a count and exact; brier is summed in a fixed order; no atomics: equal inputs, equal bits.
+ * (With min_pred_evidence <= 0 a voxel without predicted evidence has o_p = 0 / 0: it fails every threshold, falls
+ * into bin 0 and makes brier NaN.)
+ * workspace: vidar_occ_score_workspace_bytes(S,V,T,B,&bytes) bytes of device scratch, 8-byte aligned: the per-tile rows
+ * a second launch sums in a fixed order.  S == 0 or V == 0 return 0 without a launch.  VIDAR_ERR_BAD_ARG before any HIP
+ * call: negative sizes, S > 65535, T or B out of range, a NaN threshold or floor, a missing pointer, a short or
+ * misaligned workspace.
+ * ------------------------------------------------------------------------- */
+int vidar_occ_score_workspace_bytes(int S, int V, int T, int B, int64_t* bytes);
+int vidar_occ_score_f32(const float* pred, const float* meas, const float* thresholds, void* table,
+                        int S, int V, int T, int B, float min_pred_evidence, float min_meas_evidence, float min_hits,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Modulated deformable convolution v2 (backbone, "next" row SURVEY 8f-1).  Replaces the sampling
  * kernels of mmcv.ops.ModulatedDeformConv2dPack (mmcv-full 1.4.0, third party); the convolution

@@ -1152,6 +1152,139 @@ def bench_ray_occupancy(which):
                   f"{r['live_waypoints']} | {r['atomic_adds']} | {r['giga_adds_per_s']} |\n" for r in rows))
 
 
+def _occ_table_torch(pred, meas, thresholds, bins, min_pred=0.5, min_meas=0.5, min_hits=0.125):
+    """forecast.occupancy_score's table as a torch program on the device (fp32 decisions, fp64 sums)"""
+    hp, fp, hm, fm = pred[:, 0].flatten(1), pred[:, 1].flatten(1), meas[:, 0].flatten(1), meas[:, 1].flatten(1)
+    finite = torch.isfinite(hp) & torch.isfinite(fp) & torch.isfinite(hm) & torch.isfinite(fm)
+    ev_p, ev_m = hp + fp, hm + fm
+    o_p = hp / ev_p
+    ok_p, ok_m, y = finite & (ev_p >= min_pred), finite & (ev_m >= min_meas), hm >= min_hits
+    both = ok_p & ok_m
+    n = lambda m: m.sum(1, dtype=torch.float64)
+    term = (o_p.double() - y.double()) ** 2
+    cols = [n(ok_p), n(ok_m), n(both), n(both & y), torch.where(both, term, torch.zeros_like(term)).sum(1)]
+    for t in thresholds:
+        yhat = o_p >= t
+        cols += [n(both & yhat & y), n(both & yhat & ~y), n(both & ~yhat & y)]
+    b = (torch.where(both, o_p, torch.zeros_like(o_p)) * bins).long().clamp(max=bins - 1)
+    for k in range(bins):
+        cols += [n(both & (b == k)), n(both & (b == k) & y)]
+    return torch.stack(cols, 1)
+
+
+def bench_occ_score(which):
+    """The occupancy score on a 16 x 200 x 200 volume, step 1.
+    sweep_evidence (vidar_sweep_evidence_f32) next to ray_occupancy (vidar_ray_occupancy_f32) on the 34 560 rays of
+    vidar_amd.forecast.lidar_pattern() from the volume's centre, end points 4 - 120 voxels out drawn from a seed; K = 512
+    and 1026, default and deterministic mode, same process, the two ops alternating.
+    occupancy_score (vidar_occ_score_f32, 2 thresholds, 10 bins) on those two grids for 1 and 7 segments, next to a torch
+    program on the device that builds the same table and to a device copy of the same 16 B per voxel.
+    HIP events, three repeats of 2 warm-up + 20 timed calls; spread = (max - min) / median.
+    Writes profiles/kbench_occ_score.md."""
+    from vidar_amd import deterministic
+    from vidar_amd import forecast as FC
+    from vidar_amd.plugin.dense_heads.ray_ops import ray_occupancy, sweep_evidence
+    from vidar_amd._lib import lib, ptr, stream_of
+    import ctypes
+    dev = torch.device("cuda", 0)
+    Z, Y, X = 16, 200, 200
+    gen = torch.Generator().manual_seed(0)
+    sigma = torch.randn(1, Z, Y, X, generator=gen).to(dev)
+    o = torch.tensor([[X / 2.0, Y / 2.0, Z / 4.0]], device=dev)
+    d = FC.lidar_pattern()
+    length = 4.0 + 116.0 * torch.rand(d.shape[0], generator=gen)
+    p = o + (d * length.view(-1, 1)).to(dev)
+    ti = torch.zeros(p.shape[0], device=dev)
+    med = lambda v: float(np.median(v))
+    spread = lambda v: (max(v) - min(v)) / med(v)
+    rows, score_rows = [], []
+    grids = {}
+    for K in (512, 1026):
+        for det in (False, True):
+            with deterministic.use(det):
+                occ = lambda: ray_occupancy(sigma, o, p, ti, 1.0, K)
+                swp = lambda: sweep_evidence(o, p, ti, sigma.shape, 1.0, K)
+                grids[K] = (torch.stack(occ(), 1), torch.stack(swp(), 1))
+                ts = {"sweep": [], "occupancy": []}
+                for _ in range(3):
+                    ts["sweep"].append(timeit(swp, warm=2, it=20)); ts["occupancy"].append(timeit(occ, warm=2, it=20))
+            marched = int(torch.clamp(torch.ceil(length - 0.5), max=K).sum())
+            row = dict(R=p.shape[0], K=K, mode="deterministic" if det else "default",
+                       sweep_evidence_ms=[round(v, 3) for v in ts["sweep"]], sweep_evidence_median_ms=round(med(ts["sweep"]), 3),
+                       sweep_evidence_spread=round(spread(ts["sweep"]), 4),
+                       ray_occupancy_median_ms=round(med(ts["occupancy"]), 3),
+                       ray_occupancy_spread=round(spread(ts["occupancy"]), 4),
+                       ratio=round(med(ts["sweep"]) / med(ts["occupancy"]), 3), waypoints_with_a_weight=marched,
+                       hit_sum=round(float(grids[K][1][:, 0].sum()), 2), free_max=round(float(grids[K][1][:, 1].max()), 2))
+            rows.append(row)
+            report("sweep_evidence", med(ts["sweep"]), **row)
+    th, bins = (0.25, 0.5), 10
+    for S in (1, 7):
+        pred = grids[512][0].expand(S, 2, Z, Y, X).contiguous()
+        meas = grids[512][1].expand(S, 2, Z, Y, X).contiguous()
+        buf = torch.empty(2, *pred.shape, device=dev)
+        kernel = lambda: FC.occupancy_score(pred, meas, thresholds=th, bins=bins)
+        eager = lambda: _occ_table_torch(pred, meas, th, bins)
+        copy = lambda: (buf[0].copy_(pred), buf[1].copy_(meas))
+        # the entry point alone, on a table and a workspace allocated once: what the wrapper's allocations and Python cost
+        nws = ctypes.c_int64(0)
+        lib().vidar_occ_score_workspace_bytes(S, Z * Y * X, len(th), bins, ctypes.addressof(nws))
+        table, ws = torch.empty(S, 5 + 3 * len(th) + 2 * bins, dtype=torch.float64, device=dev), torch.empty(nws.value, dtype=torch.uint8, device=dev)
+        th_host, stream = (ctypes.c_float * len(th))(*th), stream_of(pred)
+        entry = lambda: lib().vidar_occ_score_f32(ptr(pred), ptr(meas), ctypes.addressof(th_host), ptr(table), S, Z * Y * X,
+                                                  len(th), bins, 0.5, 0.5, 0.125, ptr(ws), nws.value, stream)
+        got, want = kernel(), eager()
+        same = bool(torch.equal(got[:, [c for c in range(got.shape[1]) if c != 4]],
+                                want[:, [c for c in range(got.shape[1]) if c != 4]]))
+        assert entry() == 0 and torch.equal(table, got)
+        ts = {"kernel": [], "entry": [], "torch": [], "copy": []}
+        for _ in range(3):
+            for name, fn in (("kernel", kernel), ("entry", entry), ("torch", eager), ("copy", copy)):
+                ts[name].append(timeit(fn, warm=2, it=20))
+        nbytes = 16 * S * Z * Y * X
+        row = dict(S=S, V=Z * Y * X, T=len(th), B=bins, read_MB=round(nbytes / 1e6, 2),
+                   kernel_ms=[round(v, 4) for v in ts["kernel"]], kernel_median_ms=round(med(ts["kernel"]), 4),
+                   kernel_spread=round(spread(ts["kernel"]), 4), entry_median_ms=round(med(ts["entry"]), 4),
+                   entry_spread=round(spread(ts["entry"]), 4), entry_GBps=round(nbytes / med(ts["entry"]) / 1e6, 1),
+                   torch_median_ms=round(med(ts["torch"]), 3), torch_spread=round(spread(ts["torch"]), 4),
+                   copy_median_ms=round(med(ts["copy"]), 4), copy_spread=round(spread(ts["copy"]), 4),
+                   kernel_over_copy=round(med(ts["kernel"]) / med(ts["copy"]), 2),
+                   entry_over_copy=round(med(ts["entry"]) / med(ts["copy"]), 2),
+                   torch_over_kernel=round(med(ts["torch"]) / med(ts["kernel"]), 1), counts_equal_torch=same,
+                   n_both=float(got[0, 2]), brier=round(float(got[0, 4] / got[0, 2]), 4))
+        score_rows.append(row)
+        report("occ_score", med(ts["entry"]), nbytes, **row)
+    out = os.environ.get("VIDAR_KBENCH_OUT")
+    path = Path(out) if out else ROOT / "profiles" / "kbench_occ_score.md"
+    path.write_text(
+        "# Occupancy score on an MI355X: `python tools/kbench.py occ_score`\n\n"
+        f"Volume {Z} x {Y} x {X}, step 1, the {p.shape[0]} rays of `vidar_amd.forecast.lidar_pattern()` from the volume's centre,\n"
+        "end points 4 - 120 voxels out (seeded).  `sweep_evidence` (`vidar_sweep_evidence_f32`, no volume read) next to\n"
+        "`ray_occupancy` (`vidar_ray_occupancy_f32`, random-normal logits) on the same rays, in the same process, the two ops\n"
+        "alternating; `default` adds with fp32 atomics into 8 private copies of both volumes, `deterministic` measures and\n"
+        "then adds in 64-bit fixed point.  `waypoints with a weight`: the waypoints sweep_evidence marches with a_k > 0\n"
+        "(ray_occupancy scatters every live waypoint of all K).  Then `occupancy_score` (`vidar_occ_score_f32`, 2 thresholds,\n"
+        "10 bins) on the K = 512 grids for 1 and 7 segments, next to a torch program on the device that builds the same table\n"
+        "(`tools/kbench.py _occ_table_torch`) and to a device-to-device copy of the same 16 B per voxel (which also WRITES\n"
+        "16 B per voxel).  `entry`: `vidar_occ_score_f32` called on a table and a workspace allocated once -- the two launches\n"
+        "without the wrapper's allocations.  HIP events, 3 repeats of 2 warm-up + 20 timed calls; spread = (max - min) / median.  Each call\n"
+        "allocates its outputs and its workspace.\n\n"
+        "```\n" + json.dumps({"device": torch.cuda.get_device_name(0)}) + "\n"
+        + "\n".join(json.dumps(dict(op="sweep_evidence", **r)) for r in rows) + "\n"
+        + "\n".join(json.dumps(dict(op="occ_score", **r)) for r in score_rows) + "\n```\n\n"
+        "| R | K | mode | sweep_evidence ms (median) | spread | ray_occupancy ms (median) | spread | sweep / occupancy | waypoints with a weight |\n"
+        "|---|---|---|---|---|---|---|---|---|\n"
+        + "".join(f"| {r['R']} | {r['K']} | {r['mode']} | {r['sweep_evidence_median_ms']} | {r['sweep_evidence_spread']} | "
+                  f"{r['ray_occupancy_median_ms']} | {r['ray_occupancy_spread']} | {r['ratio']} | "
+                  f"{r['waypoints_with_a_weight']} |\n" for r in rows)
+        + "\n| segments | voxels each | read MB | occupancy_score ms (median) | spread | entry ms (median) | spread | entry GB/s read | copy ms | occupancy_score / copy | entry / copy | torch ms | torch / occupancy_score | counts equal torch's |\n"
+        "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|\n"
+        + "".join(f"| {r['S']} | {r['V']} | {r['read_MB']} | {r['kernel_median_ms']} | {r['kernel_spread']} | {r['entry_median_ms']} | "
+                  f"{r['entry_spread']} | {r['entry_GBps']} | {r['copy_median_ms']} | {r['kernel_over_copy']} | "
+                  f"{r['entry_over_copy']} | {r['torch_median_ms']} | {r['torch_over_kernel']} | "
+                  f"{r['counts_equal_torch']} |\n" for r in score_rows))
+
+
 if __name__ == "__main__":
     import os
     if os.environ.get("VIDAR_MSDA_ITEM_ORDER") is not None:          # A/B of the gather kernels' item order (0 banded, 1 head-major)

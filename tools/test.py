@@ -8,7 +8,10 @@
 Every rank evaluates samples rank, rank+W, ... (synthetic generator, or with --ann-file the validation info pkl
 read by vidar_amd.data in test mode: full history required, key-frame cloud only, no augmentation), the
 per-sample `frame.k` dicts are gathered over the process group (RCCL) and rank 0 prints the
-reference's summary (chamfer distance, L1 and AbsRel ray errors per future frame).
+reference's summary (chamfer distance, L1 and AbsRel ray errors per future frame).  --occupancy-metrics
+[--occ-thresholds T ...] [--min-evidence E] also scores the occupancy forecast against the measured sweep of every frame
+(vidar_amd.forecast.occupancy_score): rank 0 prints IoU / precision / recall per threshold, coverage, Brier score and
+reliability per frame and writes them under "occupancy" in --out.
 
 A detection recipe (finetune/...) runs the BEVFormer detector in video mode instead: the frames of each synthetic sequence go
 through forward_test one by one (the previous frame's BEV carried along, reset at a scene change) and the decoded boxes of
@@ -67,7 +70,17 @@ def main(argv=None):
     ap.add_argument("--device-metrics", action="store_true",
                     help="score the forecast on the device: one chamfer call, one ray-error call and one host read per "
                          "batch instead of a dozen round trips per (sample, frame) (same figures; off by default)")
+    ap.add_argument("--occupancy-metrics", action="store_true",
+                    help="also score the occupancy forecast against the measured future sweep: IoU / precision / recall "
+                         "per threshold, coverage, Brier score and reliability per future frame (off by default)")
+    ap.add_argument("--occ-thresholds", type=float, nargs="+", metavar="T",
+                    help="with --occupancy-metrics: the thresholds on the predicted occupancy (1 to 8; default 0.25 0.5)")
+    ap.add_argument("--min-evidence", type=float, metavar="E",
+                    help="with --occupancy-metrics: floor on the predicted evidence of a scored voxel (default 0.5)")
     args = ap.parse_args(argv)
+    if args.occupancy_metrics:
+        from vidar_amd.plugin.utils import eval_utils
+        eval_utils.set_occupancy_metrics(True, thresholds=args.occ_thresholds, min_evidence=args.min_evidence)
     if args.device_metrics:
         from vidar_amd.plugin.utils import eval_utils
         eval_utils.set_device_metrics(True)
@@ -135,6 +148,10 @@ def main(argv=None):
     if rank == 0:
         summary = E.summarize(results)
         print(E.format_summary(summary), flush=True)
+        occupancy = E.occupancy_summary(summary)
+        if occupancy:
+            print(E.format_occupancy(occupancy), flush=True)
+            summary = dict(summary, occupancy=occupancy)
         if args.out:
             Path(args.out).parent.mkdir(parents=True, exist_ok=True)
             Path(args.out).write_text(json.dumps(summary, indent=1))

@@ -113,6 +113,9 @@ _ABI = {
     "vidar_ray_occupancy_workspace_bytes": "i 4i p",
     "vidar_ray_occupancy_f32": "i 6p 6i f p z p",
     "vidar_ray_occupancy_cam_f32": "i 4p 4i 4f 4i f p z p",
+    "vidar_sweep_evidence_f32": "i 5p 6i f p z p",
+    "vidar_occ_score_workspace_bytes": "i 4i p",
+    "vidar_occ_score_f32": "i 4p 4i 3f p z p",
     "vidar_gemm_f32": "i p l i p l i p l 4i 3l 2p i p 2l 3i 2p z p",
     "vidar_gemm_splits": "i 6i",
     "vidar_gemm_workspace_bytes": "z 6i",

@@ -13,6 +13,7 @@
 //                 (peak probability, mean length, spread, entropy; no counterpart in the reference)
 //   ray_occupancy / ray_occupancy_cam : the decode's softmax scattered back onto the voxels, mass at / beyond every
 //                 waypoint (hit / free evidence of an occupancy grid; no counterpart in the reference)
+//   sweep_evidence : the same evidence of a MEASURED sweep -- rays with known returns, no volume is read
 // The reference materialises ~8 arrays of [rays, 513] floats per call (waypoints, lengths, masks,
 // sampled logits, -inf masks, softmax); here one wave owns one ray, its 512 waypoints live in
 // registers (8 per lane) and only O(1) values per ray ever reach HBM.
@@ -47,6 +48,7 @@
 #include "scatter_copies.h"
 #include "det_scatter.h"
 #include "cam_ray.h"
+#include "occ_score_math.h"
 
 namespace {
 
@@ -581,6 +583,42 @@ __device__ __forceinline__ void ray_occupancy_body(
 }
 
 // ---------------------------------------------------------------------------------------------
+// Measured evidence of a sweep: the other side of ray_occupancy_body's inverse sensor model.  The rays are listed rays
+// whose end point p is a measured return; no volume is read.  With L = |p - o| (dist_to: the length aim divides by), a
+// ray that is not skipped and has a finite L > 0 adds
+//   free[f, corner c of s_k] += a_k * w_kc      a_k = beam_weight(L, k, step) (occ_score_math.h), k < K
+//   hit [f, corner c of p  ] += w_pc            the trilinear weights of the end point itself, whatever K * step is
+// on ray_occupancy_body's waypoints s_k and weights (make_tri<false>: corners outside the volume dropped).  a_k == 0 from
+// the return on: only beam_trips(L, step, K) waypoints are marched, in passes of 32 with a lane pair per waypoint; the
+// end point is lanes 0 and 1's.  One body for every K: nothing is sampled, so there is nothing to keep in registers.
+// ---------------------------------------------------------------------------------------------
+template <class Acc>
+__device__ __forceinline__ void sweep_evidence_body(const ListedRays& src, float* __restrict__ hit,
+                                                    float* __restrict__ free_, int R, VolDims v, float step, int ncopies,
+                                                    int K, Acc& acc_hit, Acc& acc_free) {
+  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
+  if (r >= R) return;
+  const int lane = threadIdx.x % kWave;
+  const Ray ray = load_ray(src, r, v);
+  if (ray.f < 0) return;
+  const float L = dist_to(ray, ray.px, ray.py, ray.pz);
+  if (!(L > 0.f) || !(L < __builtin_inff())) return;       // zero length, NaN or overflowing end point: no measurement
+  const size_t copy = scatter_copy_of_block(ncopies) * v.F * v.Z * v.Y * v.X + (size_t)ray.f * v.Z * v.Y * v.X;
+  float* hvol = hit + copy;
+  float* fvol = free_ + copy;
+  const int cx = lane & 1;
+  if (lane < 2) tri_scatter_x(hvol, make_tri<false>(ray.px, ray.py, ray.pz, v), 1.f, cx, acc_hit);
+  const int trips = vidar_occ::beam_trips(L, step, K);
+  for (int j = 0; j * (kWave / 2) < trips; ++j) {
+    const int k = (lane >> 1) + j * (kWave / 2);
+    if (k >= trips) break;                                 // only in the last pass
+    float sx, sy, sz;
+    waypoint(ray, k, step, sx, sy, sz);
+    tri_scatter_x(fvol, make_tri<false>(sx, sy, sz, v), vidar_occ::beam_weight(L, k, step), cx, acc_free);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // The kernels: one instantiation of a body each.  The ones without a suffix are the register form (K == kK);
 // ray_dist runs the streamed form for every K.
 // ---------------------------------------------------------------------------------------------
@@ -705,6 +743,16 @@ RAY_KERNEL ray_occupancy_kernel(const float* __restrict__ sigma, Src src, float*
   acc_hit.flush();
   acc_free.flush();
 }
+// Measured evidence, every mode, as ray_occupancy_kernel
+template <class Acc>
+RAY_KERNEL sweep_evidence_kernel(ListedRays src, float* __restrict__ hit, float* __restrict__ free_, int R, VolDims v,
+                                 float step, int ncopies, int K, typename Acc::Param param_hit,
+                                 typename Acc::Param param_free) {
+  Acc acc_hit(hit, param_hit), acc_free(free_, param_free);
+  sweep_evidence_body(src, hit, free_, R, v, step, ncopies, K, acc_hit, acc_free);
+  acc_hit.flush();
+  acc_free.flush();
+}
 #undef RAY_KERNEL
 #undef RAY_IN
 
@@ -771,6 +819,22 @@ int rm_occupancy(const float* sigma, const Src& src, float* hit, float* free_, i
   };
   return scatter_backward(
       hit, free_, rm_cells(v), rm_cells(v), (uint64_t)R * (uint64_t)K * 8, R == 0, workspace, workspace_bytes, s,
+      [&](float* h, float* f, int ncopies) {
+        launch(Policy<det::AccAtomic>{}, h, f, ncopies, det::AccAtomic::Param{}, det::AccAtomic::Param{});
+      },
+      [&](auto tag, auto p_hit, auto p_free) { launch(Policy<decltype(tag)>{}, hit, free_, 1, p_hit, p_free); });
+}
+
+// The measured evidence: the same shell; at most 8 corners of K waypoints and of the end point per ray and output.
+int rm_sweep_evidence(const ListedRays& src, float* hit, float* free_, int R, int K, VolDims v, float step,
+                      void* workspace, size_t workspace_bytes, hipStream_t s) {
+  const auto launch = [&](auto policy, float* h, float* f, int ncopies, auto p_hit, auto p_free) {
+    using Acc = typename decltype(policy)::type;
+    hipLaunchKernelGGL(sweep_evidence_kernel<Acc>, rm_grid(R), dim3(kThreads), 0, s, src, h, f, R, v, step, ncopies, K,
+                       p_hit, p_free);
+  };
+  return scatter_backward(
+      hit, free_, rm_cells(v), rm_cells(v), (uint64_t)R * ((uint64_t)K + 1) * 8, R == 0, workspace, workspace_bytes, s,
       [&](float* h, float* f, int ncopies) {
         launch(Policy<det::AccAtomic>{}, h, f, ncopies, det::AccAtomic::Param{}, det::AccAtomic::Param{});
       },
@@ -950,6 +1014,15 @@ int vidar_ray_occupancy_cam_f32(const float* sigma, const float* pix2vox, float*
   const CameraRays cam{pix2vox, vidar_cam::CamGrid{C, Hs, Ws, u0, v0, du, dv}};
   return rm_occupancy(sigma, cam, hit, free_, R, K, VolDims{F, Z, Y, X}, step, workspace, workspace_bytes,
                       (hipStream_t)stream);
+}
+
+int vidar_sweep_evidence_f32(const float* origin, const float* pts, const float* tindex, float* hit, float* free_, int F,
+                             int R, int Z, int Y, int X, int K, float step, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  VIDAR_ENTER();
+  if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
+  return rm_sweep_evidence(ListedRays{origin, pts, tindex}, hit, free_, R, K, VolDims{F, Z, Y, X}, step, workspace,
+                           workspace_bytes, (hipStream_t)stream);
 }
 
 int vidar_cam_rays_f32(const float* pix2vox, float* origin, float* pts, int F, int C, int Hs, int Ws, float u0,

@@ -31,6 +31,7 @@ _COVERAGE = {
     "ray_gumbel backward": (FIXED_POINT, "vidar_ray_gumbel_bwd_f32"),
     "ray_dist backward": (FIXED_POINT, "vidar_ray_dist_bwd_f32"),
     "ray_occupancy": (FIXED_POINT, "vidar_ray_occupancy{,_cam}_f32 (hit, free)"),
+    "sweep_evidence": (FIXED_POINT, "vidar_sweep_evidence_f32 (hit, free)"),
     "latent_render backward": (FIXED_POINT, "vidar_latent_render_{prob,gather,gather_grouped}_bwd_f32"),
     "knn1_d3 backward": (FIXED_POINT, "vidar_knn1_d3_bwd_ws (grad_p2)"),
     "dcn col2im": (FIXED_POINT, "vidar_dcn_col2im_f32 (grad_x; the plain scatter for every variant)"),

@@ -37,6 +37,43 @@ def summarize(results: Sequence[dict]) -> dict:
     return total
 
 
+def occupancy_summary(summary: dict) -> dict:
+    """summarize()'s per-frame means -> {frame.k: vidar_amd.forecast.occupancy_metrics} for the frames that carry the
+    `occ.*` entries of ViDAR.forward_test (eval_utils.set_occupancy_metrics).  summarize divided every count of a frame by
+    the same `count`, which keeps every ratio of counts: the result is the metric of the POOLED counts, not a mean of
+    per-sample metrics.  Thresholds and bins are read from the entries' names."""
+    from .forecast import OCC_FIXED_COLUMNS, occupancy_metrics
+    out = {}
+    for frame_k, res in summary.items():
+        if "occ.n_both" not in res:
+            continue
+        th = [k[len("occ.tp@"):] for k in res if k.startswith("occ.tp@")]
+        bins = sum(k.startswith("occ.cnt.") for k in res)
+        row = [res[f"occ.{c}"] for c in OCC_FIXED_COLUMNS]
+        for t in th:
+            row += [res[f"occ.tp@{t}"], res[f"occ.fp@{t}"], res[f"occ.fn@{t}"]]
+        for b in range(bins):
+            row += [res[f"occ.cnt.{b}"], res[f"occ.pos.{b}"]]
+        out[frame_k] = occupancy_metrics([row], [float(t) for t in th], bins)
+    return out
+
+
+def format_occupancy(occupancy: dict) -> str:
+    """occupancy_summary's result as the lines tools/test.py prints"""
+    lines = []
+    for frame_k, m in occupancy.items():
+        lines.append(f"==== {frame_k} occupancy: ====")
+        lines.append(f"voxels per sample: scored {m['n_both']:.6g} of {m['n_meas']:.6g} measured (coverage {m['coverage']:.4f}), "
+                     f"occupied {m['n_occ']:.6g}, brier {m['brier']:.4f}")
+        for j, t in enumerate(m["thresholds"]):
+            lines.append(f"occ >= {t:g}: iou {m['iou'][j]:.4f} precision {m['precision'][j]:.4f} recall {m['recall'][j]:.4f}")
+        rel = m["reliability"]
+        if rel["cnt"]:
+            lines.append("reliability (share of the bin's voxels with a return): "
+                         + " ".join(f"{f:.3f}" for f in rel["freq"]))
+    return "\n".join(lines)
+
+
 def format_summary(summary: dict) -> str:
     lines = []
     for frame_k, frame_res in summary.items():

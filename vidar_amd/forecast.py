@@ -7,7 +7,9 @@
   depth_overlay  per-pixel depth laid over the camera frame
   confidence_mask / confidence_overlay  which rays pass a threshold on ray_ops.ray_stats' statistics; p_max as a picture
   occupancy_grid / occupancy_bev  occupied / free / unseen voxels from ray_ops.ray_occupancy's evidence; as a picture
-torch + PIL only; nothing here launches a kernel of its own."""
+  occupancy_score / occupancy_metrics  the predicted evidence held against a measured sweep's (ray_ops.sweep_evidence):
+                 counts per (sample, frame) on the device (csrc/occ_score.hip), then IoU / precision / recall / calibration
+torch + PIL only; occupancy_score is the one function here that launches a kernel of its own."""
 from __future__ import annotations
 
 import math
@@ -192,6 +194,104 @@ def occupancy_grid(hit, free, min_evidence=0.5):
     evidence = hit + free
     occ = torch.where(evidence >= float(min_evidence), hit / evidence, torch.full_like(evidence, float("nan")))
     return occ, evidence
+
+
+OCC_FIXED_COLUMNS = ("n_pred", "n_meas", "n_both", "n_occ", "brier")
+OCC_THRESHOLDS, OCC_BINS = (0.25, 0.5), 10      # the defaults of occupancy_score and of what reads its table
+
+
+def _thresholds(thresholds):
+    t = [float(v) for v in (thresholds if hasattr(thresholds, "__iter__") else (thresholds,))]
+    if not 1 <= len(t) <= 8 or any(math.isnan(v) for v in t):
+        raise ValueError("occupancy thresholds: 1 to 8 numbers, none of them NaN")
+    return t
+
+
+def occupancy_columns(thresholds=OCC_THRESHOLDS, bins=OCC_BINS):
+    """names of the columns of occupancy_score's table, in order: n_pred, n_meas, n_both, n_occ, brier, then tp@t, fp@t,
+    fn@t per threshold t (printed with %g) and cnt.b, pos.b per reliability bin b"""
+    cols = list(OCC_FIXED_COLUMNS)
+    for t in _thresholds(thresholds):
+        cols += [f"tp@{t:g}", f"fp@{t:g}", f"fn@{t:g}"]
+    for b in range(int(bins)):
+        cols += [f"cnt.{b}", f"pos.{b}"]
+    return cols
+
+
+def occupancy_score(pred_evidence, meas_evidence, thresholds=OCC_THRESHOLDS, min_evidence=0.5, min_meas_evidence=0.5,
+                    min_hits=0.125, bins=OCC_BINS):
+    """Score a predicted occupancy evidence against a measured one, on the device, without a host read.
+    pred_evidence / meas_evidence [..., 2, Z, H, W] (or [S, 2, V]) fp32 device tensors of one shape: hit and free of
+    ViDARHeadBase.render_occupancy / ray_ops.ray_occupancy and of ViDARHeadBase.measured_occupancy / ray_ops.sweep_evidence.
+    Per voxel (fp32): ev = hit + free on both sides, o_p = hit_p / ev_p; the voxel is scored where
+    ev_p >= min_evidence and ev_m >= min_meas_evidence (both grids speak), and its label is y = hit_m >= min_hits -- a
+    return was measured in the cell; the cell that holds a lone return always receives at least 1/8 of it.
+    -> fp64 device table [..., 5 + 3 T + 2 bins] with the leading dimensions of the input and the columns of
+    occupancy_columns: exact counts, and brier = sum (o_p - y)^2 in a fixed order (include/vidar_hip.h:
+    vidar_occ_score_f32).  occupancy_metrics turns it into IoU / precision / recall / coverage / calibration.
+    There is no CPU path."""
+    import ctypes
+    from ._lib import check, lib, ptr, stream_of
+    if not (torch.is_tensor(pred_evidence) and torch.is_tensor(meas_evidence) and pred_evidence.is_cuda
+            and meas_evidence.device == pred_evidence.device):
+        raise RuntimeError("occupancy_score needs two tensors on one GPU: the product has no CPU path")
+    if pred_evidence.shape != meas_evidence.shape:
+        raise ValueError(f"occupancy_score: the grids differ in shape, {tuple(pred_evidence.shape)} against "
+                         f"{tuple(meas_evidence.shape)}")
+    tail = 2 if pred_evidence.dim() == 3 else 4
+    if pred_evidence.dim() < 3 or pred_evidence.shape[-tail] != 2:
+        raise ValueError("occupancy_score: evidence must be [..., 2, Z, H, W] or [S, 2, V], hit and free")
+    if (pred_evidence.dtype, meas_evidence.dtype) != (torch.float32, torch.float32):
+        raise TypeError("occupancy_score: evidence must be float32")
+    th = _thresholds(thresholds)
+    T, B = len(th), int(bins)
+    lead = tuple(pred_evidence.shape[:-tail])
+    S, V = math.prod(lead), math.prod(pred_evidence.shape[-tail + 1:])
+    pred, meas = pred_evidence.contiguous(), meas_evidence.contiguous()
+    ncols = 5 + 3 * T + 2 * B
+    nbytes = ctypes.c_int64(0)
+    check(lib().vidar_occ_score_workspace_bytes(S, V, T, B, ctypes.addressof(nbytes)), "occupancy_score")
+    empty = S == 0 or V == 0
+    table = (torch.zeros if empty else torch.empty)((S, ncols), dtype=torch.float64, device=pred.device)
+    ws = torch.empty(max(nbytes.value, 8), dtype=torch.uint8, device=pred.device)
+    th_host = (ctypes.c_float * T)(*th)
+    check(lib().vidar_occ_score_f32(ptr(pred), ptr(meas), ctypes.addressof(th_host), ptr(table), S, V, T, B,
+                                    float(min_evidence), float(min_meas_evidence), float(min_hits), ptr(ws),
+                                    nbytes.value, stream_of(pred)), "occupancy_score")
+    return table.view(*lead, ncols)
+
+
+def _ratio(num, den):
+    return float(num) / float(den) if float(den) != 0.0 else float("nan")
+
+
+def occupancy_metrics(table, thresholds=OCC_THRESHOLDS, bins=OCC_BINS):
+    """occupancy_score's table [..., 5 + 3 T + 2 bins] (a tensor on any device, or anything numpy reads) summed over its
+    leading dimensions -> dict of host numbers:
+      n_pred, n_meas, n_both, n_occ;  coverage = n_both / n_meas;  brier = brier sum / n_both;
+      thresholds [T];  tp, fp, fn, iou = tp / (tp + fp + fn), precision = tp / (tp + fp), recall = tp / (tp + fn), each [T];
+      reliability: dict(cnt [bins], freq [bins] = pos / cnt) -- of the voxels the forecast puts in a bin of o_p, how many
+      held a return.
+    NaN where a denominator is 0.  Ratios of counts: a table whose every entry was divided by one number gives the same."""
+    th = _thresholds(thresholds)
+    T, B = len(th), int(bins)
+    t = table.detach().double().cpu().numpy() if torch.is_tensor(table) else np.asarray(table, dtype=np.float64)
+    if t.shape[-1] != 5 + 3 * T + 2 * B:
+        raise ValueError(f"occupancy_metrics: {t.shape[-1]} columns, {5 + 3 * T + 2 * B} expected for {T} thresholds and "
+                         f"{B} bins")
+    t = t.reshape(-1, t.shape[-1]).sum(0)
+    out = {k: float(t[i]) for i, k in enumerate(OCC_FIXED_COLUMNS[:4])}
+    out["coverage"] = _ratio(t[2], t[1])
+    out["brier"] = _ratio(t[4], t[2])
+    out["thresholds"] = th
+    tp, fp, fn = (t[5 + i:5 + 3 * T:3] for i in range(3))
+    out["tp"], out["fp"], out["fn"] = ([float(v) for v in x] for x in (tp, fp, fn))
+    out["iou"] = [_ratio(a, a + b + c) for a, b, c in zip(tp, fp, fn)]
+    out["precision"] = [_ratio(a, a + b) for a, b in zip(tp, fp)]
+    out["recall"] = [_ratio(a, a + c) for a, c in zip(tp, fn)]
+    cnt, pos = t[5 + 3 * T::2], t[6 + 3 * T::2]
+    out["reliability"] = dict(cnt=[float(v) for v in cnt], freq=[_ratio(p, c) for p, c in zip(pos, cnt)])
+    return out
 
 
 def occupancy_bev(occ, size_px=None):

@@ -267,6 +267,28 @@ def ray_occupancy_cam(sigma, pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0, step=1
     return hit, free
 
 
+def sweep_evidence(origin, pts, tindex, shape, step=1.0, K=K_SAMPLES):
+    """measured evidence of a sweep -> (hit, free), both [F,Z,Y,X] = `shape` fp32, no grad: the rays of ray_occupancy
+    (origin [F,3], pts [R,3], tindex [R], voxel units) with pts the MEASURED returns; no volume is read.  free takes
+    a_k = clamp((L - (k + 0.5) step) / step, 0, 1) at every waypoint before the return (L = |p - o|), hit the trilinear
+    weights of the end point itself; include/vidar_hip.h: vidar_sweep_evidence_f32.  The grids compare cell for cell with
+    ray_occupancy's.  Under the deterministic mode both volumes are accumulated in fixed point."""
+    origin, pts, tindex = _f(origin), _f(pts), _f(tindex)
+    F_, Z, Y, X = (int(n) for n in shape)
+    if not (origin.is_cuda and pts.device == origin.device and tindex.device == origin.device):
+        raise RuntimeError("sweep_evidence needs its rays on one GPU: there is no CPU path")
+    if tuple(origin.shape) != (F_, 3) or pts.dim() != 2 or pts.shape[1] != 3 or tuple(tindex.shape) != (pts.shape[0],):
+        raise ValueError(f"sweep_evidence: origin [{F_},3], pts [R,3], tindex [R]")
+    if min(F_, Z, Y, X) <= 0:
+        raise ValueError("sweep_evidence: shape must be four positive sizes (F, Z, Y, X)")
+    hit = torch.empty((F_, Z, Y, X), device=origin.device); free = torch.empty_like(hit)
+    deterministic.sync()
+    ws, wsp, wsn = workspace(occupancy_workspace_bytes, F_, Z, Y, X, like=origin)
+    check(lib().vidar_sweep_evidence_f32(ptr(origin), ptr(pts), ptr(tindex), ptr(hit), ptr(free), F_, pts.shape[0],
+                                         Z, Y, X, int(K), step, wsp, wsn, stream_of(origin)), "sweep_evidence")
+    return hit, free
+
+
 def cam_rays(pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0):
     """the rays ray_argmax_cam marches, written out: -> (origin [F,C,3], pts [F,C,Hs,Ws,3]) in voxel units."""
     pix2vox = _f(pix2vox)

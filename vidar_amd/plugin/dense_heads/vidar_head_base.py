@@ -27,6 +27,7 @@ from . import ray_ops
 
 _STATS_KEY = "ray_stats"      # entry of a pred_dict: decode with ray_ops.ray_stats and return "pred_stats" as well
 _OCC_KEY = "ray_occupancy"    # entry of a pred_dict: march the decode's rays with ray_ops.ray_occupancy, return its grids
+_MEAS_KEY = "sweep_evidence"  # entry of a pred_dict: hand the decode's rays to ray_ops.sweep_evidence, return its grids
 
 
 def _metre_stats(stats, scale):
@@ -276,7 +277,8 @@ class ViDARHeadBase(ViDARHeadTemplate):
         render_rays, never by the detector's evaluation) decodes with ray_ops.ray_stats -- the same distances -- and adds
         pred_stats: list[bs] of list[frames] of [n, 4], row for row with pred_pcds, mean and rms in metres.
         A true pred_dict["ray_occupancy"] (set by render_occupancy) hands the very rays of the decode to
-        ray_ops.ray_occupancy instead and returns [bs, F, 2, Z, H, W], hit and free."""
+        ray_ops.ray_occupancy instead and returns [bs, F, 2, Z, H, W], hit and free; a true pred_dict["sweep_evidence"]
+        (set by measured_occupancy) hands them to ray_ops.sweep_evidence, which reads no volume."""
         bev_preds = pred_dict["next_bev_preds"].float()
         valid_frames = pred_dict["valid_frames"]
         F_, inter_num, bs, token_num, Z = bev_preds.shape
@@ -287,6 +289,10 @@ class ViDARHeadBase(ViDARHeadTemplate):
         if pred_dict.get(_OCC_KEY):
             return torch.stack([torch.stack(ray_ops.ray_occupancy(
                 self._volumes(last, b, Z, H, W), origin_grids[b], torch.nan_to_num(gt_grids[b], nan=-1.0e6), tindex[b],
+                self.ray_grid_step, self.ray_grid_num), 1) for b in range(bs)])
+        if pred_dict.get(_MEAS_KEY):
+            return torch.stack([torch.stack(ray_ops.sweep_evidence(
+                origin_grids[b], torch.nan_to_num(gt_grids[b], nan=-1.0e6), tindex[b], (F_, Z, H, W),
                 self.ray_grid_step, self.ray_grid_num), 1) for b in range(bs)])
         # render_rays(return_stats=True) asks for the confidence through the dict every head hands on
         decode = ray_ops.ray_stats if pred_dict.get(_STATS_KEY) else ray_ops.ray_argmax
@@ -430,3 +436,15 @@ class ViDARHeadBase(ViDARHeadTemplate):
                                                     stride)])
             total = cam if total is None else total + cam
         return total
+
+    @torch.no_grad()
+    def measured_occupancy(self, pred_dict, gt_points, *, tgt_bev_h, tgt_bev_w, tgt_pc_range, img_metas=None,
+                           start_idx=0, batched_origin_points=None):
+        """Occupancy evidence of a MEASURED sweep -> [bs, F, 2, Z, H, W] fp32, hit and free (ray_ops.sweep_evidence):
+        where the rays of `gt_points` returned and which voxels they passed on the way.  The rays are exactly those
+        get_point_cloud_prediction decodes (the same origin, voxel mapping, nan_to_num and tindex), so the grids compare
+        cell for cell with render_occupancy(end_points=gt_points); pred_dict only gives the grid its shape and frames.
+        vidar_amd.forecast.occupancy_score holds the two against each other."""
+        return self.get_point_cloud_prediction(
+            dict(pred_dict, **{_MEAS_KEY: True}), gt_points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range,
+            img_metas=img_metas, batched_origin_points=batched_origin_points)

@@ -281,14 +281,18 @@ class ViDAR(nn.Module):
     def forward_test(self, img_metas, img=None, gt_points=None, img_feats=None, **kwargs):
         """history BEV over all frames -> auto-regressive future BEVs -> arg-max decode -> per-frame
         squared-L2 chamfer distance (compute_chamfer_distance_inner) and the 4d-occ ray errors
-        (utils/eval_utils.py:185-225: l1_error / absrel_error)."""
+        (utils/eval_utils.py:185-225: l1_error / absrel_error).  With eval_utils.set_occupancy_metrics on, the occupancy
+        forecast of the same rays is scored against the measured sweep as well (_occupancy_table) and every frame.k
+        dictionary also carries the additive `occ.*` entries; off, nothing more is launched."""
         pred_dict, cur_metas = self._future_pred_dict(img_metas, img, img_feats)
         on_device = eval_utils.device_metrics()
         decode = self.future_pred_head.get_point_cloud_prediction(
             pred_dict, gt_points, 0, tgt_bev_h=self.bev_h, tgt_bev_w=self.bev_w,
             tgt_pc_range=self.point_cloud_range, img_metas=cur_metas, **(dict(as_rays=True) if on_device else {}))
+        occ_options = eval_utils.occupancy_metrics()
+        occ = None if occ_options is None else self._occupancy_table(pred_dict, gt_points, cur_metas, occ_options)
         if on_device:
-            return [self._device_metrics_tail(decode, cur_metas)]
+            return [self._device_metrics_tail(decode, cur_metas, occ)]
         ret = dict()
         for f in range(len(decode["pred_pcds"][0])):
             cd, l1, absrel, count = 0.0, 0.0, 0.0, 0
@@ -306,16 +310,38 @@ class ViDAR(nn.Module):
                     self._save_prediction(pred, cur_metas[b], f)
                 count += 1
             ret[f"frame.{f}"] = dict(count=count, chamfer_distance=cd, l1_error=l1, absrel_error=absrel)
+        if occ is not None:
+            self._add_occupancy_entries(ret, occ[0].cpu(), occ[1])                                 # one read of its own
         return [ret]
 
-    def _device_metrics_tail(self, rays, cur_metas):
+    def _occupancy_table(self, pred_dict, gt_points, cur_metas, options):
+        """(table [bs, F, columns] f64 on the device, the columns' names): forecast.occupancy_score of the predicted
+        evidence of the rays forward_test decodes -- render_occupancy(end_points=gt_points) -- against the measured
+        evidence of those rays, measured_occupancy(gt_points)."""
+        from ... import forecast as FC
+        head = self.future_pred_head
+        geom = dict(tgt_bev_h=self.bev_h, tgt_bev_w=self.bev_w, tgt_pc_range=self.point_cloud_range, img_metas=cur_metas)
+        table = FC.occupancy_score(head.render_occupancy(pred_dict, end_points=gt_points, **geom),
+                                   head.measured_occupancy(pred_dict, gt_points, **geom), **options)
+        return table, FC.occupancy_columns(options.get("thresholds", FC.OCC_THRESHOLDS), options.get("bins", FC.OCC_BINS))
+
+    @staticmethod
+    def _add_occupancy_entries(ret, table, names):
+        """the host copy of _occupancy_table's table, summed over the samples, as `occ.<column>` entries of frame.k"""
+        for f in range(table.shape[1]):
+            row = table[:, f].sum(0)
+            ret[f"frame.{f}"].update({f"occ.{name}": float(row[i]) for i, name in enumerate(names)})
+
+    def _device_metrics_tail(self, rays, cur_metas, occ=None):
         """The metric tail of forward_test for every (sample, frame) segment at once (eval_utils.set_device_metrics):
         eval_utils.forecast_metrics_device scores the rays where they are, and ONE host read of its [bs, F, 4] table
-        fills the frame.k dictionaries."""
+        fills the frame.k dictionaries.  The occupancy table (`occ`, _occupancy_table's pair) rides in that same read."""
         pred, frame = rays["pred_pts"], rays["frame"]
         bs, F_ = rays["origin"].shape[:2]
-        table = eval_utils.forecast_metrics_device(pred, rays["gt_pts"], frame, rays["origin"],
-                                                   self.point_cloud_range).cpu()                     # the one read
+        table = eval_utils.forecast_metrics_device(pred, rays["gt_pts"], frame, rays["origin"], self.point_cloud_range)
+        if occ is not None:
+            table = torch.cat([table, occ[0].to(table.dtype)], -1)
+        table = table.cpu()                                                                          # the one read
         ret = dict()
         for f in range(F_):
             cd_f, l1, absrel, count = 0.0, 0.0, 0.0, 0
@@ -328,6 +354,8 @@ class ViDAR(nn.Module):
                     self._save_prediction(pred[b][frame[b] == f], cur_metas[b], f)
                 count += 1
             ret[f"frame.{f}"] = dict(count=count, chamfer_distance=cd_f, l1_error=l1, absrel_error=absrel)
+        if occ is not None:
+            self._add_occupancy_entries(ret, table[..., 4:], occ[1])
         return ret
 
     def _viz_pcd(self, pred_pcd, gt_pcd, origin, img_meta, frame_idx):

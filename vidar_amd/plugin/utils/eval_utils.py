@@ -150,6 +150,37 @@ def device_metrics():
     return os.environ.get("VIDAR_DEVICE_METRICS", "0") not in ("", "0")
 
 
+# ---- the occupancy score (csrc/occ_score.hip; vidar_amd.forecast.occupancy_score) --------------------------------------
+_occupancy_metrics = None   # None: follow VIDAR_OCC_METRICS
+_occupancy_options = {}
+_OCC_OPTIONS = ("thresholds", "min_evidence", "min_meas_evidence", "min_hits", "bins")
+
+
+def set_occupancy_metrics(on, **options):
+    """Make ViDAR.forward_test also score the occupancy forecast against the measured sweep: the predicted evidence of the
+    very rays it decodes, the measured evidence of those rays (ViDARHeadBase.measured_occupancy) and
+    forecast.occupancy_score's table, whose columns join every frame.k dictionary as additive `occ.*` entries.
+    options: thresholds, min_evidence, min_meas_evidence, min_hits, bins -- occupancy_score's keywords; what is not given
+    keeps occupancy_score's default.  Off by default; `None` returns the decision to the environment variable
+    VIDAR_OCC_METRICS.  -> the previous setting"""
+    global _occupancy_metrics, _occupancy_options
+    unknown = sorted(set(options) - set(_OCC_OPTIONS))
+    if unknown:
+        raise TypeError(f"set_occupancy_metrics: unknown option {unknown[0]!r}; the options are {', '.join(_OCC_OPTIONS)}")
+    prev, _occupancy_metrics = _occupancy_metrics, (None if on is None else bool(on))
+    _occupancy_options = {k: v for k, v in options.items() if v is not None}
+    return prev
+
+
+def occupancy_metrics():
+    """None while the occupancy score is off, else the keywords forward_test hands to forecast.occupancy_score"""
+    on = _occupancy_metrics
+    if on is None:
+        import os
+        on = os.environ.get("VIDAR_OCC_METRICS", "0") not in ("", "0")
+    return dict(_occupancy_options) if on else None
+
+
 def ray_errors_device(pred, pred_start, gt, gt_start, origin, max_gt, *, return_per_ray=False):
     """compute_ray_errors for S segments -- (sample, frame) pairs -- in one call, on the device, in fp64.
     pred [P,3] / gt [G,3] f32 grouped by segment, pred_start / gt_start [S+1] i32 DEVICE tensors (segment s owns rows
