@@ -9,7 +9,9 @@ and the forecast API on top of it (ViDARHeadBase.render_rays / render_cameras, V
    F.grid_sample, `== 0`) says for every ray whether any waypoint samples a non-zero value.
 2. geometry: a volume with one high-logit plane; per-pixel distance against the analytic ray-plane distance.
 3. pix2vox round trip through the fp64 projection.
-4. render_rays on the ground-truth rays == get_point_cloud_prediction, bit for bit.
+4. render_rays on the ground-truth rays == get_point_cloud_prediction, bit for bit; on the tiny heads of
+   tests/head_route_cases.py (both classes, both kernel forms) the statistics leave the points alone and the two evidence
+   routes are their ops on the decode's own rays.
 5. ViDAR.forecast runs without gt_points.
 Shapes are the smallest that still take every path: 4 x 12 x 14 voxels, F = C = 2, 12 x 20 and 13 x 21 pixels (no multiple
 of the 4 rays of a block), K = 512 (register form) and 37 (streamed, no multiple of 64)."""
@@ -20,6 +22,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import head_route_cases as RC
 from oracle import head as H
 from forecast_view_cases import C, F_, GRIDS, X, Y, Z, camera, camera_set, volume
 
@@ -218,6 +221,51 @@ def test_render_rays_on_the_ground_truth_rays_is_the_decode(small_model):
         head.render_rays(pred_dict, **geom)
     with pytest.raises(ValueError):
         head.render_rays(pred_dict, directions=torch.zeros(1, 3), end_points=gt, **geom)
+
+
+@pytest.mark.parametrize("K", [37, 512], ids=["K37-streamed", "K512-register"])
+@pytest.mark.parametrize("cls", RC.CLASSES)
+def test_the_routes_of_the_decode_agree_on_the_real_ops(cls, K, monkeypatch):
+    """the tiny heads of tests/test_head_decode_routes_cpu.py on the kernels: render_rays on the decode's own clouds is the
+    decode, with or without the statistics, and the two evidence routes are their ops on the decode's recorded rays"""
+    from vidar_amd import deterministic
+    from vidar_amd.plugin.dense_heads import ray_ops
+    head = RC.build_head(cls, K).cuda()
+    pred_dict, gt = RC.to("cuda", RC.pred_dict(head)), RC.to("cuda", RC.clouds(head))
+    kw = dict(RC.geom(head), img_metas=RC.metas())
+    if cls == "ViDARHeadBase":
+        kw["batched_origin_points"] = RC.origin_points().cuda()
+    marched = []                                                      # the arguments the decode hands to ray_argmax
+    real = ray_ops.ray_argmax
+
+    def recorded(*a):
+        marched.append(a)
+        return real(*a)
+    monkeypatch.setattr(ray_ops, "ray_argmax", recorded)
+    decode = head.get_point_cloud_prediction(pred_dict, gt, 0, *RC.geom(head).values(),
+                                             **{k: v for k, v in kw.items() if not k.startswith("tgt_")})
+    monkeypatch.setattr(ray_ops, "ray_argmax", real)
+    assert len(marched) == RC.BS
+    rendered = head.render_rays(pred_dict, end_points=gt, **kw)
+    with_stats, stats = head.render_rays(pred_dict, end_points=gt, return_stats=True, **kw)
+    kept = 0
+    # the ray with the NaN coordinate is decoded to NaN points: the bits themselves are compared
+    same_bits = lambda x, y: x.shape == y.shape and torch.equal(x.view(torch.int32), y.view(torch.int32))
+    for b in range(RC.BS):
+        assert len(rendered[b]) == len(with_stats[b]) == len(decode["pred_pcds"][b]) == RC.F_
+        for a, s, st, d in zip(rendered[b], with_stats[b], stats[b], decode["pred_pcds"][b]):
+            assert same_bits(a, d) and same_bits(s, d) and st.shape == (d.shape[0], 4)
+            kept += d.shape[0]
+    # the rays of the decoded frames are kept: 4 of 5 points of the two clouds (the one with the NaN coordinate may go)
+    assert 0 <= sum(n - len(range(0, n, 5)) for n in RC.LENGTHS) - kept <= 1
+    with deterministic.use(True):                                     # equal bits need the order-independent sums
+        occ = head.render_occupancy(pred_dict, end_points=gt, **kw)
+        meas = head.measured_occupancy(pred_dict, gt, **kw)
+        for b, (sigma, origin, pts, tindex, step, k) in enumerate(marched):
+            assert k == K and sigma.shape == (RC.F_, RC.Z, RC.H, RC.W)
+            assert torch.equal(occ[b], torch.stack(ray_ops.ray_occupancy(sigma, origin, pts, tindex, step, k), 1))
+            assert torch.equal(meas[b], torch.stack(ray_ops.sweep_evidence(origin, pts, tindex, sigma.shape, step, k), 1))
+    assert float(occ[:, :, 0].sum()) > 0 and float(meas[:, :, 1].sum()) > 0
 
 
 def test_forecast_needs_no_ground_truth(small_model):

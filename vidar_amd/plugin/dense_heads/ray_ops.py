@@ -41,6 +41,21 @@ def _dims(sigma, pts):
     return F_, pts.shape[0], Z, Y, X
 
 
+def _ray_bwd(ctx, grad, entry, name, per_ray):
+    """d loss / d sigma of the three ray losses: `entry` on what the forward saved (the rays and lse / aux) and the
+    per-ray gradient; `per_ray`: fp32 values moved per ray, for the span's byte count"""
+    sigma, origin, pts, tindex, saved = ctx.saved_tensors
+    step, K = ctx.cfg
+    F_, R, Z, Y, X = _dims(sigma, pts)
+    g = torch.empty_like(sigma)
+    deterministic.sync()
+    ws, wsp, wsn = workspace(lib().vidar_ray_bwd_workspace_bytes, F_, Z, Y, X, like=sigma)
+    with TIMER.span(name, 4 * (2 * sigma.numel() + R * per_ray)):
+      check(entry(ptr(sigma), ptr(origin), ptr(pts), ptr(tindex), ptr(saved), ptr(_f(grad)), ptr(g),
+                  F_, R, Z, Y, X, K, step, wsp, wsn, stream_of(sigma)), name)
+    return g
+
+
 class _RayCE(Function):
     @staticmethod
     def forward(ctx, sigma, origin, gt, tindex, step, K):
@@ -58,17 +73,7 @@ class _RayCE(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_ce, _grad_valid):
-        sigma, origin, gt, tindex, lse = ctx.saved_tensors
-        step, K = ctx.cfg
-        F_, R, Z, Y, X = _dims(sigma, gt)
-        g = torch.empty_like(sigma)
-        deterministic.sync()
-        ws, wsp, wsn = workspace(lib().vidar_ray_bwd_workspace_bytes, F_, Z, Y, X, like=sigma)
-        with TIMER.span("ray_ce_bwd", 4 * (2 * sigma.numel() + R * 6)):
-          check(lib().vidar_ray_ce_bwd_f32(ptr(sigma), ptr(origin), ptr(gt), ptr(tindex), ptr(lse),
-                                         ptr(_f(grad_ce)), ptr(g), F_, R, Z, Y, X, K, step,
-                                         wsp, wsn, stream_of(sigma)), "ray_ce_bwd")
-        return g, None, None, None, None, None
+        return (_ray_bwd(ctx, grad_ce, lib().vidar_ray_ce_bwd_f32, "ray_ce_bwd", 6),) + (None,) * 5
 
 
 class _RayGumbel(Function):
@@ -90,17 +95,7 @@ class _RayGumbel(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_dist):
-        sigma, origin, pts, tindex, aux = ctx.saved_tensors
-        step, K = ctx.cfg
-        F_, R, Z, Y, X = _dims(sigma, pts)
-        g = torch.empty_like(sigma)
-        deterministic.sync()
-        ws, wsp, wsn = workspace(lib().vidar_ray_bwd_workspace_bytes, F_, Z, Y, X, like=sigma)
-        with TIMER.span("ray_gumbel_bwd", 4 * (2 * sigma.numel() + R * 8)):
-          check(lib().vidar_ray_gumbel_bwd_f32(ptr(sigma), ptr(origin), ptr(pts), ptr(tindex), ptr(aux),
-                                             ptr(_f(grad_dist)), ptr(g), F_, R, Z, Y, X, K, step,
-                                             wsp, wsn, stream_of(sigma)), "ray_gumbel_bwd")
-        return g, None, None, None, None, None, None
+        return (_ray_bwd(ctx, grad_dist, lib().vidar_ray_gumbel_bwd_f32, "ray_gumbel_bwd", 8),) + (None,) * 6
 
 
 class _RayDist(Function):
@@ -124,17 +119,7 @@ class _RayDist(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_dist, _grad_len, _grad_valid):
-        sigma, origin, gt, tindex, aux = ctx.saved_tensors
-        step, K = ctx.cfg
-        F_, R, Z, Y, X = _dims(sigma, gt)
-        g = torch.empty_like(sigma)
-        deterministic.sync()
-        ws, wsp, wsn = workspace(lib().vidar_ray_bwd_workspace_bytes, F_, Z, Y, X, like=sigma)
-        with TIMER.span("ray_dist_bwd", 4 * (2 * sigma.numel() + R * 8)):
-          check(lib().vidar_ray_dist_bwd_f32(ptr(sigma), ptr(origin), ptr(gt), ptr(tindex), ptr(aux),
-                                           ptr(_f(grad_dist)), ptr(g), F_, R, Z, Y, X, K, step,
-                                           wsp, wsn, stream_of(sigma)), "ray_dist_bwd")
-        return g, None, None, None, None, None, None
+        return (_ray_bwd(ctx, grad_dist, lib().vidar_ray_dist_bwd_f32, "ray_dist_bwd", 8),) + (None,) * 6
 
 
 def ray_ce(sigma, origin, gt, tindex, step=1.0, K=K_SAMPLES):
@@ -163,14 +148,21 @@ def ray_dist(sigma, origin, gt, tindex, noise=None, step=1.0, K=K_SAMPLES):
     return _RayDist.apply(sigma, origin, gt, tindex, noise, float(step), int(K))
 
 
+def _listed(sigma, origin, pts, tindex, *outs):
+    """the prologue of the no-grad ops on listed rays -> ((sigma, origin, pts, tindex) as contiguous fp32,
+    (F, R, Z, Y, X), one empty output per entry of `outs`: [R, *entry], or like sigma for None)"""
+    rays = _f(sigma.detach()), _f(origin), _f(pts), _f(tindex)
+    dims = _dims(rays[0], rays[2])
+    return rays, dims, tuple(torch.empty_like(rays[0]) if o is None else torch.empty((dims[1], *o), device=rays[0].device)
+                             for o in outs)
+
+
 def ray_argmax(sigma, origin, pts, tindex, step=1.0, K=K_SAMPLES):
     """test-time decode -> (pred_dist [R], gt_dist [R]) in voxel units, no grad."""
-    sigma, origin, pts, tindex = _f(sigma.detach()), _f(origin), _f(pts), _f(tindex)
-    F_, R, Z, Y, X = _dims(sigma, pts)
-    pred = torch.empty(R, device=sigma.device); gt = torch.empty_like(pred)
-    check(lib().vidar_ray_argmax_f32(ptr(sigma), ptr(origin), ptr(pts), ptr(tindex), ptr(pred),
-                                     ptr(gt), F_, R, Z, Y, X, int(K), step, stream_of(sigma)), "ray_argmax")
-    return pred, gt
+    rays, dims, out = _listed(sigma, origin, pts, tindex, (), ())
+    check(lib().vidar_ray_argmax_f32(*map(ptr, rays), *map(ptr, out), *dims, int(K), step, stream_of(rays[0])),
+          "ray_argmax")
+    return out
 
 
 def _cam_args(pix2vox, hw, u0, v0, du, dv):
@@ -180,10 +172,8 @@ def _cam_args(pix2vox, hw, u0, v0, du, dv):
     return F_, C, int(hw[0]), int(hw[1]), float(u0), float(v0), float(du), float(dv)
 
 
-def ray_argmax_cam(sigma, pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0, step=1.0, K=K_SAMPLES):
-    """camera-view decode: sigma [F,Z,Y,X], pix2vox [F,C,4,4] (homogeneous pixel -> voxel, affine), one ray per pixel
-    (x, y) of the hw = (Hs, Ws) grid at u = u0 + x*du, v = v0 + y*dv -> dist [F,C,Hs,Ws] in voxel units, 0 where the
-    ray meets nothing.  The rays are never stored (vidar_ray_argmax_cam_f32); no grad."""
+def _cam(sigma, pix2vox, hw, u0, v0, du, dv):
+    """the prologue of the camera-view ops -> (sigma, pix2vox as contiguous fp32, _cam_args' geometry, (Z, Y, X))"""
     sigma, pix2vox = _f(sigma.detach()), _f(pix2vox)
     geom = _cam_args(pix2vox, hw, u0, v0, du, dv)
     F_, Z, Y, X = sigma.shape
@@ -191,8 +181,16 @@ def ray_argmax_cam(sigma, pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0, step=1.0,
         raise ValueError(f"pix2vox holds {geom[0]} frames, sigma {F_}")
     if pix2vox.device != sigma.device:
         raise RuntimeError(f"pix2vox is on {pix2vox.device}, sigma on {sigma.device}")
+    return sigma, pix2vox, geom, (Z, Y, X)
+
+
+def ray_argmax_cam(sigma, pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0, step=1.0, K=K_SAMPLES):
+    """camera-view decode: sigma [F,Z,Y,X], pix2vox [F,C,4,4] (homogeneous pixel -> voxel, affine), one ray per pixel
+    (x, y) of the hw = (Hs, Ws) grid at u = u0 + x*du, v = v0 + y*dv -> dist [F,C,Hs,Ws] in voxel units, 0 where the
+    ray meets nothing.  The rays are never stored (vidar_ray_argmax_cam_f32); no grad."""
+    sigma, pix2vox, geom, zyx = _cam(sigma, pix2vox, hw, u0, v0, du, dv)
     dist = torch.empty(geom[:4], device=sigma.device)
-    check(lib().vidar_ray_argmax_cam_f32(ptr(sigma), ptr(pix2vox), ptr(dist), *geom, Z, Y, X, int(K), step,
+    check(lib().vidar_ray_argmax_cam_f32(ptr(sigma), ptr(pix2vox), ptr(dist), *geom, *zyx, int(K), step,
                                          stream_of(sigma)), "ray_argmax_cam")
     return dist
 
@@ -201,28 +199,19 @@ def ray_stats(sigma, origin, pts, tindex, step=1.0, K=K_SAMPLES):
     """ray_argmax with its confidence -> (pred_dist [R], gt_dist [R], stats [R, 4]) in voxel units, no grad.  The two
     distances are ray_argmax's bits; stats = (p_max, mean, rms, entropy) of the softmax over the ray's live waypoints
     (include/vidar_hip.h: vidar_ray_stats_f32), four zeros for a skipped ray or one without a live waypoint."""
-    sigma, origin, pts, tindex = _f(sigma.detach()), _f(origin), _f(pts), _f(tindex)
-    F_, R, Z, Y, X = _dims(sigma, pts)
-    pred = torch.empty(R, device=sigma.device); gt = torch.empty_like(pred)
-    stats = torch.empty((R, 4), device=sigma.device)
-    check(lib().vidar_ray_stats_f32(ptr(sigma), ptr(origin), ptr(pts), ptr(tindex), ptr(pred), ptr(gt), ptr(stats),
-                                    F_, R, Z, Y, X, int(K), step, stream_of(sigma)), "ray_stats")
-    return pred, gt, stats
+    rays, dims, out = _listed(sigma, origin, pts, tindex, (), (), (4,))
+    check(lib().vidar_ray_stats_f32(*map(ptr, rays), *map(ptr, out), *dims, int(K), step, stream_of(rays[0])),
+          "ray_stats")
+    return out
 
 
 def ray_stats_cam(sigma, pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0, step=1.0, K=K_SAMPLES):
     """ray_argmax_cam with its confidence -> (dist [F,C,Hs,Ws], stats [F,C,Hs,Ws,4]) in voxel units, no grad: dist is
     ray_argmax_cam's bits, stats as in ray_stats (four zeros where the ray meets nothing)."""
-    sigma, pix2vox = _f(sigma.detach()), _f(pix2vox)
-    geom = _cam_args(pix2vox, hw, u0, v0, du, dv)
-    F_, Z, Y, X = sigma.shape
-    if geom[0] != F_:
-        raise ValueError(f"pix2vox holds {geom[0]} frames, sigma {F_}")
-    if pix2vox.device != sigma.device:
-        raise RuntimeError(f"pix2vox is on {pix2vox.device}, sigma on {sigma.device}")
+    sigma, pix2vox, geom, zyx = _cam(sigma, pix2vox, hw, u0, v0, du, dv)
     dist = torch.empty(geom[:4], device=sigma.device)
     stats = torch.empty((*geom[:4], 4), device=sigma.device)
-    check(lib().vidar_ray_stats_cam_f32(ptr(sigma), ptr(pix2vox), ptr(dist), ptr(stats), *geom, Z, Y, X, int(K), step,
+    check(lib().vidar_ray_stats_cam_f32(ptr(sigma), ptr(pix2vox), ptr(dist), ptr(stats), *geom, *zyx, int(K), step,
                                         stream_of(sigma)), "ray_stats_cam")
     return dist, stats
 
@@ -239,30 +228,22 @@ def ray_occupancy(sigma, origin, pts, tindex, step=1.0, K=K_SAMPLES):
     every ray's live waypoints splatted through the trilinear weights its logits were read with -- hit takes p_k (the
     return lies at k), free takes b_k = the mass beyond k (the ray passed k); include/vidar_hip.h:
     vidar_ray_occupancy_f32.  Under the deterministic mode both volumes are accumulated in fixed point."""
-    sigma, origin, pts, tindex = _f(sigma.detach()), _f(origin), _f(pts), _f(tindex)
-    F_, R, Z, Y, X = _dims(sigma, pts)
-    hit = torch.empty_like(sigma); free = torch.empty_like(sigma)
+    rays, (F_, R, Z, Y, X), out = _listed(sigma, origin, pts, tindex, None, None)
     deterministic.sync()
-    ws, wsp, wsn = workspace(occupancy_workspace_bytes, F_, Z, Y, X, like=sigma)
-    check(lib().vidar_ray_occupancy_f32(ptr(sigma), ptr(origin), ptr(pts), ptr(tindex), ptr(hit), ptr(free),
-                                        F_, R, Z, Y, X, int(K), step, wsp, wsn, stream_of(sigma)), "ray_occupancy")
-    return hit, free
+    ws, wsp, wsn = workspace(occupancy_workspace_bytes, F_, Z, Y, X, like=rays[0])
+    check(lib().vidar_ray_occupancy_f32(*map(ptr, rays), *map(ptr, out), F_, R, Z, Y, X, int(K), step, wsp, wsn,
+                                        stream_of(rays[0])), "ray_occupancy")
+    return out
 
 
 def ray_occupancy_cam(sigma, pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0, step=1.0, K=K_SAMPLES):
     """ray_occupancy on the rays ray_argmax_cam marches (one per pixel of the hw grid, never stored) -> (hit, free)
     [F,Z,Y,X], no grad."""
-    sigma, pix2vox = _f(sigma.detach()), _f(pix2vox)
-    geom = _cam_args(pix2vox, hw, u0, v0, du, dv)
-    F_, Z, Y, X = sigma.shape
-    if geom[0] != F_:
-        raise ValueError(f"pix2vox holds {geom[0]} frames, sigma {F_}")
-    if pix2vox.device != sigma.device:
-        raise RuntimeError(f"pix2vox is on {pix2vox.device}, sigma on {sigma.device}")
+    sigma, pix2vox, geom, zyx = _cam(sigma, pix2vox, hw, u0, v0, du, dv)
     hit = torch.empty_like(sigma); free = torch.empty_like(sigma)
     deterministic.sync()
-    ws, wsp, wsn = workspace(occupancy_workspace_bytes, F_, Z, Y, X, like=sigma)
-    check(lib().vidar_ray_occupancy_cam_f32(ptr(sigma), ptr(pix2vox), ptr(hit), ptr(free), *geom, Z, Y, X, int(K), step,
+    ws, wsp, wsn = workspace(occupancy_workspace_bytes, geom[0], *zyx, like=sigma)
+    check(lib().vidar_ray_occupancy_cam_f32(ptr(sigma), ptr(pix2vox), ptr(hit), ptr(free), *geom, *zyx, int(K), step,
                                             wsp, wsn, stream_of(sigma)), "ray_occupancy_cam")
     return hit, free
 

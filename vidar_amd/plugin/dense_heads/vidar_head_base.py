@@ -12,6 +12,8 @@ What changed is the execution plan, not the math:
     of a dense [N, M, 3] expansion."""
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 import torch
 
@@ -25,9 +27,18 @@ from ..registry import HEADS, build_positional_encoding, build_transformer
 from ..utils import e2e_predictor_utils
 from . import ray_ops
 
-_STATS_KEY = "ray_stats"      # entry of a pred_dict: decode with ray_ops.ray_stats and return "pred_stats" as well
-_OCC_KEY = "ray_occupancy"    # entry of a pred_dict: march the decode's rays with ray_ops.ray_occupancy, return its grids
-_MEAS_KEY = "sweep_evidence"  # entry of a pred_dict: hand the decode's rays to ray_ops.sweep_evidence, return its grids
+
+class DecodeRays(NamedTuple):
+    """The rays the decode marches (ViDARHeadBase._decode_rays), per sample b what a listed ray op takes:
+    (volumes[b], origin_grids[b], end_grids[b], tindex[b]) in voxel units."""
+    volumes: tuple               # bs x [F, Z, H, W] logits
+    origin_grids: torch.Tensor   # [bs, F, 3]
+    end_grids: torch.Tensor      # [bs, N, 3], a NaN (padding) moved far outside: -1e6
+    tindex: torch.Tensor         # [bs, N] frame slot of a ray, -1 = skip it
+    origin_pts: torch.Tensor     # [bs, F, 3] metric origins
+    xyz: torch.Tensor            # [bs, N, 3] metric end points, NaN-padded
+    scale: float                 # metres per voxel unit along a ray (the BEV cell size)
+    shape: tuple                 # (F, Z, H, W)
 
 
 def _metre_stats(stats, scale):
@@ -273,56 +284,61 @@ class ViDARHeadBase(ViDARHeadTemplate):
     def get_point_cloud_prediction(self, pred_dict, gt_points, start_idx, tgt_bev_h, tgt_bev_w,
                                    tgt_pc_range, img_metas=None, batched_origin_points=None, as_rays=False):
         """arg-max decode (:663-752) -> dict(pred_pcds, gt_pcds, origin); as_rays: the dict of get_rendered_rays
-        instead (the device metrics' input: nothing is selected on the host).  A true pred_dict["ray_stats"] (set by
-        render_rays, never by the detector's evaluation) decodes with ray_ops.ray_stats -- the same distances -- and adds
-        pred_stats: list[bs] of list[frames] of [n, 4], row for row with pred_pcds, mean and rms in metres.
-        A true pred_dict["ray_occupancy"] (set by render_occupancy) hands the very rays of the decode to
-        ray_ops.ray_occupancy instead and returns [bs, F, 2, Z, H, W], hit and free; a true pred_dict["sweep_evidence"]
-        (set by measured_occupancy) hands them to ray_ops.sweep_evidence, which reads no volume."""
-        bev_preds = pred_dict["next_bev_preds"].float()
-        valid_frames = pred_dict["valid_frames"]
+        instead (the device metrics' input: nothing is selected on the host)."""
+        rays = self._decode_rays(pred_dict, gt_points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range, img_metas,
+                                 batched_origin_points)
+        pred, gt, _ = self._decode_dists(ray_ops.ray_argmax, rays)
+        if as_rays:
+            return self.get_rendered_rays(rays.origin_pts, rays.xyz, rays.tindex, gt, pred, tgt_pc_range)
+        return dict(
+            pred_pcds=self.get_rendered_pcds(rays.origin_pts, rays.xyz, rays.tindex, gt, pred, tgt_pc_range),
+            gt_pcds=self.get_rendered_pcds(rays.origin_pts, rays.xyz, rays.tindex, gt, gt, tgt_pc_range),
+            origin=rays.origin_pts)
+
+    def _decode_rays(self, pred_dict, points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range, img_metas=None,
+                     batched_origin_points=None):
+        """The one place that turns (pred_dict, points) into the rays a decode marches -> DecodeRays.  Which logits and
+        which coordinates is the subclass's pair of hooks, _decode_preds and _decode_points; every route below -- the
+        decode, render_rays, render_occupancy, measured_occupancy -- takes its rays from here, so they agree bit for bit."""
+        bev_preds = self._decode_preds(pred_dict).float()
+        points, batched_origin_points = self._decode_points(pred_dict, points, batched_origin_points, img_metas)
         F_, inter_num, bs, token_num, Z = bev_preds.shape
         H, W = tgt_bev_h, tgt_bev_w
         origin_grids, origin_pts, gt_grids, gt_xyz, tindex = self._process_gt_points(
-            bev_preds, gt_points, batched_origin_points, valid_frames, start_idx, F_, H, W, tgt_pc_range)
+            bev_preds, points, batched_origin_points, pred_dict["valid_frames"], start_idx, F_, H, W, tgt_pc_range)
         last = bev_preds[:, -1:]
-        if pred_dict.get(_OCC_KEY):
-            return torch.stack([torch.stack(ray_ops.ray_occupancy(
-                self._volumes(last, b, Z, H, W), origin_grids[b], torch.nan_to_num(gt_grids[b], nan=-1.0e6), tindex[b],
-                self.ray_grid_step, self.ray_grid_num), 1) for b in range(bs)])
-        if pred_dict.get(_MEAS_KEY):
-            return torch.stack([torch.stack(ray_ops.sweep_evidence(
-                origin_grids[b], torch.nan_to_num(gt_grids[b], nan=-1.0e6), tindex[b], (F_, Z, H, W),
-                self.ray_grid_step, self.ray_grid_num), 1) for b in range(bs)])
-        # render_rays(return_stats=True) asks for the confidence through the dict every head hands on
-        decode = ray_ops.ray_stats if pred_dict.get(_STATS_KEY) else ray_ops.ray_argmax
-        pred, gt, stats = [], [], []
-        for b in range(bs):
-            p, g, *s = decode(self._volumes(last, b, Z, H, W), origin_grids[b],
-                              torch.nan_to_num(gt_grids[b], nan=-1.0e6), tindex[b],
-                              self.ray_grid_step, self.ray_grid_num)
-            pred.append(p); gt.append(g); stats.extend(s)
-        scale = (tgt_pc_range[3] - tgt_pc_range[0]) / W
-        pred = torch.stack(pred) * scale
-        gt = torch.stack(gt) * scale
-        if as_rays:
-            return self.get_rendered_rays(origin_pts, gt_xyz, tindex, gt, pred, tgt_pc_range)
-        out = dict(
-            pred_pcds=self.get_rendered_pcds(origin_pts, gt_xyz, tindex, gt, pred, tgt_pc_range),
-            gt_pcds=self.get_rendered_pcds(origin_pts, gt_xyz, tindex, gt, gt, tgt_pc_range),
-            origin=origin_pts)
-        if stats:
-            out["pred_stats"] = self.get_rendered_stats(gt_xyz, tindex, gt, _metre_stats(torch.stack(stats), scale),
-                                                        tgt_pc_range, origin_pts.shape[1])
-        return out
+        return DecodeRays(tuple(self._volumes(last, b, Z, H, W) for b in range(bs)), origin_grids,
+                          torch.nan_to_num(gt_grids, nan=-1.0e6), tindex, origin_pts, gt_xyz,
+                          (tgt_pc_range[3] - tgt_pc_range[0]) / W, (F_, Z, H, W))
+
+    def _march(self, op, rays):
+        """op(sigma, origin, pts, tindex, step, K) -- a listed op of ray_ops -- on every sample of `rays`, in order"""
+        return [op(rays.volumes[b], rays.origin_grids[b], rays.end_grids[b], rays.tindex[b], self.ray_grid_step,
+                   self.ray_grid_num) for b in range(len(rays.volumes))]
+
+    def _decode_dists(self, op, rays):
+        """ray_ops.ray_argmax or ray_ops.ray_stats on `rays` -> (pred [bs, N], gt [bs, N] in metres, what else the op
+        returned, stacked over the samples)"""
+        pred, gt, *more = (torch.stack(t) for t in zip(*self._march(op, rays)))
+        return pred * rays.scale, gt * rays.scale, more
+
+    @staticmethod
+    def _evidence(pairs):
+        """per sample (hit, free), each [F, Z, H, W] -> [bs, F, 2, Z, H, W]"""
+        return torch.stack([torch.stack(pair, 1) for pair in pairs])
 
     def _ray_frame_labels(self, valid_frames):
         """the value the last column of a point holds for each frame slot of `valid_frames`"""
         return [float(f) for f in valid_frames]
 
     def _decode_preds(self, pred_dict):
-        """the logits get_point_cloud_prediction decodes: [F, inter, bs, Q, Z]"""
+        """hook of _decode_rays: the logits to decode, [F, inter, bs, Q, Z]"""
         return pred_dict["next_bev_preds"]
+
+    def _decode_points(self, pred_dict, points, batched_origin_points, img_metas):
+        """hook of _decode_rays: (points, batched_origin_points) in the coordinates the decoded volumes live in (here:
+        as they are)"""
+        return points, batched_origin_points
 
     def frame_alignment(self, valid_frames, img_metas):
         """[bs, F, 4, 4] fp64, row-vector form: frame slot f's own LiDAR coordinates -> the coordinates its decoded
@@ -334,7 +350,7 @@ class ViDARHeadBase(ViDARHeadTemplate):
                        return_stats=False):
         """The decode seen from the cameras: one ray per `stride` x `stride` block of every camera's pixels, through the
         block's centre, marched by ray_ops.ray_argmax_cam (the rays are never stored).
-        cameras: indices into img_metas[b]["lidar2img"] (None = all; their images must share one size).
+        cameras: indices into img_metas[b]["lidar2img"] (None or "all" = all; their images must share one size).
         -> depth [bs, F, C, Hs, Ws], Hs = ceil(H / stride): metres along the ray (voxel units times the BEV cell size, the
         decode's own scale), 0 where the ray meets nothing.  The cameras of a future frame are the current frame's, by the
         rigid-rig assumption of vidar_amd.forecast.pix2vox.
@@ -354,11 +370,14 @@ class ViDARHeadBase(ViDARHeadTemplate):
         return torch.stack(out)
 
     def _camera_marches(self, pred_dict, img_metas, tgt_bev_h, tgt_bev_w, tgt_pc_range, cameras, stride):
-        """per sample, the arguments of a ray_ops.*_cam call on render_cameras' rays: ((sigma, pix2vox, hw), keywords)"""
+        """per sample, the arguments of a ray_ops.*_cam call on render_cameras' rays: ((sigma, pix2vox, hw), keywords);
+        cameras: indices, or None / "all" for every camera"""
         from ...forecast import pix2vox
         stride = int(stride)
         if stride < 1:
             raise ValueError("stride must be >= 1")
+        if isinstance(cameras, str) and cameras == "all":
+            cameras = None
         bev_preds = self._decode_preds(pred_dict).float()
         F_, inter_num, bs, token_num, Z = bev_preds.shape
         last = bev_preds[:, -1:]
@@ -380,7 +399,7 @@ class ViDARHeadBase(ViDARHeadTemplate):
     def render_rays(self, pred_dict, directions=None, end_points=None, *, tgt_bev_h, tgt_bev_w, tgt_pc_range,
                     img_metas=None, start_idx=0, batched_origin_points=None, return_stats=False):
         """The decode of get_point_cloud_prediction along rays handed in instead of taken from `gt_points`: the same
-        origin, voxel mapping, ray_argmax call and masking, because it IS that call.  Exactly one of
+        origin, voxel mapping, ray_argmax call and masking, because both take their rays from _decode_rays.  Exactly one of
           directions [R, 3]: unit directions in every predicted frame's own sensor coordinates, shared by all samples
                              and frames (vidar_amd.forecast.lidar_pattern); the ray's end point is the point 1 m out;
           end_points list[bs] of [N, >=4]: points in the layout of gt_points (xyz first, the frame label last).
@@ -391,11 +410,14 @@ class ViDARHeadBase(ViDARHeadTemplate):
         of [n, 4], row for row the points' (p_max, mean, rms, entropy), mean and rms in metres; a ray without a live
         waypoint has four zeros."""
         end_points = self._listed_end_points(pred_dict, directions, end_points)
-        if return_stats:
-            pred_dict = dict(pred_dict, **{_STATS_KEY: True})
-        out = self.get_point_cloud_prediction(pred_dict, end_points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range,
-                                              img_metas=img_metas, batched_origin_points=batched_origin_points)
-        return (out["pred_pcds"], out["pred_stats"]) if return_stats else out["pred_pcds"]
+        rays = self._decode_rays(pred_dict, end_points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range, img_metas,
+                                 batched_origin_points)
+        pred, gt, stats = self._decode_dists(ray_ops.ray_stats if return_stats else ray_ops.ray_argmax, rays)
+        points = self.get_rendered_pcds(rays.origin_pts, rays.xyz, rays.tindex, gt, pred, tgt_pc_range)
+        if not return_stats:
+            return points
+        return points, self.get_rendered_stats(rays.xyz, rays.tindex, gt, _metre_stats(stats[0], rays.scale),
+                                               tgt_pc_range, rays.origin_pts.shape[1])
 
     def _listed_end_points(self, pred_dict, directions, end_points):
         """render_rays' rays in the layout of gt_points: the end points as they are, or the points 1 m out along
@@ -426,14 +448,12 @@ class ViDARHeadBase(ViDARHeadTemplate):
         total = None
         if listed:
             end_points = self._listed_end_points(pred_dict, directions, end_points)
-            total = self.get_point_cloud_prediction(
-                dict(pred_dict, **{_OCC_KEY: True}), end_points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range,
-                img_metas=img_metas, batched_origin_points=batched_origin_points)
+            rays = self._decode_rays(pred_dict, end_points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range, img_metas,
+                                     batched_origin_points)
+            total = self._evidence(self._march(ray_ops.ray_occupancy, rays))
         if cameras is not None:
-            cams = None if isinstance(cameras, str) and cameras == "all" else cameras
-            cam = torch.stack([torch.stack(ray_ops.ray_occupancy_cam(*args, **kw), 1) for args, kw in
-                               self._camera_marches(pred_dict, img_metas, tgt_bev_h, tgt_bev_w, tgt_pc_range, cams,
-                                                    stride)])
+            cam = self._evidence(ray_ops.ray_occupancy_cam(*args, **kw) for args, kw in self._camera_marches(
+                pred_dict, img_metas, tgt_bev_h, tgt_bev_w, tgt_pc_range, cameras, stride))
             total = cam if total is None else total + cam
         return total
 
@@ -445,6 +465,8 @@ class ViDARHeadBase(ViDARHeadTemplate):
         get_point_cloud_prediction decodes (the same origin, voxel mapping, nan_to_num and tindex), so the grids compare
         cell for cell with render_occupancy(end_points=gt_points); pred_dict only gives the grid its shape and frames.
         vidar_amd.forecast.occupancy_score holds the two against each other."""
-        return self.get_point_cloud_prediction(
-            dict(pred_dict, **{_MEAS_KEY: True}), gt_points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range,
-            img_metas=img_metas, batched_origin_points=batched_origin_points)
+        rays = self._decode_rays(pred_dict, gt_points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range, img_metas,
+                                 batched_origin_points)
+        return self._evidence(self._march(
+            lambda sigma, origin, pts, tindex, step, K: ray_ops.sweep_evidence(origin, pts, tindex, rays.shape, step, K),
+            rays))

@@ -126,21 +126,16 @@ class ViDARHeadV1(ViDARHeadBase):
 
     def frame_alignment(self, valid_frames, img_metas):
         """[bs, F, 4, 4] fp64, row-vector form: frame slot f's own LiDAR coordinates -> the coordinates its decoded
-        volume lives in; the transform get_point_cloud_prediction applies to the rays (source = target frame, so the
+        volume lives in; the transform _decode_points applies to the rays (source = target frame, so the
         identity up to the rounding of the stored pair of inverse matrices)."""
         frames = np.array(valid_frames) + self.history_queue_length
         return np.array([[np.asarray(m["total_cur2ref_lidar_transform"][t], dtype=np.float64)
                           @ np.asarray(m["total_ref2cur_lidar_transform"][t], dtype=np.float64) for t in frames]
                          for m in img_metas])
 
-    def get_point_cloud_prediction(self, pred_dict, gt_points, start_idx, tgt_bev_h, tgt_bev_w,
-                                   tgt_pc_range, img_metas=None, batched_origin_points=None, as_rays=False):
-        pred_dict = dict(pred_dict, next_bev_preds=self._decode_preds(pred_dict))
-        valid_frames = np.array(pred_dict["valid_frames"])
-        gt, origin = self._get_reference_gt_points(
-            gt_points, src_frame_idx_list=valid_frames + self.history_queue_length,
-            tgt_frame_idx_list=valid_frames + self.history_queue_length, img_metas=img_metas)
-        return super().get_point_cloud_prediction(
-            pred_dict=pred_dict, gt_points=gt, start_idx=start_idx, tgt_bev_h=tgt_bev_h,
-            tgt_bev_w=tgt_bev_w, tgt_pc_range=tgt_pc_range, img_metas=img_metas,
-            batched_origin_points=origin, as_rays=as_rays)
+    def _decode_points(self, pred_dict, points, batched_origin_points, img_metas):
+        """every frame's points in that frame's own coordinates (source = target frame), relabelled as frame slots; the
+        origins are the transform's (:222-250)"""
+        frames = np.array(pred_dict["valid_frames"]) + self.history_queue_length
+        return self._get_reference_gt_points(points, src_frame_idx_list=frames, tgt_frame_idx_list=frames,
+                                             img_metas=img_metas)

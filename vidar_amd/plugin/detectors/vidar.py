@@ -417,8 +417,7 @@ class ViDAR(nn.Module):
             out["sweep"] = [[p[k] for p, k in zip(per, ks)] for per, ks in zip(sweep, keep)]
             out["sweep_index"] = [[k.nonzero().squeeze(-1) for k in ks] for ks in keep]
         if cameras is not None:
-            cams = None if isinstance(cameras, str) and cameras == "all" else cameras
-            depth = self.future_pred_head.render_cameras(pred_dict, cur_metas, cameras=cams, stride=stride, **geom,
+            depth = self.future_pred_head.render_cameras(pred_dict, cur_metas, cameras=cameras, stride=stride, **geom,
                                                          **more)
             if stats:
                 depth, out["depth_stats"] = depth
