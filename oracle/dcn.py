@@ -2,7 +2,8 @@
 
 mmcv-full 1.4.0 (`mmcv.ops.modulated_deform_conv2d`) is third party and neither vendored in
 /root/reference nor installable here; this restates its published semantics with F.grid_sample
-(align_corners=True maps pixel centres exactly; zero padding == the op's per-corner bounds checks).
+(align_corners=True maps pixel centres exactly; zero padding == the op's per-corner bounds checks, and the op's
+whole-tap check `h > -1 && w > -1 && h < H && w < W` is restated explicitly: it decides the derivative AT -1).
 offset [N,2K,Ho,Wo] holds (dy,dx) per tap, mask [N,K,Ho,Wo].
 PINNED (round 5) as far as reference-held code reaches: the SAMPLER (bilinear taps, zero padding, base
 position, stride / padding / dilation, modulation, and all three gradients) equals the reference's
@@ -28,6 +29,11 @@ def modulated_deform_conv2d(x, offset, mask, weight, bias=None, stride=1, paddin
         w = xs + j * dilation + offset[:, 2 * t + 1]
         grid = torch.stack((2 * w / max(W - 1, 1) - 1, 2 * h / max(H - 1, 1) - 1), -1)
         s = F.grid_sample(x, grid, mode="bilinear", padding_mode="zeros", align_corners=True)
+        # the op's bounds check (`h > -1 && w > -1 && h < H && w < W`, else the tap contributes nothing): values agree with
+        # zero padding everywhere, but AT -1 exactly (a zero offset on a padded border tap) grid_sample returns the one-sided
+        # derivative towards the image where the op returns zero
+        inside = (h > -1) & (w > -1) & (h < H) & (w < W)
+        s = torch.where(inside.unsqueeze(1), s, torch.zeros_like(s))
         s = s * mask[:, t:t + 1]
         out = out + torch.einsum("oc,nchw->nohw", weight[:, :, i, j], s)
     if bias is not None:

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import grad_parity as GP
 from test_reader_cpu import _mini_nuscenes
 
 pytestmark = pytest.mark.gpu
@@ -66,6 +67,9 @@ def test_disk_dataset_feeds_the_hip_step_and_matches_the_oracle_step(tmp_path):
     num = sum(float(((a.cpu() - b) ** 2).sum()) for a, b in zip(grads, ref_grads))
     den = sum(float((b ** 2).sum()) for b in ref_grads)
     assert (num / den) ** 0.5 < 1e-2, f"relative gradient error {(num / den) ** 0.5:.2e}"
+    # ... and per parameter tensor: the backbone holds too little of the whole gradient's norm for the aggregate to see it
+    bad = GP.compare([n for n, p in model.named_parameters() if p.requires_grad], grads, ref_grads, GP.COEFF, what="disk dataset step")
+    assert not bad, GP.report(bad)
     # checkpoint bridge: mmcv layout out, strict key-for-key load into a fresh model, same losses
     path = save_checkpoint(model, tmp_path / "epoch_1.pth", meta=dict(epoch=1, iter=7))
     torch.manual_seed(5)

@@ -10,13 +10,13 @@ from oracle import dcn as D
 pytestmark = pytest.mark.gpu
 
 
-def _fwd_bwd(N, C, Cout, H, W, stride, kh=3, kw=3, pad=1, dil=1):
+def _fwd_bwd(N, C, Cout, H, W, stride, kh=3, kw=3, pad=1, dil=1, sigma=1.5):
     from vidar_amd.plugin.backbones import modulated_deform_conv2d
     g = torch.Generator().manual_seed(N * 100 + C)
     K = kh * kw
     Ho = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1; Wo = (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
     x = torch.randn(N, C, H, W, generator=g, dtype=torch.float64)
-    off = torch.randn(N, 2 * K, Ho, Wo, generator=g, dtype=torch.float64) * 1.5     # leaves the image at borders
+    off = torch.randn(N, 2 * K, Ho, Wo, generator=g, dtype=torch.float64) * sigma   # leaves the image at borders
     mask = torch.rand(N, K, Ho, Wo, generator=g, dtype=torch.float64)
     wgt = torch.randn(Cout, C, kh, kw, generator=g, dtype=torch.float64) * 0.2
     bias = torch.randn(Cout, generator=g, dtype=torch.float64)
@@ -35,9 +35,20 @@ def _fwd_bwd(N, C, Cout, H, W, stride, kh=3, kw=3, pad=1, dil=1):
 
 @pytest.mark.parametrize("N,C,Cout,H,W,stride", [(2, 8, 6, 9, 11, 1), (1, 16, 16, 12, 10, 2), (1, 3, 4, 5, 5, 1),
                                                  (2, 40, 8, 58, 100, 1),       # stage-3 feature map size
-                                                 (1, 20, 4, 6, 2, 1)])         # narrowest image of the pair-load kernels
+                                                 (1, 20, 4, 6, 2, 1),          # narrowest image of the pair-load kernels
+                                                 # ResNet101 stage 3 / 4 widths on the maps of a 96 x 160 image: the
+                                                 # kernel calls of tests/test_step_backbone_gpu.py, both stride-2 blocks
+                                                 (1, 256, 8, 12, 20, 2), (1, 256, 8, 6, 10, 1), (1, 512, 8, 6, 10, 2),
+                                                 (1, 512, 8, 3, 5, 1)])
 def test_dcn_fwd_bwd(N, C, Cout, H, W, stride):
     _fwd_bwd(N, C, Cout, H, W, stride)
+
+
+@pytest.mark.parametrize("H,W,stride", [(2, 2, 1), (4, 4, 2)])
+def test_dcn_fwd_bwd_zero_offsets_border_taps_at_minus_one(H, W, stride):
+    """a zero-initialised conv_offset on ResNet101 stage 4 of a 64 x 64 image (tests/test_data_bridge_gpu.py): every padded
+    border tap sits AT -1, outside by the op's `h > -1 && w > -1` check -- no value, no offset / mask gradient"""
+    _fwd_bwd(2, 512, 8, H, W, stride, sigma=0.0)
 
 
 @pytest.mark.parametrize("kh,kw,pad,dil", [(2, 3, 1, 1), (3, 3, 2, 2)])
@@ -109,7 +120,8 @@ def test_im2col_far_and_nan_offsets_contribute_nothing():
 
 
 @pytest.mark.parametrize("N,C,H,W,stride", [(2, 19, 9, 11, 1), (1, 32, 29, 50, 1), (2, 5, 12, 10, 2),
-                                            (2, 19, 5, 1, 1)])              # one column
+                                            (2, 19, 5, 1, 1),               # one column
+                                            (1, 512, 3, 5, 1)])             # ResNet101 stage 4 of a 96 x 160 image
 def test_col2im_gather_equals_atomic_scatter(N, C, H, W, stride):
     """both grad_x strategies of vidar_dcn_col2im_f32 (workspace / reverse-map gather vs atomics)"""
     from vidar_amd.plugin.backbones import dcn_col2im
@@ -193,7 +205,8 @@ def test_fused_stem_pool_matches_two_kernel_path(shape):
     assert stem_bn_relu_pool(x.requires_grad_(), bn) is None           # gradients needed -> the caller's two-kernel path
 
 
-@pytest.mark.parametrize("N,C,H,W,std", [(2, 40, 58, 100, 1.5), (1, 33, 29, 50, 4.0), (1, 16, 9, 70, 8.0), (3, 5, 7, 3, 1.0)])
+@pytest.mark.parametrize("N,C,H,W,std", [(2, 40, 58, 100, 1.5), (1, 33, 29, 50, 4.0), (1, 16, 9, 70, 8.0), (3, 5, 7, 3, 1.0),
+                                         (1, 512, 3, 5, 1.5)])          # ResNet101 stage 4 of a 96 x 160 image
 def test_col2im_lds_window_gather_equals_global_gather(N, C, H, W, std):
     """the two grad_x gathers of 3x3 / stride 1 layers (vidar_dcn_set_variant): per-tap LDS window of grad_cols + global
     loads for sources beyond the 4-pixel halo (std 4 / 8: most of them) against 4-byte global gathers everywhere; NaN and

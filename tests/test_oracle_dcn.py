@@ -14,14 +14,25 @@ from oracle import dcn as D
 
 @pytest.mark.parametrize("N,C,H,W,stride,pad,dil", [(2, 5, 9, 11, 1, 1, 1), (1, 4, 10, 13, 2, 1, 1), (1, 3, 8, 8, 1, 2, 2)])
 def test_dcnv2_sampler_matches_reference_dcnv3_kernels(N, C, H, W, stride, pad, dil, ref_modules):
-    ref = ref_modules("ref_dcnv3")
+    _sampler_against_reference(ref_modules("ref_dcnv3"), N, C, H, W, stride, pad, dil, 1.5)
+
+
+@pytest.mark.parametrize("H,W,stride", [(2, 2, 1), (4, 4, 2), (3, 5, 1)])
+def test_zero_offsets_put_border_taps_at_minus_one_exactly(H, W, stride, ref_modules):
+    """zero-initialised conv_offset: the padded border taps sit AT -1, where the kernels' `h > -1 && w > -1` check makes the
+    tap contribute nothing -- no value and no offset gradient -- while plain zero padding has the one-sided derivative
+    towards the image.  The maps of ResNet101 stage 4 on a 64 x 64 image (2 x 2, and 4 x 4 into its stride-2 block)."""
+    _sampler_against_reference(ref_modules("ref_dcnv3"), 2, 3, H, W, stride, 1, 1, 0.0)
+
+
+def _sampler_against_reference(ref, N, C, H, W, stride, pad, dil, sigma):
     k = 3
     K = k * k
     Ho = (H + 2 * pad - (dil * (k - 1) + 1)) // stride + 1
     Wo = (W + 2 * pad - (dil * (k - 1) + 1)) // stride + 1
     g = torch.Generator().manual_seed(N * 100 + H)
     x = torch.randn(N, C, H, W, generator=g, dtype=torch.float64, requires_grad=True)
-    offset = (torch.randn(N, 2 * K, Ho, Wo, generator=g, dtype=torch.float64) * 1.5).requires_grad_(True)
+    offset = (torch.randn(N, 2 * K, Ho, Wo, generator=g, dtype=torch.float64) * sigma).requires_grad_(True)
     mask = torch.rand(N, K, Ho, Wo, generator=g, dtype=torch.float64, requires_grad=True)
     weight = torch.zeros(C, C, k, k, dtype=torch.float64)
     weight[torch.arange(C), torch.arange(C)] = 1.0                       # identity on every tap
