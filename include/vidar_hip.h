@@ -505,6 +505,32 @@ int vidar_sweep_evidence_f32(const float* origin, const float* pts, const float*
                              int F, int R, int Z, int Y, int X, int K, float step,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* The occupancy query (csrc/ray_march.hip, point_occupancy_body; the weights in csrc/occ_at_math.h): the decode's softmax
+ * asked about ONE place on a ray instead of being scattered over all of them.  Rays, waypoints, sampler and the live rule
+ * are those of vidar_ray_stats_f32; the ray runs from origin[f] through its end point q, L = |q - o| in fp32.  Waypoint k
+ * owns the stretch [k step, (k + 1) step) of the ray, the query [L - extent/2, L + extent/2] (extent in voxel units).  With
+ * p_k = e_k / S over the live waypoints,
+ *   c_near(k) = clamp((L - extent/2 - k step) / step, 0, 1)      c_far(k) = clamp((L + extent/2 - k step) / step, 0, 1)
+ *   hit  = sum p_k (c_far(k) - c_near(k))      the return lies in the query's stretch
+ *   free = sum p_k (1 - c_far(k))              the return lies beyond it: the ray passed the query
+ * Both are sums of non-negative terms; hit + free = sum p_k (1 - c_near(k)) in [0, 1] is the mass the ray has not spent
+ * before the query; both are continuous and piecewise linear in L.  A skipped ray, a ray without a live waypoint and
+ * q == o (a NaN direction: every waypoint dead) give two zeros; a query with L - extent/2 >= K step gives exact zeros.
+ * +inf or NaN logits may give non-finite output.
+ *   vidar_point_occupancy_f32: listed end points, origin [F,3], pts [R,3], tindex [R] -> out [R,2] = (hit, free);
+ *   vidar_voxel_occupancy_f32: one ray per voxel (f, z, y, x) through its centre (x + 0.5, y + 0.5, z + 0.5), never
+ *     stored -> hit, free [F,Z,Y,X]; the listed form's bits on the same end points.  The grids read like
+ *     vidar_ray_occupancy_f32's, with the evidence hit + free a probability instead of a count of waypoints.
+ * fp32 sums in a fixed order, no atomics, no workspace: equal inputs give equal bits in every mode, and K == 512 gives
+ * the same bits through the streamed kernels.  VIDAR_ERR_BAD_ARG before any HIP call: K outside 1..vidar_ray_max_k(),
+ * non-positive Z, Y, X, F <= 0 (the per-voxel form: F < 0, or F*Z*Y*X beyond the 32-bit ray index), R < 0, an extent that
+ * is not finite and > 0, a NULL pointer with work to do.  R == 0 (the per-voxel form: F == 0) returns 0 and writes nothing. */
+int vidar_point_occupancy_f32(const float* sigma, const float* origin, const float* pts, const float* tindex,
+                              float* out /*[R,2] hit, free*/, int F, int R, int Z, int Y, int X, int K, float step,
+                              float extent, void* stream);
+int vidar_voxel_occupancy_f32(const float* sigma, const float* origin, float* hit /*[F,Z,Y,X]*/, float* free_,
+                              int F, int Z, int Y, int X, int K, float step, float extent, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Occupancy score (csrc/occ_score.hip, per-voxel decisions in csrc/occ_score_math.h): a predicted evidence grid held
  * against a measured one, for S segments -- (sample, frame) pairs -- at once.

@@ -15,8 +15,9 @@ the depth picture) also
     sweep_stats_{i}_{k}.npy  [n, 4] float32, row for row with sweep_{i}_{k}.npy: peak probability, mean depth (m), spread
                              about the decoded depth (m) and entropy (nats) of the softmax along the ray
     conf_{i}_{k}_cam{c}.png  the peak probability of camera c's pixels over the same frame (blue = 0 .. red = 1)
-with --occupancy [sweep|cameras|both] (the rays that are marched: the sweep's, the cameras' at --stride, or both; --min-evidence
-E is the floor under hit + free, default 0.5 waypoints) also
+with --occupancy [sweep|cameras|both|dense] (the rays that are marched: the sweep's, the cameras' at --stride, both, or one
+ray per voxel through its centre; --min-evidence E is the floor under hit + free, default 0.5 -- waypoints of the marched
+rays, or with dense the probability the voxel's own ray still has when it reaches the voxel) also
     occ_{i}_{k}.npy          [Z, H, W] float32: hit / (hit + free) of the forecast volume's voxels, NaN = never seen or
                              occluded (ViDAR.forecast(occupancy=...), vidar_amd.forecast.occupancy_grid)
     occ_bev_{i}_{k}.png      its bird's-eye picture: the most occupied seen voxel of every column, free white, occupied
@@ -69,10 +70,12 @@ def main(argv=None):
     ap.add_argument("--stats", action="store_true", help="also write the decode's confidence (sweep_stats_*, conf_*)")
     ap.add_argument("--min-prob", type=float, metavar="P", help="drop rays whose peak probability is below P")
     ap.add_argument("--max-rms", type=float, metavar="M", help="drop rays whose spread about the depth exceeds M metres")
-    ap.add_argument("--occupancy", nargs="?", const="sweep", choices=["sweep", "cameras", "both"],
-                    help="also write the occupancy grid (occ_*, occ_bev_*) from the sweep's rays, the cameras' or both")
+    ap.add_argument("--occupancy", nargs="?", const="sweep", choices=["sweep", "cameras", "both", "dense"],
+                    help="also write the occupancy grid (occ_*, occ_bev_*) from the sweep's rays, the cameras', both, or "
+                         "from one ray per voxel (dense)")
     ap.add_argument("--min-evidence", type=float, default=0.5, metavar="E",
-                    help="a voxel with hit + free below E waypoints is unseen (NaN)")
+                    help="a voxel with hit + free below E is unseen (NaN): E waypoints of the marched rays, or with "
+                         "--occupancy dense the probability the voxel's own ray still has when it gets there")
     args = ap.parse_args(argv)
     if args.occupancy in ("cameras", "both") and args.no_depth:
         raise SystemExit("--occupancy cameras / both marches the cameras' rays: drop --no-depth")

@@ -1285,9 +1285,118 @@ def bench_occ_score(which):
                   f"{r['counts_equal_torch']} |\n" for r in score_rows))
 
 
+def bench_voxel_occupancy(which):
+    """the dense occupancy query (vidar_voxel_occupancy_f32: one ray per voxel) on a 16 x 200 x 200 volume, step 1, at
+    K = 512 (register form) and K = 1026 (streamed), one frame and seven.  In the same process, the ops alternating:
+      * ray_stats and point_occupancy on the same 640 000 rays per frame materialised as listed end points -- the same two
+        visits of every waypoint, plus 12 bytes of end point read and 16 (ray_stats) / 8 bytes stored per ray;
+      * what users run today, one frame: ray_occupancy on the 34 560 rays of vidar_amd.forecast.lidar_pattern() and
+        ray_occupancy_cam on 6 cameras of 900 x 1600 pixels at strides 8 and 4 (default mode: fp32 atomics),
+    and under every source the count of voxels whose evidence hit + free reaches 0.5 (the two evidences have different
+    units: a probability for the dense form, waypoints for the splat).  HIP events, three repeats of 2 warm-up + 5 timed
+    calls; the spread is (max - min) / median over the repeats.  Writes profiles/kbench_voxel_occupancy.md."""
+    from vidar_amd import forecast as FC
+    from vidar_amd.plugin.dense_heads.ray_ops import (point_occupancy, ray_occupancy, ray_occupancy_cam, ray_stats,
+                                                      voxel_occupancy)
+    from vidar_amd.synthetic import PC_RANGE, camera_matrices
+    dev = torch.device("cuda", 0)
+    Z, Y, X, C, H, W = 16, 200, 200, 6, 900, 1600
+    med = lambda v: float(np.median(v))
+    spread = lambda v: (max(v) - min(v)) / med(v)
+    seen = lambda hit, free: int((hit + free >= 0.5).sum())
+    touched = lambda hit, free: int((hit + free > 0).sum())
+    rows, splat_rows = [], []
+
+    def times(fns, it=5):
+        ts = {name: [] for name in fns}
+        for _ in range(3):
+            for name, fn in fns.items():
+                ts[name].append(timeit(fn, warm=2, it=it))
+        return ts
+
+    for F_ in (1, 7):
+        sigma = torch.randn(F_, Z, Y, X, generator=torch.Generator().manual_seed(0)).to(dev)
+        o = torch.tensor([[X / 2.0, Y / 2.0, Z / 4.0]], device=dev).repeat(F_, 1)
+        z, y, x = torch.meshgrid(torch.arange(Z, device=dev), torch.arange(Y, device=dev), torch.arange(X, device=dev),
+                                 indexing="ij")
+        p = (torch.stack([x, y, z], -1).reshape(-1, 3).float() + 0.5).repeat(F_, 1)
+        ti = torch.arange(F_, device=dev).repeat_interleave(Z * Y * X).float()
+        for K in (512, 1026):
+            hit, free = voxel_occupancy(sigma, o, 1.0, K)
+            listed = point_occupancy(sigma, o, p, ti, 1.0, K)
+            same = bool(torch.equal(torch.stack([hit.reshape(-1), free.reshape(-1)], 1), listed))
+            ts = times({"voxel_occupancy": lambda: voxel_occupancy(sigma, o, 1.0, K),
+                        "ray_stats": lambda: ray_stats(sigma, o, p, ti, 1.0, K),
+                        "point_occupancy": lambda: point_occupancy(sigma, o, p, ti, 1.0, K)})
+            t, ts_stats = med(ts["voxel_occupancy"]), med(ts["ray_stats"])
+            row = dict(F=F_, R=p.shape[0], K=K, form="register" if K == 512 else "streamed",
+                       voxel_occupancy_ms=[round(v, 3) for v in ts["voxel_occupancy"]], voxel_occupancy_median_ms=round(t, 3),
+                       voxel_occupancy_spread=round(spread(ts["voxel_occupancy"]), 4),
+                       ray_stats_median_ms=round(ts_stats, 3), ray_stats_spread=round(spread(ts["ray_stats"]), 4),
+                       point_occupancy_median_ms=round(med(ts["point_occupancy"]), 3),
+                       point_occupancy_spread=round(spread(ts["point_occupancy"]), 4),
+                       dense_over_ray_stats=round(t / ts_stats, 4), equals_point_form=same,
+                       voxels=hit.numel(), voxels_seen=seen(hit, free), voxels_touched=touched(hit, free), ns_per_ray=round(t * 1e6 / p.shape[0], 2))
+            rows.append(row)
+            report("voxel_occupancy", t, **row)
+        del p, ti
+
+    sigma = torch.randn(1, Z, Y, X, generator=torch.Generator().manual_seed(0)).to(dev)
+    o = torch.tensor([[X / 2.0, Y / 2.0, Z / 4.0]], device=dev)
+    sweep = o + FC.lidar_pattern().to(dev)
+    ti = torch.zeros(sweep.shape[0], device=dev)
+    m = FC.pix2vox(camera_matrices(img_hw=(H, W))[:C], PC_RANGE, Y, X, Z).to(dev)
+    for K in (512, 1026):
+        dense = next(r for r in rows if r["F"] == 1 and r["K"] == K)
+        sources = [("sweep", "-", sweep.shape[0], lambda: ray_occupancy(sigma, o, sweep, ti, 1.0, K))]
+        for stride in (8, 4):
+            Hs, Ws = -(-H // stride), -(-W // stride)
+            geom = ((Hs, Ws), stride / 2.0, stride / 2.0, float(stride), float(stride))
+            sources.append(("camera", stride, C * Hs * Ws, lambda geom=geom: ray_occupancy_cam(sigma, m, *geom, 1.0, K)))
+        for name, stride, R, fn in sources:
+            hit, free = fn()
+            ts = times({"splat": fn})["splat"]
+            row = dict(rays=name, stride=stride, R=R, K=K, splat_ms=[round(v, 3) for v in ts], splat_median_ms=round(med(ts), 3),
+                       splat_spread=round(spread(ts), 4), voxels_seen=seen(hit, free), voxels_touched=touched(hit, free),
+                       seen_per_ms=round(seen(hit, free) / med(ts)), dense_median_ms=dense["voxel_occupancy_median_ms"],
+                       dense_voxels_seen=dense["voxels_seen"], dense_voxels_touched=dense["voxels_touched"],
+                       dense_seen_per_ms=round(dense["voxels_seen"] / dense["voxel_occupancy_median_ms"]))
+            splat_rows.append(row)
+            report("voxel_occupancy_vs_splat", med(ts), **row)
+    out = os.environ.get("VIDAR_KBENCH_OUT")
+    path = Path(out) if out else ROOT / "profiles" / "kbench_voxel_occupancy.md"
+    path.write_text(
+        "# The dense occupancy query on an MI355X: `python tools/kbench.py voxel_occupancy`\n\n"
+        f"Volume F x {Z} x {Y} x {X}, random-normal logits (seed 0), step 1, every origin at the volume's centre, extent 1.\n"
+        "`voxel_occupancy` (`vidar_voxel_occupancy_f32`) marches one ray per voxel and never stores the rays; `ray_stats`\n"
+        "(`vidar_ray_stats_f32`) and `point_occupancy` (`vidar_point_occupancy_f32`) march the same rays materialised as listed\n"
+        "end points.  K = 512 runs the register form, K = 1026 the streamed one.  HIP events, the ops alternating, 3 repeats\n"
+        "of 2 warm-up + 5 timed calls; spread = (max - min) / median.  Each call allocates its outputs.  `seen` = voxels with\n"
+        "hit + free >= 0.5, `touched` = voxels with hit + free > 0 (an answer at a floor of 0).\n\n"
+        "```\n" + json.dumps({"device": torch.cuda.get_device_name(0)}) + "\n"
+        + "\n".join(json.dumps(dict(op="voxel_occupancy", **r)) for r in rows) + "\n"
+        + "\n".join(json.dumps(dict(op="voxel_occupancy_vs_splat", **r)) for r in splat_rows) + "\n```\n\n"
+        "| F | R | K | voxel_occupancy ms (median) | spread | ray_stats ms | spread | point_occupancy ms | spread | dense / ray_stats | "
+        "equals the point form | seen | touched |\n|---|---|---|---|---|---|---|---|---|---|---|---|---|\n"
+        + "".join(f"| {r['F']} | {r['R']} | {r['K']} | {r['voxel_occupancy_median_ms']} | {r['voxel_occupancy_spread']} | "
+                  f"{r['ray_stats_median_ms']} | {r['ray_stats_spread']} | {r['point_occupancy_median_ms']} | "
+                  f"{r['point_occupancy_spread']} | {r['dense_over_ray_stats']} | {r['equals_point_form']} | "
+                  f"{r['voxels_seen']} of {r['voxels']} | {r['voxels_touched']} |\n" for r in rows)
+        + "\nWhat users run today, one frame, default mode (`ray_occupancy` on the rays of `vidar_amd.forecast.lidar_pattern()`,\n"
+        f"`ray_occupancy_cam` on {C} cameras of {H} x {W} pixels), next to the dense form at the same K.  The evidence units\n"
+        "differ -- waypoints of the rays that happened to pass for the splat, the probability the voxel's own ray still has for\n"
+        "the dense form -- so `seen` compares answers given, not their quality.\n\n"
+        "| rays | stride | R | K | splat ms (median) | spread | touched | seen | seen / ms | dense ms | dense touched | dense seen | "
+        "dense seen / ms |\n|---|---|---|---|---|---|---|---|---|---|---|---|---|\n"
+        + "".join(f"| {r['rays']} | {r['stride']} | {r['R']} | {r['K']} | {r['splat_median_ms']} | {r['splat_spread']} | "
+                  f"{r['voxels_touched']} | {r['voxels_seen']} | {r['seen_per_ms']} | {r['dense_median_ms']} | "
+                  f"{r['dense_voxels_touched']} | {r['dense_voxels_seen']} | "
+                  f"{r['dense_seen_per_ms']} |\n" for r in splat_rows))
+
+
 if __name__ == "__main__":
     import os
-    if os.environ.get("VIDAR_MSDA_ITEM_ORDER") is not None:          # A/B of the gather kernels' item order (0 banded, 1 head-major)
+    if os.environ.get("VIDAR_MSDA_ITEM_ORDER") is not None:         # A/B of the gather kernels' item order (0 banded, 1 head-major)
         from vidar_amd._lib import lib
         lib().vidar_msda_set_item_order(int(os.environ["VIDAR_MSDA_ITEM_ORDER"]))
     if os.environ.get("VIDAR_GEMM_VARIANT") is not None:               # A/B of the GEMM kernel's structure (0 classic, 1 / 2 wave-specialised)

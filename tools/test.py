@@ -77,10 +77,14 @@ def main(argv=None):
                     help="with --occupancy-metrics: the thresholds on the predicted occupancy (1 to 8; default 0.25 0.5)")
     ap.add_argument("--min-evidence", type=float, metavar="E",
                     help="with --occupancy-metrics: floor on the predicted evidence of a scored voxel (default 0.5)")
+    ap.add_argument("--occ-source", choices=["rays", "dense"], default="rays",
+                    help="with --occupancy-metrics: the predicted evidence comes from the measured sweep's own ray "
+                         "directions (rays) or from one ray per voxel, the grid forecast(occupancy=\"dense\") returns (dense)")
     args = ap.parse_args(argv)
     if args.occupancy_metrics:
         from vidar_amd.plugin.utils import eval_utils
-        eval_utils.set_occupancy_metrics(True, thresholds=args.occ_thresholds, min_evidence=args.min_evidence)
+        eval_utils.set_occupancy_metrics(True, source=args.occ_source, thresholds=args.occ_thresholds,
+                                         min_evidence=args.min_evidence)
     if args.device_metrics:
         from vidar_amd.plugin.utils import eval_utils
         eval_utils.set_device_metrics(True)

@@ -114,6 +114,8 @@ _ABI = {
     "vidar_ray_occupancy_f32": "i 6p 6i f p z p",
     "vidar_ray_occupancy_cam_f32": "i 4p 4i 4f 4i f p z p",
     "vidar_sweep_evidence_f32": "i 5p 6i f p z p",
+    "vidar_point_occupancy_f32": "i 5p 6i 2f p",
+    "vidar_voxel_occupancy_f32": "i 4p 5i 2f p",
     "vidar_occ_score_workspace_bytes": "i 4i p",
     "vidar_occ_score_f32": "i 4p 4i 3f p z p",
     "vidar_gemm_f32": "i p l i p l i p l 4i 3l 2p i p 2l 3i 2p z p",

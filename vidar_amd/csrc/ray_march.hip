@@ -14,6 +14,9 @@
 //   ray_occupancy / ray_occupancy_cam : the decode's softmax scattered back onto the voxels, mass at / beyond every
 //                 waypoint (hit / free evidence of an occupancy grid; no counterpart in the reference)
 //   sweep_evidence : the same evidence of a MEASURED sweep -- rays with known returns, no volume is read
+//   point_occupancy / voxel_occupancy : the decode's softmax asked about one place on the ray -- the return lies at /
+//                 beyond the ray's end point -- for listed end points and for one ray per voxel through its centre
+//                 (occ_at_math.h; no scatter, no atomics)
 // The reference materialises ~8 arrays of [rays, 513] floats per call (waypoints, lengths, masks,
 // sampled logits, -inf masks, softmax); here one wave owns one ray, its 512 waypoints live in
 // registers (8 per lane) and only O(1) values per ray ever reach HBM.
@@ -49,6 +52,7 @@
 #include "det_scatter.h"
 #include "cam_ray.h"
 #include "occ_score_math.h"
+#include "occ_at_math.h"
 
 namespace {
 
@@ -84,6 +88,9 @@ struct CameraRays {       // ray r = pixel (f, c, y, x) of [F, C, Hs, Ws] throug
   const float* __restrict__ pix2vox;
   vidar_cam::CamGrid g;
 };
+struct VoxelRays {        // ray r = voxel (f, z, y, x) of the volume itself, x fastest: from origin[f] through the voxel's
+  const float* __restrict__ origin;   // centre (x + 0.5, y + 0.5, z + 0.5), exact in fp32.  No kTarget: only
+};                                    // point_occupancy_body marches these, and it reports no distance
 
 __device__ __forceinline__ void aim(Ray& ray) {
   const float rx = ray.px - ray.ox, ry = ray.py - ray.oy, rz = ray.pz - ray.oz;
@@ -108,6 +115,15 @@ __device__ __forceinline__ Ray load_ray(const CameraRays& s, int r, const VolDim
   const vidar_cam::CamRay c = vidar_cam::pixel_ray(s.pix2vox + (size_t)fc * 16, s.g, x, y);
   ray.ox = c.ox; ray.oy = c.oy; ray.oz = c.oz;
   ray.px = c.px; ray.py = c.py; ray.pz = c.pz;
+  aim(ray);
+  return ray;
+}
+__device__ __forceinline__ Ray load_ray(const VoxelRays& s, int r, const VolDims& v) {
+  Ray ray;
+  const int x = r % v.X, zy = r / v.X, y = zy % v.Y, fz = zy / v.Y, z = fz % v.Z;
+  ray.f = fz / v.Z;
+  ray.ox = s.origin[ray.f * 3 + 0]; ray.oy = s.origin[ray.f * 3 + 1]; ray.oz = s.origin[ray.f * 3 + 2];
+  ray.px = x + 0.5f; ray.py = y + 0.5f; ray.pz = z + 0.5f;
   aim(ray);
   return ray;
 }
@@ -455,6 +471,50 @@ __device__ __forceinline__ void ray_stats_body(
   }
 }
 
+// The occupancy query: the softmax of ray_stats_body (visits 1 and 2, live as there) asked about the ray's END POINT q.
+// With L = |q - o| (dist_to: the length aim divides by) and the weights of occ_at_math.h -- waypoint k owns
+// [k step, (k + 1) step) of the ray, the query [L - extent/2, L + extent/2] --
+//   hit = sum p_k w_hit(k)        the return lies in the query's stretch
+//   free = sum p_k w_free(k)      the return lies beyond it: the ray passed the query
+// both sums of non-negative terms, hit + free <= 1.  The two answers of ray r go to hit[r * stride] and free_[r * stride]:
+// stride 2 with free_ = hit + 1 is the listed form's [R,2], stride 1 the per-voxel form's two grids.  A skipped ray and a
+// ray without a live waypoint (q == o: the direction is NaN and every waypoint dead) give two zeros.  No atomics, no
+// workspace; +inf / NaN logits may give non-finite output.
+template <bool K512, class Src>
+__device__ __forceinline__ void point_occupancy_body(
+    const float* __restrict__ sigma, const Src& src, float* __restrict__ hit, float* __restrict__ free_, int stride,
+    int R, VolDims v, float step, float extent, int K) {
+  const int r = blockIdx.x * kRaysPerBlock + threadIdx.x / kWave;
+  if (r >= R) return;
+  const int lane = threadIdx.x % kWave;
+  const Ray ray = load_ray(src, r, v);
+  float o_hit = 0.f, o_free = 0.f;
+  if (ray.f >= 0) {
+    Waypoints<K512, false> w{sigma + (size_t)ray.f * v.Z * v.Y * v.X, ray, v, step, lane, K};
+    float m = kNegInf;
+    w.first([&](int, float z, float) { m = fmaxf(m, z); });
+    m = wave_max(m);
+    if (m != kNegInf) {                                    // a live waypoint; the same in every lane
+      const float L = dist_to(ray, ray.px, ray.py, ray.pz);
+      float se = 0.f, sh = 0.f, sf = 0.f;
+      w.second([&](int k, float z, float) {
+        if (z == kNegInf) return;
+        const float e = expf(z - m);
+        const vidar_occ_at::Weights c = vidar_occ_at::weights(L, extent, k, step);
+        se += e;
+        sh += e * c.hit;
+        sf += e * c.free;
+      });
+      se = wave_sum(se); sh = wave_sum(sh); sf = wave_sum(sf);
+      o_hit = sh / se; o_free = sf / se;
+    }
+  }
+  if (lane == 0) {
+    hit[(size_t)r * stride] = o_hit;
+    free_[(size_t)r * stride] = o_free;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // The backwards: d loss / d logit of every live entry, scattered through the entry's trilinear weights.
 // A Coef is built from what the forward saved for ray r and gives g * d loss_r / d logit of an entry with softmax
@@ -709,6 +769,22 @@ RAY_KERNEL ray_stats_cam_kernel(const float* __restrict__ sigma, CameraRays cam,
 RAY_KERNEL ray_stats_cam_any_kernel(const float* __restrict__ sigma, CameraRays cam, float* __restrict__ dist,
                                     float* __restrict__ stats, int R, VolDims v, float step, int K) {
   ray_stats_body<false>(sigma, cam, dist, nullptr, stats, R, v, step, K);
+}
+// the occupancy query at listed end points (out [R,2]) and at every voxel's centre (hit, free [F,Z,Y,X])
+RAY_KERNEL point_occupancy_kernel(RAY_IN, float* __restrict__ out, int R, VolDims v, float step, float extent) {
+  point_occupancy_body<true>(sigma, ListedRays{origin, pts, tindex}, out, out + 1, 2, R, v, step, extent, kK);
+}
+RAY_KERNEL point_occupancy_any_kernel(RAY_IN, float* __restrict__ out, int R, VolDims v, float step, float extent,
+                                      int K) {
+  point_occupancy_body<false>(sigma, ListedRays{origin, pts, tindex}, out, out + 1, 2, R, v, step, extent, K);
+}
+RAY_KERNEL voxel_occupancy_kernel(const float* __restrict__ sigma, VoxelRays vox, float* __restrict__ hit,
+                                  float* __restrict__ free_, int R, VolDims v, float step, float extent) {
+  point_occupancy_body<true>(sigma, vox, hit, free_, 1, R, v, step, extent, kK);
+}
+RAY_KERNEL voxel_occupancy_any_kernel(const float* __restrict__ sigma, VoxelRays vox, float* __restrict__ hit,
+                                      float* __restrict__ free_, int R, VolDims v, float step, float extent, int K) {
+  point_occupancy_body<false>(sigma, vox, hit, free_, 1, R, v, step, extent, K);
 }
 // what ray_argmax_cam_kernel marches, written out: origin [F,C,3], pts [F,C,Hs,Ws,3]; a thread per pixel
 __global__ __launch_bounds__(kThreads) void cam_rays_kernel(CameraRays cam, float* __restrict__ origin,
@@ -1023,6 +1099,34 @@ int vidar_sweep_evidence_f32(const float* origin, const float* pts, const float*
   if (rm_bad(F, R, Z, Y, X, K)) return VIDAR_ERR_BAD_ARG;
   return rm_sweep_evidence(ListedRays{origin, pts, tindex}, hit, free_, R, K, VolDims{F, Z, Y, X}, step, workspace,
                            workspace_bytes, (hipStream_t)stream);
+}
+
+int vidar_point_occupancy_f32(const float* sigma, const float* origin, const float* pts, const float* tindex,
+                              float* out, int F, int R, int Z, int Y, int X, int K, float step, float extent,
+                              void* stream) {
+  VIDAR_ENTER();
+  if (rm_bad(F, R, Z, Y, X, K) || vidar_occ_at::bad_extent(extent)) return VIDAR_ERR_BAD_ARG;
+  if (R == 0) return 0;
+  if (!sigma || !origin || !pts || !tindex || !out) return VIDAR_ERR_BAD_ARG;
+  VolDims v{F, Z, Y, X};
+  rm_launch(point_occupancy_kernel, point_occupancy_any_kernel, R, K, (hipStream_t)stream, sigma, origin, pts, tindex,
+            out, R, v, step, extent);
+  return vidar_last_error();
+}
+
+int vidar_voxel_occupancy_f32(const float* sigma, const float* origin, float* hit, float* free_, int F, int Z, int Y,
+                              int X, int K, float step, float extent, void* stream) {
+  VIDAR_ENTER();
+  // F == 0 is the empty problem here (the rays are the voxels); F*Z*Y*X must fit the 32-bit ray index
+  if (F < 0 || rm_bad(F ? F : 1, 0, Z, Y, X, K) || vidar_occ_at::bad_extent(extent)) return VIDAR_ERR_BAD_ARG;
+  VolDims v{F, Z, Y, X};
+  if ((uint64_t)F * (uint64_t)Z * (uint64_t)Y * (uint64_t)X > (uint64_t)0x7fffffff - kThreads) return VIDAR_ERR_BAD_ARG;
+  if (F == 0) return 0;
+  if (!sigma || !origin || !hit || !free_) return VIDAR_ERR_BAD_ARG;
+  const int R = (int)rm_cells(v);
+  rm_launch(voxel_occupancy_kernel, voxel_occupancy_any_kernel, R, K, (hipStream_t)stream, sigma, VoxelRays{origin}, hit,
+            free_, R, v, step, extent);
+  return vidar_last_error();
 }
 
 int vidar_cam_rays_f32(const float* pix2vox, float* origin, float* pts, int F, int C, int Hs, int Ws, float u0,

@@ -189,7 +189,9 @@ def occupancy_grid(hit, free, min_evidence=0.5):
     -> (occ, evidence), both of that shape: evidence = hit + free; occ = hit / evidence where evidence >= min_evidence,
     NaN elsewhere -- never seen, or occluded (every ray that came by had already spent its mass).
     Evidence is counted in waypoints: 1.0 is one waypoint of one ray wholly attributed to the voxel and certainly not
-    occluded; half of one is the default floor.  min_evidence is a parameter of the answer, not a tolerance.  A NaN
+    occluded; half of one is the default floor.  The grids of ray_ops.voxel_occupancy (one ray per voxel) read the same
+    way, with the evidence a probability in [0, 1] -- the softmax mass the voxel's own ray still has when it gets there --
+    and the floor a bound under that.  min_evidence is a parameter of the answer, not a tolerance.  A NaN
     evidence fails the floor (and 0 / 0 under a floor of 0 is NaN as well).  Pure torch, any device."""
     evidence = hit + free
     occ = torch.where(evidence >= float(min_evidence), hit / evidence, torch.full_like(evidence, float("nan")))

@@ -270,6 +270,34 @@ def sweep_evidence(origin, pts, tindex, shape, step=1.0, K=K_SAMPLES):
     return hit, free
 
 
+def point_occupancy(sigma, origin, pts, tindex, step=1.0, K=K_SAMPLES, extent=1.0):
+    """occupancy at listed points -> [R, 2] fp32 (hit, free), no grad: the decode's softmax along the ray from the origin
+    through pts[r], asked two questions about the stretch [L - extent/2, L + extent/2] of that ray (L = |pts[r] - origin|,
+    extent in voxel units): hit = the probability that the return lies in it, free = that it lies beyond it -- the ray
+    reached the point and went on.  hit + free <= 1 is the mass the ray still has when it gets there; two zeros for a
+    skipped ray, one without a live waypoint, and pts[r] == origin.  include/vidar_hip.h: vidar_point_occupancy_f32.
+    No atomics: equal inputs give equal bits in every mode."""
+    rays, dims, (out,) = _listed(sigma, origin, pts, tindex, (2,))
+    check(lib().vidar_point_occupancy_f32(*map(ptr, rays), ptr(out), *dims, int(K), step, float(extent),
+                                          stream_of(rays[0])), "point_occupancy")
+    return out
+
+
+def voxel_occupancy(sigma, origin, step=1.0, K=K_SAMPLES, extent=1.0):
+    """point_occupancy at every voxel's centre, one ray per voxel from its frame's origin [F,3] -> (hit, free), both
+    [F,Z,Y,X] fp32, no grad, the listed form's bits; the rays are never stored (vidar_voxel_occupancy_f32).  The grids
+    read like ray_occupancy's -- forecast.occupancy_grid(hit, free, min_evidence) -- with the evidence hit + free a
+    probability in [0, 1] instead of a count of waypoints, and they depend on no ray set."""
+    sigma, origin = _f(sigma.detach()), _f(origin)
+    F_, Z, Y, X = sigma.shape
+    if tuple(origin.shape) != (F_, 3) or origin.device != sigma.device:
+        raise ValueError(f"voxel_occupancy: origin must be [{F_},3] on sigma's device")
+    hit = torch.empty_like(sigma); free = torch.empty_like(sigma)
+    check(lib().vidar_voxel_occupancy_f32(ptr(sigma), ptr(origin), ptr(hit), ptr(free), F_, Z, Y, X, int(K), step,
+                                          float(extent), stream_of(sigma)), "voxel_occupancy")
+    return hit, free
+
+
 def cam_rays(pix2vox, hw, u0=0.5, v0=0.5, du=1.0, dv=1.0):
     """the rays ray_argmax_cam marches, written out: -> (origin [F,C,3], pts [F,C,Hs,Ws,3]) in voxel units."""
     pix2vox = _f(pix2vox)

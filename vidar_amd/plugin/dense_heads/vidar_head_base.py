@@ -299,7 +299,8 @@ class ViDARHeadBase(ViDARHeadTemplate):
                      batched_origin_points=None):
         """The one place that turns (pred_dict, points) into the rays a decode marches -> DecodeRays.  Which logits and
         which coordinates is the subclass's pair of hooks, _decode_preds and _decode_points; every route below -- the
-        decode, render_rays, render_occupancy, measured_occupancy -- takes its rays from here, so they agree bit for bit."""
+        decode, render_rays, render_occupancy, measured_occupancy, occupancy_at, render_occupancy_dense (volumes and
+        origins only) -- takes its rays from here, so they agree bit for bit."""
         bev_preds = self._decode_preds(pred_dict).float()
         points, batched_origin_points = self._decode_points(pred_dict, points, batched_origin_points, img_metas)
         F_, inter_num, bs, token_num, Z = bev_preds.shape
@@ -470,3 +471,30 @@ class ViDARHeadBase(ViDARHeadTemplate):
         return self._evidence(self._march(
             lambda sigma, origin, pts, tindex, step, K: ray_ops.sweep_evidence(origin, pts, tindex, rays.shape, step, K),
             rays))
+
+    @torch.no_grad()
+    def occupancy_at(self, pred_dict, points, *, extent=1.0, tgt_bev_h, tgt_bev_w, tgt_pc_range, img_metas=None,
+                     start_idx=0, batched_origin_points=None):
+        """The occupancy forecast at listed points (ray_ops.point_occupancy): for each point, how likely a return is within
+        `extent` voxel units of it along the ray from the sensor (hit), and how likely the ray goes on past it (free).
+        points: list[bs] of [N, >=4] in the layout of gt_points (xyz first, the frame label last); the rays are those
+        get_point_cloud_prediction would decode for them (_decode_rays).
+        -> list[bs] of [N, 2] (hit, free), row for row; two zeros for a point of a frame that is not predicted."""
+        rays = self._decode_rays(pred_dict, points, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range, img_metas,
+                                 batched_origin_points)
+        out = self._march(lambda *a: ray_ops.point_occupancy(*a, extent=extent), rays)
+        return [o[:p.shape[0]] for o, p in zip(out, points)]
+
+    @torch.no_grad()
+    def render_occupancy_dense(self, pred_dict, *, extent=1.0, tgt_bev_h, tgt_bev_w, tgt_pc_range, img_metas=None,
+                               start_idx=0, batched_origin_points=None):
+        """Occupancy evidence of the decoded volumes without a ray set -> [bs, F, 2, Z, H, W] fp32, hit and free
+        (ray_ops.voxel_occupancy): one ray per voxel, from the frame's origin through the voxel's centre.  The volumes and
+        origins are those of every other decode (_decode_rays).  Reads like render_occupancy's result --
+        vidar_amd.forecast.occupancy_grid -- but hit + free is a probability in [0, 1]: the softmax mass the ray still
+        has when it reaches the voxel."""
+        none = [pred_dict["next_bev_preds"].new_zeros((0, 4))] * pred_dict["next_bev_preds"].shape[-3]
+        rays = self._decode_rays(pred_dict, none, start_idx, tgt_bev_h, tgt_bev_w, tgt_pc_range, img_metas,
+                                 batched_origin_points)
+        return self._evidence(ray_ops.voxel_occupancy(rays.volumes[b], rays.origin_grids[b], self.ray_grid_step,
+                                                      self.ray_grid_num, extent) for b in range(len(rays.volumes)))

@@ -316,13 +316,17 @@ class ViDAR(nn.Module):
 
     def _occupancy_table(self, pred_dict, gt_points, cur_metas, options):
         """(table [bs, F, columns] f64 on the device, the columns' names): forecast.occupancy_score of the predicted
-        evidence of the rays forward_test decodes -- render_occupancy(end_points=gt_points) -- against the measured
-        evidence of those rays, measured_occupancy(gt_points)."""
+        evidence of the rays forward_test decodes -- render_occupancy(end_points=gt_points) --, or with
+        options["source"] == "dense" of one ray per voxel -- render_occupancy_dense, the grid a user of forecast() gets --,
+        against the measured evidence of the sweep's rays, measured_occupancy(gt_points)."""
         from ... import forecast as FC
         head = self.future_pred_head
         geom = dict(tgt_bev_h=self.bev_h, tgt_bev_w=self.bev_w, tgt_pc_range=self.point_cloud_range, img_metas=cur_metas)
-        table = FC.occupancy_score(head.render_occupancy(pred_dict, end_points=gt_points, **geom),
-                                   head.measured_occupancy(pred_dict, gt_points, **geom), **options)
+        options = dict(options)
+        source = options.pop("source", "rays")
+        pred = (head.render_occupancy_dense(pred_dict, **geom) if source == "dense"
+                else head.render_occupancy(pred_dict, end_points=gt_points, **geom))
+        table = FC.occupancy_score(pred, head.measured_occupancy(pred_dict, gt_points, **geom), **options)
         return table, FC.occupancy_columns(options.get("thresholds", FC.OCC_THRESHOLDS), options.get("bins", FC.OCC_BINS))
 
     @staticmethod
@@ -391,7 +395,11 @@ class ViDAR(nn.Module):
               softmax mass the marched rays put at each voxel (hit) and beyond it (free), and "occupancy" [bs, F, Z, H, W]
               = hit / (hit + free) where hit + free >= min_evidence, NaN (never seen, or occluded) elsewhere
               (vidar_amd.forecast.occupancy_grid).  Without it nothing more is launched and every other output keeps its
-              bits."""
+              bits.
+          occupancy="dense" needs neither rays nor cameras: one ray per voxel through its centre
+              (future_pred_head.render_occupancy_dense), so every voxel within ray_grid_num * ray_grid_step of the sensor
+              gets an answer.  Same two outputs; hit + free is then a probability -- the softmax mass the ray still has when
+              it reaches the voxel -- and min_evidence a floor under it."""
         if img_metas is None or (img is None and img_feats is None):
             raise ValueError("forecast needs img_metas and img (or img_feats)")
         from ...forecast import confidence_mask
@@ -427,16 +435,19 @@ class ViDAR(nn.Module):
         if occupancy:
             from ...forecast import occupancy_grid
             source = "sweep" if occupancy is True else occupancy
-            if source not in ("sweep", "cameras", "both"):
-                raise ValueError('occupancy must be False, True, "sweep", "cameras" or "both"')
-            if source != "cameras" and rays is None:
+            if source not in ("sweep", "cameras", "both", "dense"):
+                raise ValueError('occupancy must be False, True, "sweep", "cameras", "both" or "dense"')
+            if source in ("sweep", "both") and rays is None:
                 raise ValueError(f"occupancy={source!r} needs rays")
-            if source != "sweep" and cameras is None:
+            if source in ("cameras", "both") and cameras is None:
                 raise ValueError(f"occupancy={source!r} needs cameras")
-            dev = pred_dict["next_bev_preds"].device
-            evidence = self.future_pred_head.render_occupancy(
-                pred_dict, directions=None if source == "cameras" else rays.to(dev),
-                cameras=None if source == "sweep" else cameras, stride=stride, img_metas=cur_metas, **geom)
+            if source == "dense":
+                evidence = self.future_pred_head.render_occupancy_dense(pred_dict, img_metas=cur_metas, **geom)
+            else:
+                dev = pred_dict["next_bev_preds"].device
+                evidence = self.future_pred_head.render_occupancy(
+                    pred_dict, directions=None if source == "cameras" else rays.to(dev),
+                    cameras=None if source == "sweep" else cameras, stride=stride, img_metas=cur_metas, **geom)
             out["evidence"] = evidence
             out["occupancy"] = occupancy_grid(evidence[:, :, 0], evidence[:, :, 1], min_evidence)[0]
         return out

@@ -156,10 +156,14 @@ _occupancy_options = {}
 _OCC_OPTIONS = ("thresholds", "min_evidence", "min_meas_evidence", "min_hits", "bins")
 
 
-def set_occupancy_metrics(on, **options):
+def set_occupancy_metrics(on, source="rays", **options):
     """Make ViDAR.forward_test also score the occupancy forecast against the measured sweep: the predicted evidence of the
     very rays it decodes, the measured evidence of those rays (ViDARHeadBase.measured_occupancy) and
     forecast.occupancy_score's table, whose columns join every frame.k dictionary as additive `occ.*` entries.
+    source: where the PREDICTED evidence comes from -- "rays": the measured sweep's own ray directions
+    (render_occupancy(end_points=gt_points)); "dense": one ray per voxel (render_occupancy_dense), the grid a user of
+    ViDAR.forecast(occupancy="dense") gets, whose evidence is a probability: min_evidence is then a floor under the mass
+    the ray still has at the voxel.  The measured side is the same under both.
     options: thresholds, min_evidence, min_meas_evidence, min_hits, bins -- occupancy_score's keywords; what is not given
     keeps occupancy_score's default.  Off by default; `None` returns the decision to the environment variable
     VIDAR_OCC_METRICS.  -> the previous setting"""
@@ -167,8 +171,12 @@ def set_occupancy_metrics(on, **options):
     unknown = sorted(set(options) - set(_OCC_OPTIONS))
     if unknown:
         raise TypeError(f"set_occupancy_metrics: unknown option {unknown[0]!r}; the options are {', '.join(_OCC_OPTIONS)}")
+    if source not in ("rays", "dense"):
+        raise ValueError(f'set_occupancy_metrics: source must be "rays" or "dense", not {source!r}')
     prev, _occupancy_metrics = _occupancy_metrics, (None if on is None else bool(on))
     _occupancy_options = {k: v for k, v in options.items() if v is not None}
+    if source != "rays":
+        _occupancy_options["source"] = source      # ViDAR._occupancy_table takes it out before occupancy_score sees them
     return prev
 
 
