@@ -658,7 +658,16 @@ int vidar_conv3x3_few_f32(const float* x, const float* weight, const float* bias
 /* Fused frozen-BatchNorm epilogue of the backbone: y = act(x*scale[c] + shift[c] (+ residual)),
  * NCHW, scale = gamma/sqrt(var+eps), shift = beta - mean*scale (BN is frozen / eval in every ViDAR
  * config: vidar_1_8_nusc_1future.py:93-95).  relu: 0/1.  residual / grad_residual may be NULL.
- * bwd needs y (the forward output) for the ReLU mask; scale/shift receive no gradient (frozen). */
+ * bwd needs y (the forward output) for the ReLU mask; scale/shift receive no gradient (frozen): grad_residual =
+ * (y > 0 ? grad_y : 0), grad_x = grad_residual * scale[c]; with relu = 0, y is never read.
+ * NaN: the ReLU is fmaxf(v, 0), so with relu = 1 a NaN (NaN input, inf - inf) comes out as 0 -- as from the GEMM
+ * epilogue (csrc/gemm_mfma.hip) -- and the stem does the same; with relu = 0 it propagates.  +-inf follow IEEE.
+ * N = 0 is an empty problem (returns 0, writes nothing); N < 0, C <= 0 or HW <= 0 is VIDAR_ERR_BAD_ARG.
+ * N*C: fwd and bwd launch one grid row (gridDim.y) per channel plane and set no limit of their own; the HIP runtime
+ * takes a y extent past 65535 on gfx950 (measured: 65537 and 33 x 2048 planes give the same bits as few planes,
+ * tests/test_affine_act_gpu.py; stage 4 of the backbone on a two-sample batch has 48 x 2048).  The stem keeps its own,
+ * narrower limit (below).  Pointers need no alignment: the float4 kernels run when HW % 4 == 0 and every operand is
+ * 16-byte aligned, the scalar ones otherwise, with the same results. */
 int vidar_affine_act_fwd_f32(const float* x, const float* scale, const float* shift,
                              const float* residual, float* y, int N, int C, int HW, int relu,
                              void* stream);

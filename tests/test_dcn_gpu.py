@@ -145,15 +145,15 @@ def test_zero_offsets_equal_plain_convolution():
     torch.testing.assert_close(m(x), ref, rtol=1e-4, atol=1e-4)
 
 
-@pytest.mark.parametrize("shape,res", [((2, 8, 6, 8), True), ((1, 5, 7, 5), True), ((3, 4, 29, 50), False),
-                                       ((2, 3, 58, 100), True), ((1, 2, 116, 200), False)])
-def test_fused_frozen_bn_epilogue(shape, res):
-    """FrozenBN(x, residual, relu) == relu(batch_norm_eval(x) + residual), values and gradients."""
+def _frozen_bn_parity(shape, res, signed_gamma=False):
     from vidar_amd.plugin.backbones import FrozenBN
     import torch.nn.functional as F
     torch.manual_seed(0)
     bn = FrozenBN(shape[1]).cuda()
     bn.weight.data.uniform_(0.5, 1.5); bn.bias.data.normal_(); bn.running_mean.normal_(); bn.running_var.uniform_(0.5, 2)
+    if signed_gamma:                                  # a frozen BN weight can be negative
+        bn.weight.data.mul_(torch.where(torch.rand(shape[1], device="cuda") < 0.5, -1.0, 1.0))
+        assert bool((bn.weight < 0).any()) and bool((bn.weight > 0).any())
     x = torch.randn(*shape, device="cuda", requires_grad=True)
     r = torch.randn(*shape, device="cuda", requires_grad=True) if res else None
     y = bn(x, residual=r, relu=True)
@@ -166,6 +166,21 @@ def test_fused_frozen_bn_epilogue(shape, res):
     b = torch.autograd.grad(ref, leaves, g)
     for u, v in zip(a, b):
         torch.testing.assert_close(u, v, rtol=1e-5, atol=1e-5)
+
+
+@pytest.mark.parametrize("shape,res", [((2, 8, 6, 8), True), ((1, 5, 7, 5), True), ((3, 4, 29, 50), False),
+                                       ((2, 3, 58, 100), True), ((1, 2, 116, 200), False)])
+def test_fused_frozen_bn_epilogue(shape, res):
+    """FrozenBN(x, residual, relu) == relu(batch_norm_eval(x) + residual), values and gradients."""
+    _frozen_bn_parity(shape, res)
+
+
+@pytest.mark.parametrize("shape,res", [((33, 2048, 2, 2), True), ((33, 2048, 2, 2), False), ((2, 6, 5, 7), True)],
+                         ids=["many-planes-res", "many-planes", "small-res"])
+def test_fused_frozen_bn_negative_gamma_and_many_planes(shape, res):
+    """the same with weights of both signs, and at 33 x 2048 = 67584 channel planes, past 65535 in gridDim.y (stage 4
+    of the backbone on the 48 history images of a two-sample batch has 98304)."""
+    _frozen_bn_parity(shape, res, signed_gamma=True)
 
 
 @pytest.mark.parametrize("stride,bias", [(1, False), (2, False), (1, True)])
