@@ -266,7 +266,17 @@ int vidar_msda_fused_bwd_f32(const float* value, const int64_t* spatial_shapes,
  *   x, residual, y, sum_out [rows, C] f32 with C == 256; gamma, beta [C]; mean_out, rstd_out [rows].
  *   dropout keeps element i iff hash(seed, i) >= p (recomputed in the backward from the same seed; p = 0: exact).
  *   bwd: grad_x, grad_residual, grad_gamma, grad_beta fully written (the affine gradients from per-workgroup
- *   partial rows kept in `workspace` (vidar_drop_add_ln_bwd_workspace_bytes, scratch).
+ *   partial rows kept in `workspace` (vidar_drop_add_ln_bwd_workspace_bytes, scratch).  `workspace` must hold
+ *   vidar_drop_add_ln_bwd_workspace_bytes(rows) bytes: the call takes no size and cannot see a shorter one.
+ *   Pointers (these two entries, vidar_relu_drop_{fwd,bwd}_f32 and vidar_colsum_f32): the [rows, C] and [n] tensors,
+ *   gamma, beta, `workspace` and colsum's `x` are read and written as float4 and must sit on a 16-byte boundary; every
+ *   operand the call dereferences must be non-NULL (an empty problem, rows == 0 / n == 0, dereferences only what it
+ *   zeroes: grad_gamma, grad_beta, colsum's `out`).  Either fault, a NaN p, or p outside [0, 1) is VIDAR_ERR_BAD_ARG
+ *   before anything is launched or written.
+ *   Domain: the variance squares (sum - mean) in fp32, so a row with |dropout(x) + residual| beyond about 1e19
+ *   overflows to var = inf, rstd = 0.
+ *   grad_gamma / grad_beta are sums over rows: in the default mode their last bits depend on the order in which the
+ *   row slices meet (fp32 atomics) and can differ from run to run; under vidar_set_deterministic(1) the order is fixed.
  * ------------------------------------------------------------------------- */
 int vidar_drop_add_ln_fwd_f32(const float* x, const float* residual, const float* gamma, const float* beta, float* y,
                               float* sum_out, float* mean_out, float* rstd_out, int64_t rows, int C, float p, float eps,
@@ -282,7 +292,9 @@ size_t vidar_drop_add_ln_bwd_workspace_bytes(int64_t rows); /* scratch for the p
  * ffn_cfgs).  n elements (a multiple of 4), 0 <= p < 1; keeps element i iff hash(seed, i) >= p and scales it by
  * 1 / (1 - p) (same hash as the fused LayerNorm tail; not torch's Philox stream: dropout noise has no parity contract,
  * p = 0 is exact).  bwd: grad_x = y > 0 ? grad_y / (1 - p) : 0 -- y is the forward's OUTPUT, no mask is stored.
- * x / y and grad_y / grad_x may alias. */
+ * x / y and grad_y / grad_x may alias.  The ReLU is fmaxf(x, 0), the rule of vidar_affine_act_fwd_f32: a NaN comes out
+ * as 0 where torch.relu gives NaN.  A dropped element is relu(x) * 0, so a dropped +inf comes out as NaN (a kept one as
+ * +inf), and the backward, which asks y > 0, gives such an element the gradient 0. */
 int vidar_relu_drop_fwd_f32(const float* x, float* y, int64_t n, float p, uint32_t seed, void* stream);
 int vidar_relu_drop_bwd_f32(const float* grad_y, const float* y, float* grad_x, int64_t n, float p, void* stream);
 

@@ -33,6 +33,9 @@ def reference(x, w, b):
     (1, 8, 3, 191, 3, True),           # the widest supported row
     (3, 8, 2, 1, 5, True),             # one-pixel rows: left and right padding on the same pixel
     (1, 24, 131, 33, 1, True),         # many tiles per image, a single output
+    # both sides of every boundary of ITERS = (193 + 2 W) / 64, the template argument of the kernel: 3 up to W = 31,
+    # 4 to 63, 5 to 95, 6 to 127, 7 to 159, 8 to 191 (5 and 7 run nowhere else)
+    *[(1, 8, 3, W, 27, True) for W in (31, 32, 63, 64, 95, 96, 127, 128, 159, 160)],
 ])
 def test_forward_matches_fp64_convolution(N, C, H, W, cout, with_bias):
     g = torch.Generator().manual_seed(N * 1000 + C + H * W)
@@ -44,6 +47,23 @@ def test_forward_matches_fp64_convolution(N, C, H, W, cout, with_bias):
     assert torch.isfinite(got).all()
     scale = float(ref.abs().max())
     assert float((got - ref).abs().max()) <= 1e-5 * scale
+
+
+@pytest.mark.parametrize("W", [1, 2, 70, 130])
+def test_all_ones_count_the_taps_inside_the_image(W):
+    """x = w = 1, no bias, C = 8: every output is 8 x (taps that fall inside the image), small integers with no
+    tolerance -- 32 at a corner, 48 on an edge, 72 inside (fewer where the image is one or two pixels wide); a padding
+    slip that random data shows only statistically changes a count"""
+    H, C, cout = 5, 8, 27
+    x = torch.ones(1, C, H, W, device="cuda")
+    w = torch.ones(cout, C, 3, 3, device="cuda")
+    got = call(x, w, None).cpu()
+    rows = torch.tensor([2.0] + [3.0] * (H - 2) + [2.0])
+    cols = torch.tensor([min(3, W, c + 2, W - c + 1) for c in range(W)], dtype=torch.float32)
+    want = (C * rows[:, None] * cols[None, :]).expand(1, cout, H, W)
+    assert torch.equal(got, want)
+    if W >= 3:
+        assert float(got[0, 0, 0, 0]) == 32 and float(got[0, 0, 0, 1]) == 48 and float(got[0, 0, 2, 1]) == 72
 
 
 def test_empty_batch_and_limits():

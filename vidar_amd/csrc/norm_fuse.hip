@@ -259,14 +259,23 @@ __global__ __launch_bounds__(256) void relu_drop_bwd_kernel(const float4* __rest
   }
 }
 
+// The entries' pointer contract, tested before any launch or memset: an operand the call would dereference is not NULL,
+// and one the kernels read or write as float4 (`vec`) sits on a 16-byte boundary.
+template <typename... P> bool given(P... p) { return ((p != nullptr) && ...); }
+template <typename... P> bool vec(P... p) {
+  return ((p != nullptr && (reinterpret_cast<uintptr_t>(p) & 15) == 0) && ...);
+}
+inline bool drop_p_ok(float p) { return p >= 0.f && p < 1.f; }   // false for a NaN
+
 }  // namespace
 
 extern "C" {
 
 int vidar_relu_drop_fwd_f32(const float* x, float* y, int64_t n, float p, uint32_t seed, void* stream) {
   VIDAR_ENTER();
-  if (n < 0 || n % 4 != 0 || !(p >= 0.f) || p >= 1.f) return VIDAR_ERR_BAD_ARG;
+  if (n < 0 || n % 4 != 0 || !drop_p_ok(p)) return VIDAR_ERR_BAD_ARG;
   if (n == 0) return 0;
+  if (!vec(x, y)) return VIDAR_ERR_BAD_ARG;
   const int64_t n4 = n / 4;
   const unsigned grid = (unsigned)(n4 / 256 + 1 < 16384 ? n4 / 256 + 1 : 16384);
   hipLaunchKernelGGL(relu_drop_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,
@@ -276,8 +285,9 @@ int vidar_relu_drop_fwd_f32(const float* x, float* y, int64_t n, float p, uint32
 
 int vidar_relu_drop_bwd_f32(const float* grad_y, const float* y, float* grad_x, int64_t n, float p, void* stream) {
   VIDAR_ENTER();
-  if (n < 0 || n % 4 != 0 || !(p >= 0.f) || p >= 1.f) return VIDAR_ERR_BAD_ARG;
+  if (n < 0 || n % 4 != 0 || !drop_p_ok(p)) return VIDAR_ERR_BAD_ARG;
   if (n == 0) return 0;
+  if (!vec(grad_y, y, grad_x)) return VIDAR_ERR_BAD_ARG;
   const int64_t n4 = n / 4;
   const unsigned grid = (unsigned)(n4 / 256 + 1 < 16384 ? n4 / 256 + 1 : 16384);
   hipLaunchKernelGGL(relu_drop_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,
@@ -292,6 +302,7 @@ int vidar_colsum_f32(const float* x, float* out, int64_t rows, int cols, void* s
   const int groups = cols / 4;
   if (rows < 0 || cols <= 0 || cols % 4 != 0 || (groups & (groups - 1)) != 0 || groups > kColsumThreads)
     return VIDAR_ERR_BAD_ARG;
+  if (!given(out) || (rows > 0 && !vec(x))) return VIDAR_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)cols, s);
   if (e != hipSuccess) return (int)e;
@@ -307,8 +318,9 @@ int vidar_drop_add_ln_fwd_f32(const float* x, const float* residual, const float
                               float* sum_out, float* mean_out, float* rstd_out, int64_t rows, int C, float p, float eps,
                               uint32_t seed, void* stream) {
   VIDAR_ENTER();
-  if (rows < 0 || C != kC || p < 0.f || p >= 1.f) return VIDAR_ERR_BAD_ARG;
+  if (rows < 0 || C != kC || !drop_p_ok(p)) return VIDAR_ERR_BAD_ARG;
   if (rows == 0) return 0;
+  if (!vec(x, residual, gamma, beta, y, sum_out) || !given(mean_out, rstd_out)) return VIDAR_ERR_BAD_ARG;
   hipLaunchKernelGGL(drop_add_ln_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x,
                      residual, gamma, beta, y, sum_out, mean_out, rstd_out, rows, p, eps, seed);
   return vidar_last_error();
@@ -325,14 +337,15 @@ int vidar_drop_add_ln_bwd_f32(const float* grad_y, const float* sum_in, const fl
                               float* grad_beta, void* workspace, int64_t rows, int C, float p, uint32_t seed,
                               void* stream) {
   VIDAR_ENTER();
-  if (rows < 0 || C != kC || p < 0.f || p >= 1.f) return VIDAR_ERR_BAD_ARG;
+  if (rows < 0 || C != kC || !drop_p_ok(p) || !given(grad_gamma, grad_beta)) return VIDAR_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (rows == 0) {
     hipError_t e = hipMemsetAsync(grad_gamma, 0, sizeof(float) * kC, s);
     if (e == hipSuccess) e = hipMemsetAsync(grad_beta, 0, sizeof(float) * kC, s);
     return (int)e;
   }
-  if (!workspace) return VIDAR_ERR_BAD_ARG;
+  if (!vec(grad_y, sum_in, gamma, grad_x, grad_residual, workspace) || !given(mean_in, rstd_in))
+    return VIDAR_ERR_BAD_ARG;
   const int64_t waves = (rows + kRowsPerWave - 1) / kRowsPerWave;
   const int nparts = (int)((waves + 3) / 4);
   hipLaunchKernelGGL(drop_add_ln_bwd_kernel, dim3((unsigned)nparts), dim3(256), 0, s, grad_y, sum_in, gamma, mean_in,

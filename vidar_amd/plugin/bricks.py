@@ -118,6 +118,13 @@ class Linear(nn.Linear):
         return F.relu(y, inplace=True) if relu else y
 
 
+def _vec(t):
+    """`t` contiguous on a 16-byte boundary (the kernels of csrc/norm_fuse.hip read float4, and the entries refuse anything
+    else); a contiguous view that starts elsewhere in its storage is cloned"""
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
 class _ReluDropout(torch.autograd.Function):
     """dropout(relu(x), p) as one HIP pass each way (csrc/norm_fuse.hip: vidar_relu_drop_{fwd,bwd}_f32); the backward reads
     the saved OUTPUT (which the next Linear saves anyway) instead of a mask."""
@@ -125,7 +132,7 @@ class _ReluDropout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p, seed):
         from .._lib import lib, check, ptr, stream_of
-        x = x.contiguous()
+        x = _vec(x)
         y = torch.empty_like(x)
         check(lib().vidar_relu_drop_fwd_f32(ptr(x), ptr(y), x.numel(), p, seed, stream_of(x)), "relu_drop_fwd")
         ctx.save_for_backward(y)
@@ -136,7 +143,7 @@ class _ReluDropout(torch.autograd.Function):
     def backward(ctx, gy):
         from .._lib import lib, check, ptr, stream_of
         y, = ctx.saved_tensors
-        gy = gy.contiguous()
+        gy = _vec(gy)
         gx = torch.empty_like(gy)
         check(lib().vidar_relu_drop_bwd_f32(ptr(gy), ptr(y), ptr(gx), gy.numel(), ctx.p, stream_of(gy)), "relu_drop_bwd")
         return gx, None, None
@@ -262,7 +269,7 @@ class _DropAddLayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, gamma, beta, p, eps, seed):
         from .._lib import lib, check, ptr, stream_of
-        x, residual = x.contiguous(), residual.contiguous()
+        x, residual, gamma, beta = _vec(x), _vec(residual), _vec(gamma), _vec(beta)
         rows = x.numel() // 256
         y = torch.empty_like(x); s = torch.empty_like(x)
         mean = torch.empty(rows, device=x.device); rstd = torch.empty(rows, device=x.device)
@@ -277,7 +284,7 @@ class _DropAddLayerNorm(torch.autograd.Function):
         from .._lib import lib, check, ptr, stream_of, workspace
         s, gamma, mean, rstd = ctx.saved_tensors
         p, seed, rows = ctx.cfg
-        gy = gy.contiguous()
+        gy = _vec(gy)
         gx = torch.empty_like(s); gres = torch.empty_like(s)
         dgamma = torch.empty_like(gamma); dbeta = torch.empty_like(gamma)
         deterministic.sync()                 # in the mode the partial rows of dgamma / dbeta are summed in a fixed order
